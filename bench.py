@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- node-state updates/sec of the sparse GGNN propagation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode forward|train] [--n1-value V1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode forward|train] [--n1-value V1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: it sets up, warms up, times the K steps, writes the last timed step's outputs if
+--dump-outputs is given and prints the JSON line.  --full adds every other leg listed below (one-stream figure, roofline
+and per-kernel tables, fresh-batch epochs, the other mode, secondary configs, exact-format and mean-9 children, CPU
+baseline); --no-roofline / --no-secondary / --no-cpu-baseline leave legs of a --full run out.
 
 Started as plain `python bench.py --gpus N` with N > 1 (no WORLD_SIZE in the environment) it launches its own N ranks through
 torch.distributed.run on 127.0.0.1 and exits with their status; `ranks_seen` on the JSON line is the size of the process
@@ -18,11 +23,16 @@ metric value = nodes * 8 / time, whole job (all ranks).  Multi-GPU: graphs are i
 disjoint batches and the forward path has no collective ("scaling": "weak", per-GPU batch fixed).
 
 Timing: every resident batch is run once before anything is timed (whatever --warmup says), then W warm-up steps, then
-the K-step loop is timed `timed_repeats` times back to back inside ONE barrier/synchronize bracket -- as often as
-it takes to reach --min-time seconds (a 20-step loop is 25 ms, too short to be stable across boxes) -- and
-ms_per_step / value are taken over all `steps_timed` = K * timed_repeats steps.
+exactly K steps are timed inside ONE barrier/synchronize bracket, and ms_per_step / value are taken over them.  With
+--min-time S > 0 (experiments; off by default) an untimed K-step calibration loop follows the warm-up and the K-step
+loop is timed `timed_repeats` times back to back, as often as it takes to reach S seconds; `steps_timed` = K * timed_repeats.
 
-Also on the JSON line:
+--dump-outputs DIR: after the timed steps, what the last timed step returned is written as float32 .npy files -- forward:
+DIR/final_node_representations.npy ([nodes, hidden] of that step's batch); train: DIR/loss.npy and DIR/var__<name>.npy for
+every trainable variable after the step.  Inputs and weights are seeded, so the same arguments give the same inputs on
+every run.  Rank 0 only; an array beyond the size cap is replaced by a fixed, seeded sample of its rows.
+
+Also on the JSON line of a --full run:
   roofline      -- the dominant kernel (by measured time): algorithmic flops (or bytes) per launch /
                    its average launch duration, measured live with HIP events on the launch stream; `traffic` from
                    the newest profiles/*_pmc_summary.json, only if it was recorded for the kernel sources in this tree.
@@ -85,7 +95,14 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--mode", choices=("forward", "train"), default="forward",
                     help="forward: the propagation (headline metric); train: the full optimisation step incl. the RCCL all-reduce")
-    ap.add_argument("--min-time", type=float, default=0.5, help="minimum duration of the timed region in seconds")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="experiments: repeat the timed K-step loop until it lasts this many seconds (0: exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (one stream, roofline, fresh batches, other mode, secondary, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--detail-file", metavar="PATH", default=None,
+                    help="also write the full record (with --full: per-kernel tables, secondary configs, sweeps) to PATH as JSON")
     ap.add_argument("--mean-nodes", type=float, default=18.0, help="mean atoms per molecule (18 = QM9 with H)")
     ap.add_argument("--batches", type=int, default=6, help="distinct resident batches to cycle through")
     ap.add_argument("--streams", type=int, default=2, help="HIP streams the independent batches are issued on")
@@ -100,7 +117,10 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="no kernels: rendezvous, per-rank data sharding, the flat gradient all-reduce and the timing bracket only "
                          "(runs on CPU over gloo; exercises the N-rank launch path where there is no GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def respawn_as_ranks(args):
@@ -417,7 +437,8 @@ def child_line(args, env_extra, argv_extra, run=subprocess.run, timeout=180):
     legs then share nothing but the box."""
     env = dict(os.environ, GGNN_BENCH_CHILD="1", **env_extra)
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--min-time", "0.3", "--streams", str(args.streams), "--batches", str(args.batches), "--no-secondary", "--no-cpu-baseline"] + argv_extra
+           "--min-time", "0.3", "--streams", str(args.streams), "--batches", str(args.batches), "--full", "--no-secondary",
+           "--no-cpu-baseline"] + argv_extra
     r = run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -501,19 +522,37 @@ def compact_line(out, detail_file):
     return line
 
 
-def emit(out):
-    """Full record -> gpurun_out/bench_detail.json (best effort) and stderr; the compact line -> stdout, LAST."""
+def emit(out, detail_path=None):
+    """Full record -> stderr and, if given, `detail_path` (best effort); the compact line -> stdout, LAST."""
     detail_file = None
-    try:
-        d = os.path.join(ROOT, "gpurun_out")
-        os.makedirs(d, exist_ok=True)
-        detail_file = os.path.join("gpurun_out", "bench_detail.json")
-        with open(os.path.join(ROOT, detail_file), "w") as fh:
-            json.dump(out, fh)
-    except Exception:
-        detail_file = None
+    if detail_path:
+        try:
+            d = os.path.dirname(os.path.abspath(detail_path))
+            os.makedirs(d, exist_ok=True)
+            with open(detail_path, "w") as fh:
+                json.dump(out, fh)
+            detail_file = detail_path
+        except Exception:
+            detail_file = None
     print("[bench detail] " + json.dumps(out), file=sys.stderr, flush=True)
     print(json.dumps(compact_line(out, detail_file)), flush=True)
+
+
+DUMP_BYTES_MAX = 60 << 20          # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} to out_dir/<name>.npy as float32.  If they exceed DUMP_BYTES_MAX together, every array longer
+    than its share of the budget keeps a fixed, seeded sample of its rows (sorted; the same rows on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy().reshape(v.shape if v.dim() else (1,)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_BYTES_MAX // max(len(host), 1)
+    for name, a in host.items():
+        if total > DUMP_BYTES_MAX and a.nbytes > share and a.shape[0] > 1:
+            rows = max(1, share // max(a.nbytes // a.shape[0], 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def ranks_seen(dist_ctx):
@@ -655,8 +694,9 @@ def main():
         return model.train_batch(train_feeds[i % len(train_feeds)])
 
     def timed_region(step, steps, warmup, min_time, no_grad):
-        """barrier + synchronize | `repeats` x K steps | synchronize + barrier; MAX over ranks.  The repeat count is
-        agreed between the ranks from a calibration pass (one untimed K-step loop)."""
+        """barrier + synchronize | `repeats` x K steps | synchronize + barrier; MAX over ranks.  repeats = 1 unless min_time > 0:
+        then the repeat count is agreed between the ranks from a calibration pass (one untimed K-step loop).
+        -> (elapsed seconds, repeats, what the last timed step returned)."""
         ctx = torch.no_grad() if no_grad else torch.enable_grad()
         with ctx:
             if streams is not None:
@@ -666,14 +706,16 @@ def main():
                 step(i)
             for i in range(warmup):
                 step(i)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(steps):                                              # calibration (also warm-up)
-                step(i)
-            torch.cuda.synchronize()
-            cal = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist_ctx.all_reduce_max_(cal)
-            repeats = max(1, int(np.ceil(min_time / max(float(cal.item()), 1e-6))))
+            repeats = 1
+            if min_time > 0:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):                                          # calibration (also warm-up)
+                    step(i)
+                torch.cuda.synchronize()
+                cal = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+                dist_ctx.all_reduce_max_(cal)
+                repeats = max(1, int(np.ceil(min_time / max(float(cal.item()), 1e-6))))
             # One generation-2 pass of Python's cyclic garbage collector over the interpreter's long-lived objects
             # (torch, numpy, the model) blocks the host for ~45 ms; the launch queue runs dry and a short timed
             # region reads 20-40 % slow (tools/stream_jitter.py).  Nothing in the timed region creates reference cycles.
@@ -685,8 +727,10 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(repeats):
-                for i in range(steps):
+                last = None
+                for i in range(steps - 1):
                     step(i)
+                last = step(steps - 1)                                          # (held: the only result kept, for --dump-outputs)
             torch.cuda.synchronize()
             dist_ctx.barrier()
             torch.cuda.synchronize()
@@ -694,7 +738,7 @@ def main():
             gc.enable()
         el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist_ctx.all_reduce_max_(el)
-        return float(el.item()), repeats
+        return float(el.item()), repeats, last
 
     def totals(steps_timed):
         my_nodes = sum(nodes[i % len(feeds)] for i in range(args.steps)) * (steps_timed // args.steps)
@@ -704,8 +748,16 @@ def main():
         return float(tot[0].item()), float(tot[1].item())
 
     headline_train = args.mode == "train"
-    elapsed, repeats = timed_region(train_step if headline_train else fwd_step, args.steps, args.warmup, args.min_time,
-                                    no_grad=not headline_train)
+    elapsed, repeats, last = timed_region(train_step if headline_train else fwd_step, args.steps, args.warmup, args.min_time,
+                                          no_grad=not headline_train)
+    if args.dump_outputs and rank == 0:
+        if headline_train:                  # the step's loss and the variables it left behind
+            dumped = {"loss": last}
+            dumped.update({"var__" + "".join(c if c.isalnum() else "_" for c in n): v for n, v in model.named_variables().items()})
+        else:
+            dumped = {"final_node_representations": last}
+        dump_outputs(args.dump_outputs, dumped)
+    del last
     steps_timed = args.steps * repeats
     total_nodes, total_graphs = totals(steps_timed)
     value = total_nodes * n_prop / elapsed
@@ -730,8 +782,9 @@ def main():
     # batch's launches).  The same loop on ONE stream, timed the same way: the difference is that overlap, and it is why the
     # per-launch kernel times of the roofline leg (one stream, launches strictly in sequence) can add up to more than ms_per_step.
     one_stream = None
-    if not headline_train and streams is not None:
-        el1, rep1 = timed_region(lambda i: fwd_step(i, multi=False), args.steps, 2, min(args.min_time, 0.25), no_grad=True)
+    if args.full and not headline_train and streams is not None:
+        el1, rep1, _ = timed_region(lambda i: fwd_step(i, multi=False), args.steps, 2,
+                                    min(args.min_time, 0.25) if args.min_time > 0 else 0.25, no_grad=True)
         one_stream = el1 / (args.steps * rep1) * 1e3
 
     what = ("sparse GGNN TRAINING step (forward + backward + gradient all-reduce + per-variable clip + Adam)" if headline_train
@@ -768,7 +821,7 @@ def main():
 
     # ---- index prep / packing outside the timed region, and the rate with them inside (rank 0) ----------------------
     # (before the training leg: after a few seconds of training steps the same leg measures ~4 % lower -- clocks, not code)
-    if rank == 0 and not headline_train and not os.environ.get("GGNN_BENCH_CHILD"):
+    if args.full and rank == 0 and not headline_train and not os.environ.get("GGNN_BENCH_CHILD"):
         ops = pkg.ops
         for warm in (True, False):
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -856,23 +909,23 @@ def main():
                     "fills and drains once per epoch); one_stream_value: packing and forward in sequence on one stream"}
 
     # ---- the other mode, short: forward runs get a `train` object, train runs a `forward` object (all ranks: it holds the collective)
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         o_steps = max(4, min(args.steps, 12))
         if headline_train:
-            el2, rep2 = timed_region(fwd_step, o_steps, 2, 0.2, no_grad=True)
+            el2, rep2, _ = timed_region(fwd_step, o_steps, 2, 0.2, no_grad=True)
             n2 = sum(nodes[i % len(feeds)] for i in range(o_steps)) * rep2
             t2 = torch.tensor([n2], dtype=torch.float64, device=dev); dist_ctx.all_reduce_sum_(t2)
             out["forward"] = {"value": float(t2.item()) * n_prop / el2, "unit": "node-state updates/s", "ms_per_step": el2 / (o_steps * rep2) * 1e3,
                               "steps_timed": o_steps * rep2}
         else:
-            el2, rep2 = timed_region(train_step, o_steps, 2, 0.3, no_grad=False)
+            el2, rep2, _ = timed_region(train_step, o_steps, 2, 0.3, no_grad=False)
             n2 = sum(nodes[i % len(feeds)] for i in range(o_steps)) * rep2
             t2 = torch.tensor([n2], dtype=torch.float64, device=dev); dist_ctx.all_reduce_sum_(t2)
             out["train"] = {"what": "forward + backward + flat gradient all-reduce (RCCL, N > 1) + per-variable clip + Adam, one batch per rank per step",
                             "value": float(t2.item()) * n_prop / el2, "unit": "node-state updates/s",
                             "ms_per_step": el2 / (o_steps * rep2) * 1e3, "steps_timed": o_steps * rep2, "n_gpus": world}
     # the gradient all-reduce on its own (HIP events around DataParallelContext.reduce_gradients), all ranks take part
-    if world > 1 and (headline_train or not args.no_secondary):
+    if args.full and world > 1 and (headline_train or not args.no_secondary):
         variables = list(model.trainable_variables.values())
         gbuf = [torch.zeros_like(v) for v in variables]
         ev = []
@@ -888,7 +941,7 @@ def main():
         out["allreduce_us"] = rec["allreduce_us"]
 
     # ---- roofline leg: per-launch HIP-event timing of every kernel (rank 0) -----------------------------
-    if rank == 0 and not args.no_roofline and not headline_train:
+    if args.full and rank == 0 and not args.no_roofline and not headline_train:
         reps = max(4, min(args.steps, 12))
         with torch.no_grad(), pkg.ops.kernel_timing():
             fwd_step(0, multi=False)          # untimed: the per-step entry points' first launches (one-off set-up)
@@ -963,7 +1016,7 @@ def main():
         out["kernel_time_ms_per_step"] = tot_ms / reps
 
     # ---- secondary configs (rank 0, N = 1) ----------------------------------------------------------------------------
-    if rank == 0 and world == 1 and not args.no_secondary and not headline_train:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not headline_train:
         sec = {}
         for key, fn in (("config3_dense_b256", secondary_dense), ("config5_large_graph_h256", secondary_large)):
             try:
@@ -978,7 +1031,7 @@ def main():
             out["secondary"]["config1_mean9_molecules"] = small_molecule_reference(args)
 
     # ---- CPU baseline leg: torch-CPU port of the reference op order, bounded sample (rank 0, N=1) ---------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import ggnn_oracle_torch as OT       # the reported baseline; never the thing measured above
         f = feeds[0]
@@ -1026,7 +1079,7 @@ def main():
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
 
     if rank == 0:
-        emit(out)
+        emit(out, args.detail_file)
     if world > 1:
         dist_ctx.barrier()          # rank 0 was still busy with the roofline leg: leave together
         torch.distributed.destroy_process_group()

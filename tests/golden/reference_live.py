@@ -1,5 +1,5 @@
-"""Driver run in a SUBPROCESS by tests/test_reference_live.py (only where /root/reference exists): constructs the
-reference's own model class over the TF-1.3 op shim and either
+"""Driver run in a SUBPROCESS by tests/golden/make_reference_live_golden.py (with GGNN_REFERENCE_DIR = a checkout of the
+reference): constructs the reference's own model class over the TF-1.3 op shim and either
 
     restore <kind> <data_dir> <checkpoint.pickle> <out.npz>
         builds the reference model with --restore <checkpoint> (chem_tensorflow.py:330-359: by-name assignment of every
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 
 def main():
     mode, kind, data_dir = sys.argv[1:4]
-    sys.path[:0] = [os.path.join(ROOT, "oracle", "tf13_shim"), "/root/reference"]
+    sys.path[:0] = [os.path.join(ROOT, "oracle", "tf13_shim"), os.environ["GGNN_REFERENCE_DIR"]]
     import numpy as np
     import tensorflow as tf
     assert tf.__version__.endswith("shim")

@@ -139,7 +139,7 @@ def test_bench_two_ranks_on_one_gpu(cuda):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GGNN_LOCAL_DEVICE="0", GGNN_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--batches", "2",
-                        "--min-time", "0.05", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--min-time", "0.05", "--full", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["value"] > 0

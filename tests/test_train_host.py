@@ -57,10 +57,17 @@ class _ToyModel:
         self.ops["loss_denominator_task0"] = mask.sum()
 
 
+def _host_rank():
+    """The gloo workers below rehearse the host side of data parallelism on CPU tensors: they must not claim cuda:<rank>,
+    which a box with fewer GPUs than ranks does not have.  (Spawned process: the patch dies with it.)"""
+    torch.cuda.is_available = lambda: False
+
+
 def _dp_worker(rank, world, port, ret):
     import importlib
     pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _host_rank()
     ctx = pkg.parallel.DataParallelContext.from_env(backend="gloo")
     g = torch.Generator().manual_seed(0)
     X = torch.randn(10, 4, generator=g, dtype=torch.float64); Y = torch.randn(10, generator=g, dtype=torch.float64)
@@ -104,6 +111,7 @@ def _dp8_worker(rank, world, port, ret):
     pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(1)
+    _host_rank()
     ctx = pkg.parallel.DataParallelContext.from_env(backend="gloo")
     ms = pkg.synthetic_qm9(900, mean_nodes=12, seed=5)
     params = {"batch_size": 1000, "hidden_size": 100}
@@ -318,6 +326,7 @@ def _epoch_stats_worker(rank, world, port, ret):
     import types
     pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _host_rank()
     ctx = pkg.parallel.DataParallelContext.from_env(backend="gloo")
     stub = types.SimpleNamespace(params={"task_ids": [0, 1], "task_sample_ratios": {}}, dist=ctx)
     rng = np.random.default_rng(7)                                 # the same stream on both ranks: [step, rank, ...]
@@ -385,6 +394,7 @@ def test_bench_spawns_its_own_ranks_dry_run():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GGNN_LOCAL_DEVICE="0", GGNN_DIST_BACKEND="gloo")           # (a box with fewer GPUs than ranks: all on device 0, gloo)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -404,6 +414,7 @@ def test_bench_gpus_8_dry_run():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GGNN_LOCAL_DEVICE="0", GGNN_DIST_BACKEND="gloo")           # (a box with fewer GPUs than ranks: all on device 0, gloo)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "2", "--n1-value", "1.25e9"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

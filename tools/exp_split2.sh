@@ -16,8 +16,8 @@ for v in "" s2; do
     echo "== variant=${v:-default}" >> $OUT/fwd.txt;   GGNN_LIB_VARIANT=$v timeout 300 python tools/fwd_kernels.py >> $OUT/fwd.txt 2>&1
     echo "== variant=${v:-default}" >> $OUT/probe.txt; GGNN_LIB_VARIANT=$v timeout 300 python tools/split_probe.py 2>&1 | tail -3 >> $OUT/probe.txt
 done
-GGNN_LIB_VARIANT=s2 timeout 300 python bench.py --no-secondary > $OUT/bench_s2.json 2> $OUT/bench_s2.err
-timeout 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+GGNN_LIB_VARIANT=s2 timeout 300 python bench.py --full --no-secondary > $OUT/bench_s2.json 2> $OUT/bench_s2.err
+timeout 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 # the inference parity tests on the variant, tolerances unchanged
 GGNN_LIB_VARIANT=s2 timeout 300 python -m pytest tests/test_gpu_parity.py -q -x --deselect tests/test_gpu_parity.py::test_library_loaded \
     -k "test_gru or test_msg_transform or test_sparse_model_matches_oracle or test_random_model_shapes_match_oracle or test_golden_fixture_on_gpu or test_full_size_batch_properties or test_compact_transform" \

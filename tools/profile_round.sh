@@ -35,9 +35,9 @@ for leg in $LEGS; do
 case $leg in
 bench)
     # (the roofline leg stays on: it also launches the stand-alone scatter-add kernel, which the timed path fuses away)
-    timeout 900 python "$ROOT/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout 900 python "$ROOT/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
     tail -1 "$OUT/bench.json" | cut -c1-600
-    four_passes "" python "$ROOT/bench.py" --steps 12 --warmup 4 --streams 1 --min-time 0 --no-cpu-baseline --no-secondary ;;
+    four_passes "" python "$ROOT/bench.py" --full --steps 12 --warmup 4 --streams 1 --min-time 0 --no-cpu-baseline --no-secondary ;;
 large) four_passes config5_ python "$ROOT/tools/bench_extra.py" large ;;
 dense) four_passes config3_ python "$ROOT/tools/bench_extra.py" dense ;;
 train)
