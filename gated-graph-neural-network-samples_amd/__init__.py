@@ -11,7 +11,7 @@ import sys as _sys
 
 _ALIAS = "ggnn_amd"
 _SUBMODULES = ["_lib", "data", "utils", "ops", "formats", "data_device", "autograd", "backward", "train", "train_native", "chem_model", "sparse_model",
-               "dense_model", "parallel", "build"]
+               "dense_model", "gcn_model", "parallel", "build"]
 
 _sys.modules.setdefault(_ALIAS, _sys.modules[__name__])
 for _m in _SUBMODULES:
@@ -21,7 +21,8 @@ for _m in _SUBMODULES:
 from .chem_model import ChemModel                                   # noqa: E402
 from .sparse_model import SparseGGNNChemModel, GGNNWeights          # noqa: E402
 from .dense_model import DenseGGNNChemModel                         # noqa: E402
+from .gcn_model import SparseGCNChemModel                           # noqa: E402
 from .data import MoleculeSet, synthetic_qm9, synthetic_large_graph, pack_batches          # noqa: E402
 
-__all__ = ["ChemModel", "SparseGGNNChemModel", "DenseGGNNChemModel", "GGNNWeights", "MoleculeSet",
+__all__ = ["ChemModel", "SparseGGNNChemModel", "DenseGGNNChemModel", "SparseGCNChemModel", "GGNNWeights", "MoleculeSet",
            "synthetic_qm9", "synthetic_large_graph", "pack_batches"]

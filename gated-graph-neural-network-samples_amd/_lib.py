@@ -140,6 +140,15 @@ SYMBOLS = {
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p]),
     "ggnn_dropout_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_float, c_int64, c_int, c_void_p]),
+    "ggnn_gcn_fused_supported": (c_int, [c_int]),
+    "ggnn_gcn_image_bytes": (c_size_t, [c_int]),
+    "ggnn_gcn_pack_weights_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                   c_uint64, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ggnn_gcn_epilogue_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_uint64, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "ggnn_gcn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ggnn_gcn_propagate_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p),
+                                       POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

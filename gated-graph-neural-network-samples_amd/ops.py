@@ -1254,3 +1254,145 @@ def cudnn_gru(x_segs: Sequence[torch.Tensor], h: torch.Tensor, Wg, bg, Wcx, bcx,
     _launch("cudnn_gru[nx=%d]" % nx, lambda: lib.ggnn_cudnn_gru_f32(segs, nx, _ptr(h), _ptr(Wg), _ptr(bg), _ptr(Wcx), _ptr(bcx),
                                                                     _ptr(Wch), _ptr(bch), _ptr(out), _ptr(ws), ws_bytes, V, D, _stream()))
     return out
+
+
+# ---- sparse GCN (chem_tensorflow_gcn.py:62-82; csrc/ggnn_gcn.hip) -----------------------------------------------------------------
+class GCNGraph:
+    """A_hat of one batch as CSR (row_ptr, col, val) and its transpose (row_ptr_t, col_t, val_t), device tensors.  The backward pass
+    multiplies by A_hat^T, which need not equal A_hat for a user feed.  slot_ids / slot_ids_t (0 .. nnz-1) are the per-slot weight ids
+    of the composed path's ggnn_weighted_segment_sum_f32."""
+
+    def __init__(self, row_ptr, col, val, row_ptr_t, col_t, val_t, num_nodes: int):
+        self.row_ptr, self.col, self.val = row_ptr, col, val
+        self.row_ptr_t, self.col_t, self.val_t = row_ptr_t, col_t, val_t
+        self.num_nodes = int(num_nodes)
+        self.nnz = int(col.numel())
+        self._slots = None
+
+    def slot_ids(self) -> torch.Tensor:
+        if self._slots is None:
+            self._slots = torch.arange(self.nnz, dtype=torch.int32, device=self.col.device)
+        return self._slots
+
+
+def gcn_csr_host(adjacency_list, adjacency_weights, num_nodes: int):
+    """NumPy CSR of the sparse matrix with entries (adjacency_list[k] = (i, j), adjacency_weights[k]) and of its transpose:
+    -> (row_ptr, col, val, row_ptr_t, col_t, val_t).  Entries keep their feed order inside a row (a stable sort by row; the packer's
+    lists are row-major sorted already), so every row is summed in the order tf.sparse_tensor_dense_matmul sees its nonzeros.
+    Indices outside [0, num_nodes) raise."""
+    import numpy as np
+    adj = np.asarray(adjacency_list, dtype=np.int64).reshape(-1, 2)
+    w = np.asarray(adjacency_weights, dtype=np.float32).reshape(-1)
+    if adj.shape[0] != w.shape[0]:
+        raise ValueError("adjacency_list and adjacency_weights differ in length")
+    V = int(num_nodes)
+    if adj.size and (adj.min() < 0 or adj.max() >= V):
+        raise IndexError("adjacency_list holds a node index outside [0, %d)" % V)
+    if adj.shape[0] >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 nonzeros")
+
+    def csr(rows, cols, vals):
+        order = np.argsort(rows, kind="stable")
+        ptr = np.zeros(V + 1, np.int32)
+        np.cumsum(np.bincount(rows, minlength=V), out=ptr[1:])
+        return ptr, cols[order].astype(np.int32), vals[order]
+
+    rp, c, v = csr(adj[:, 0], adj[:, 1], w)
+    # transpose of the row-sorted matrix: stable by column, i.e. row-ascending inside each transposed row
+    rows_sorted = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    rpt, ct, vt = csr(c.astype(np.int64), rows_sorted, v)
+    return rp, c, v, rpt, ct, vt
+
+
+def gcn_graph(adjacency_list, adjacency_weights, num_nodes: int, device) -> GCNGraph:
+    """GCNGraph of a fed (adjacency_list [nnz, 2], adjacency_weights [nnz]) pair (NumPy or tensors), uploaded to `device`."""
+    if isinstance(adjacency_list, torch.Tensor):
+        adjacency_list = adjacency_list.cpu().numpy()
+    if isinstance(adjacency_weights, torch.Tensor):
+        adjacency_weights = adjacency_weights.cpu().numpy()
+    parts = gcn_csr_host(adjacency_list, adjacency_weights, num_nodes)
+    return GCNGraph(*[torch.from_numpy(p).to(device) for p in parts], num_nodes)
+
+
+def gcn_fused_supported(D: int) -> bool:
+    return bool(_lib.load().ggnn_gcn_fused_supported(int(D)))
+
+
+def gcn_pack(W: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """LDS image of W [D, D] (or of W^T) for the fused GCN layer."""
+    lib = _lib.load()
+    _req(W, torch.float32, "W")
+    D = W.shape[0]
+    img = torch.empty(lib.ggnn_gcn_image_bytes(D) // 4, dtype=torch.float32, device=W.device)
+    _launch("gcn_pack", lambda: lib.ggnn_gcn_pack_weights_f32(_ptr(W), D, 1 if transpose else 0, _ptr(img), _stream()))
+    return img
+
+
+def gcn_layer(x: torch.Tensor, graph: GCNGraph, W: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
+              keep_prob: float = 1.0, seed: int = 0, row_key: Optional[torch.Tensor] = None, transpose: bool = False,
+              save_s: bool = False, fused: Optional[bool] = None, img: Optional[torch.Tensor] = None):
+    """One GCN layer  out = dropout(relu(M x W' + bias))  with M = A_hat, W' = W, or (transpose=True, the backward's
+    dx = A_hat^T (dP W^T)) M = A_hat^T, W' = W^T.  -> (out, S = M x if save_s else None).
+    Fused single launch for hidden sizes 32 / 64 / 100 (ggnn_gcn_layer_f32); otherwise (or fused=False) the composition
+    ggnn_weighted_segment_sum_f32 -> ggnn_gemm_f32 -> ggnn_gcn_epilogue_f32.  The dropout mask is ggnn_dropout_f32's for
+    (seed, row key, column)."""
+    lib = _lib.load()
+    _req(x, torch.float32, "x")
+    V, D = x.shape
+    if V != graph.num_nodes:
+        raise ValueError("x has %d rows, the graph %d nodes" % (V, graph.num_nodes))
+    if tuple(W.shape) != (D, D):
+        raise ValueError("W must be [%d, %d]" % (D, D))
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+    if row_key is not None:
+        _req(row_key, torch.int64, "row_key")
+    rp, col, val = (graph.row_ptr_t, graph.col_t, graph.val_t) if transpose else (graph.row_ptr, graph.col, graph.val)
+    out = torch.empty_like(x)
+    S = torch.empty_like(x) if save_s else None
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if fused is None:
+        fused = gcn_fused_supported(D)
+    if fused:
+        if img is None:
+            img = gcn_pack(W.contiguous(), transpose)
+        _launch("gcn_layer[D=%d]" % D, lambda: lib.ggnn_gcn_layer_f32(
+            _ptr(x), _ptr(rp), _ptr(col), _ptr(val), graph.nnz, _ptr(img), _ptr(bias), 1 if relu else 0, _ptr(row_key), 0, seed,
+            float(keep_prob), _ptr(out), _ptr(S), V, D, _stream()))
+        return out, S
+    Wm = (W.t() if transpose else W).contiguous()
+    Dk = kernel_width(D)
+    if Dk == D:
+        agg = weighted_segment_sum(x, SegmentIndex(rp, col, V), graph.slot_ids(), val, out=S)
+        P = gemm([agg], Wm)
+    else:
+        # (the GEMM takes K = 32 / 64 / 100 / multiples: the aggregate and W's rows zero-padded to kernel_width(D))
+        import torch.nn.functional as F
+        agg = weighted_segment_sum(F.pad(x, (0, Dk - D)), SegmentIndex(rp, col, V), graph.slot_ids(), val)
+        P = gemm([agg], F.pad(Wm, (0, 0, 0, Dk - D)))
+        if save_s:
+            S.copy_(agg[:, :D])
+            agg = S
+    _launch("gcn_epilogue", lambda: lib.ggnn_gcn_epilogue_f32(_ptr(P), _ptr(bias), 1 if relu else 0, _ptr(row_key), 0, seed,
+                                                               float(keep_prob), _ptr(out), V, D, _stream()))
+    return out, agg if save_s else None
+
+
+def gcn_propagate(h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
+                  biases: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """Inference forward of all layers (ReLU on all but the last) in one native call, ggnn_gcn_propagate_f32 (fused sizes only)."""
+    lib = _lib.load()
+    _req(h0, torch.float32, "h0")
+    V, D = h0.shape
+    L = len(weights)
+    ws_bytes = lib.ggnn_gcn_workspace_bytes(V, D, L)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=h0.device)
+    out = torch.empty_like(h0)
+    Ws = [_req(w, torch.float32, "W") for w in weights]
+    bs = None if biases is None else [_req(b, torch.float32, "bias") for b in biases]
+    w_arr = _ptr_array(Ws)
+    b_arr = None if bs is None else _ptr_array(bs)
+    _launch("gcn_propagate[D=%d,L=%d]" % (D, L), lambda: lib.ggnn_gcn_propagate_f32(
+        _ptr(h0), V, D, L, _ptr(graph.row_ptr), _ptr(graph.col), _ptr(graph.val), graph.nnz, w_arr, b_arr, _ptr(out), _ptr(ws),
+        ws_bytes, _stream()))
+    return out

@@ -603,6 +603,33 @@ int ggnn_sparse_train_backward_f32(const float* h0, int V, int D, int T, const i
 int ggnn_dropout_f32(const float* x, float* out, const int64_t* row_key, int64_t row_key_base, uint64_t seed, float keep_prob,
                      int64_t rows, int cols, ggnn_stream_t stream);
 
+/* ---- sparse GCN (chem_tensorflow_gcn.py:62-82, Kipf-style): one layer  out = dropout(relu(A_hat x W + b)) ----------------------
+ * A_hat is a weighted sparse [V,V] matrix in CSR form: row_ptr [V+1], col [nnz], val [nnz] (int32, int32, fp32).  Row i of
+ * S = A_hat x is summed in slot order (deterministic, no atomics); column indices outside [0, V) contribute nothing.
+ * Fused single-launch kernel for D = 32, 64, 100 (ggnn_gcn_fused_supported); other hidden sizes return GGNN_E_UNSUPPORTED and are
+ * composed by the caller from ggnn_weighted_segment_sum_f32, ggnn_gemm_f32 and ggnn_gcn_epilogue_f32.
+ * The product S W runs in the exact bf16x3 split form only (no f16x2 format: the final layer is linear and unbounded).
+ * ggnn_gcn_pack_weights_f32: the LDS image (ggnn_gcn_image_bytes(D) bytes, 16-byte aligned) of W [D,D], or of W^T (transpose != 0:
+ *   the backward pass dx = A_hat^T (dP W^T) is the same layer call on the transposed CSR with that image, no bias/ReLU/dropout).
+ * ggnn_gcn_layer_f32: bias [D] or NULL; relu != 0 applies ReLU; keep_prob < 1 applies the dropout of ggnn_dropout_f32 with the same
+ *   (seed, row key, column) -- bit-identical masks; s_out [V,D] or NULL receives S.  out and s_out must not alias x.
+ * ggnn_gcn_epilogue_f32: out = dropout(relu(P + bias)) with the same options (the composed path's third launch; in place allowed).
+ * ggnn_gcn_propagate_f32: all num_layers layers of an inference forward behind one call (ReLU on all but the last layer, no
+ *   dropout); W / bias are HOST arrays of num_layers device pointers (bias NULL: no bias); ws: ggnn_gcn_workspace_bytes(V, D,
+ *   num_layers) bytes (weight images and two ping-pong state buffers).  V == 0 is a no-op. */
+int ggnn_gcn_fused_supported(int D);
+size_t ggnn_gcn_image_bytes(int D);
+int ggnn_gcn_pack_weights_f32(const float* W, int D, int transpose, float* img, ggnn_stream_t stream);
+int ggnn_gcn_layer_f32(const float* x, const int32_t* row_ptr, const int32_t* col, const float* val, int64_t nnz, const float* img,
+                       const float* bias, int relu, const int64_t* row_key, int64_t row_key_base, uint64_t seed, float keep_prob,
+                       float* out, float* s_out, int V, int D, ggnn_stream_t stream);
+int ggnn_gcn_epilogue_f32(const float* P, const float* bias, int relu, const int64_t* row_key, int64_t row_key_base, uint64_t seed,
+                          float keep_prob, float* out, int V, int D, ggnn_stream_t stream);
+size_t ggnn_gcn_workspace_bytes(int V, int D, int num_layers);
+int ggnn_gcn_propagate_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col, const float* val,
+                           int64_t nnz, const float* const* W, const float* const* bias, float* out, void* ws, size_t ws_bytes,
+                           ggnn_stream_t stream);
+
 /* ---- measurement aid (bench.py's roofline leg; not on the product path) --------------------------------------------------------
  * The dense bf16 MFMA rate the chip SUSTAINS: `launches` back-to-back launches (~16 ms each) of v_mfma_f32_16x16x32_bf16 on
  * register operands, 8 waves per CU; mode 0 all-zero operands, 1 random operands, 2 the operand pattern and planes of the 3-way
