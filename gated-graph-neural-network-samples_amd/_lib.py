@@ -149,6 +149,8 @@ SYMBOLS = {
     "ggnn_gcn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ggnn_gcn_propagate_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p),
                                        POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ggnn_gcn_assemble_batch": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, POINTER(c_void_p), c_void_p]),
 }
 
 _lib = None

@@ -273,6 +273,14 @@ class ChemModel(object):
         finally:
             self.dropout_step += 1
 
+    def threaded_batches_default(self) -> bool:
+        """Whether run_epoch packs training batches on a producer thread when params['threaded_batches'] is 'auto'.
+        The producer thread pays when the launching thread is the bottleneck (the autograd path: ~4 ms of Python per step);
+        with the native step the host has slack, packing a batch inline costs 0.3 ms of it, and a second thread only takes
+        the interpreter lock away from the launches (5.8 vs 6.05 ms per step, tools/bench_extra.py epoch)."""
+        from . import train_native
+        return not train_native.model_eligible(self)
+
     def run_epoch(self, epoch_name: str, data, is_training: bool, start_step: int = 0):
         """chem_tensorflow.py:214-253."""
         chemical_accuracies = np.array([0.066513725, 0.012235489, 0.071939046, 0.033730778, 0.033486113, 0.004278493,
@@ -289,11 +297,7 @@ class ChemModel(object):
         batch_iterator = self.make_minibatch_iterator(data, is_training)
         threaded = self.params.get('threaded_batches', 'auto')
         if threaded == 'auto':
-            # The producer thread pays when the launching thread is the bottleneck (the autograd path: ~4 ms of Python per step);
-            # with the native step the host has slack, packing a batch inline costs 0.3 ms of it, and a second thread only takes
-            # the interpreter lock away from the launches (5.8 vs 6.05 ms per step, tools/bench_extra.py epoch).
-            from . import train_native
-            threaded = not train_native.model_eligible(self)
+            threaded = self.threaded_batches_default()
         if is_training and threaded:
             # chem_tensorflow.py:219 ThreadedIterator(..., max_queue_size=5): the next batches are packed while this one trains
             # (validation batches are packed once and stay resident: nothing to prefetch).  Two ahead is enough here.

@@ -146,6 +146,35 @@ class DeviceMoleculeSet:
             self._tids = (key, self._complete(torch.as_tensor(list(key), dtype=torch.int64, device=self.device)))
         return self._tids[1]
 
+    def gcn_tables(self, entry_ptr: np.ndarray, adjacency_list: np.ndarray, adjacency_weights: np.ndarray) -> dict:
+        """Dataset-level tables of ggnn_gcn_assemble_batch (SparseGCNChemModel with pack_on_device): A_hat and A_hat^T of ALL graphs
+        taken as one batch with global node ids, by the packer's own rule (ops.gcn_csr_host; weights cast to float32 as pack_batch
+        does).  A_hat is block-diagonal, and gcn_csr_host is a stable sort by row of row-major lists, so a batch's rows and entries are
+        slices of these in exactly the order gcn_csr_host gives the batch.  Built once (the arguments are gcn_model.gcn_adjacency's
+        arrays of this dataset), on the current stream, complete on return."""
+        if getattr(self, "_gcn", None) is not None:
+            return self._gcn
+        ms = self.host
+        ne = np.diff(np.asarray(entry_ptr, dtype=np.int64))
+        adj = np.asarray(adjacency_list, dtype=np.int64).reshape(-1, 2)
+        if len(ne) != ms.num_graphs or int(ne.sum()) != len(adj) or len(adjacency_weights) != len(adj):
+            raise ValueError("entry_ptr / adjacency lists do not describe this dataset's %d graphs" % ms.num_graphs)
+        n_of_entry = np.repeat(self.nodes_per_graph, ne)
+        if len(adj) and ((adj < 0) | (adj >= n_of_entry[:, None])).any():
+            raise IndexError("an adjacency entry mentions a node outside its graph")
+        glob = adj + np.repeat(np.asarray(ms.node_ptr[:-1], dtype=np.int64), ne)[:, None]
+        parts = ops.gcn_csr_host(glob, adjacency_weights, int(ms.node_ptr[-1]))
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        dev = [t(p) for p in parts]
+        self._gcn = {
+            "node_ptr": t(np.asarray(ms.node_ptr).astype(np.int32)),
+            "csr": dev[:3], "csr_t": dev[3:],
+            "entries_per_graph": ne,                                            # host copy: a batch's nnz without a device read
+            "counts_t": t(np.stack([self.nodes_per_graph, ne]).astype(np.int32)),   # [2, Gd] for the per-epoch prefix sums
+        }
+        self._complete(self._gcn["counts_t"])
+        return self._gcn
+
     def static_backward_tables(self, num_edge_types: int, tie_fwd_bkwd: bool):
         """The same for the backward pass's transpose structures (by-source CSR, ops.CompactBackward), built lazily on the first
         training batch."""

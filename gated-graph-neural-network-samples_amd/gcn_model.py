@@ -104,18 +104,25 @@ class SparseGCNChemModel(ChemModel):
                        'gcn_use_bias': False,
                        'graph_state_dropout_keep_prob': 1.0,
                        })
+        # (params['pack_on_device'], default False, is read with .get like the sparse model's: a key in this dict would break
+        # restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340)
         return params
 
     DERIVED_PLACEHOLDERS = dict(ChemModel.DERIVED_PLACEHOLDERS, adjacency_list=('gcn_graph',), adjacency_weights=('gcn_graph',))
 
     # ---- weights ------------------------------------------------------------------------------------
     def prepare_specific_graph_model(self) -> None:
-        """chem_tensorflow_gcn.py:42-59: glorot weights [D, D] per layer from the NumPy stream in creation order, zero biases."""
+        """chem_tensorflow_gcn.py:42-59: glorot weights [D, D] per layer from the NumPy stream in creation order, zero biases.
+        params['pack_on_device'] (default False): batches are assembled on the GPU from the resident dataset
+        (DeviceMoleculeSet.gcn_tables, ggnn_gcn_assemble_batch) instead of packed in NumPy and uploaded -- the same feeds bit for bit,
+        without 'adjacency_list' / 'adjacency_weights'.  Needs a CUDA/HIP device."""
         h_dim = self.params['hidden_size']
         if h_dim <= 0 or h_dim % 4:
             raise ValueError("hidden_size %r: the GCN kernels take positive multiples of 4" % (h_dim,))
         if self.annotation_size > h_dim:
             raise ValueError("annotation_size %d exceeds hidden_size %d" % (self.annotation_size, h_dim))
+        if self.params.get('pack_on_device') and torch.device(self.device).type != 'cuda':
+            raise ValueError("pack_on_device=True assembles batches on the GPU; device %r is not a CUDA/HIP device" % (str(self.device),))
         self._kw = h_dim                               # (the borrowed readout methods read the kernel width)
         for name in ('initial_node_representation', 'adjacency_list', 'adjacency_weights', 'graph_nodes_list', 'gcn_graph'):
             self.placeholders[name] = None
@@ -240,9 +247,71 @@ class SparseGCNChemModel(ChemModel):
             'graph_state_keep_prob': keep_prob,
         }
 
+    def prepare_resident_data(self, data: Any, is_training: bool) -> None:
+        """pack_on_device: upload the dataset and build the dataset-level A_hat tables on the CURRENT stream (run_epoch calls this
+        before it hands the epoch to the producer thread, whose stream is ordered behind it)."""
+        if not self.params.get('pack_on_device') or data is None:
+            return
+        if data.get("molecules_dev") is None:
+            from .data_device import DeviceMoleculeSet
+            data["molecules_dev"] = DeviceMoleculeSet(data["molecules"], self.device, data["label_mask"])
+        dms = data["molecules_dev"]
+        dms.gcn_tables(data["entry_ptr"], data["adjacency_list"], data["adjacency_weights"])
+        K = dms.targets.shape[1] if dms.targets.dim() == 2 else 0
+        if any(not 0 <= int(t) < K for t in self.params['task_ids']):
+            raise IndexError("task_ids %s outside the dataset's %d targets" % (self.params['task_ids'], K))
+        dms.task_ids_dev(self.params['task_ids'])
+
+    # run_epoch's producer thread with pack_on_device (threaded_batches 'auto'): a batch is one launch and ~0.13 ms of host work, so
+    # a second thread mostly takes the interpreter lock from the step's launches: 1.55 against 1.44 ms per step inline
+    # (tools/gcn_bench.py --leg epoch, profiles/gcn_epoch.json)
+    DEVICE_PACK_THREADED = False
+
+    def threaded_batches_default(self) -> bool:
+        if self.params.get('pack_on_device'):
+            return self.DEVICE_PACK_THREADED
+        return super().threaded_batches_default()
+
+    def device_batches(self, data: Any, order: np.ndarray, keep_prob: float):
+        """One epoch's batches of graph order `order`, assembled on the GPU (pack_on_device): the order goes up once
+        (DeviceMoleculeSet.upload_order), its node / entry prefix sums are formed there once (ops.gcn_epoch_table), and every batch
+        is one ggnn_gcn_assemble_batch launch.  The host computes only the batch boundaries and totals, from its own count copies;
+        nothing is read back.  Feeds are pack_batch's without 'adjacency_list' / 'adjacency_weights'."""
+        self.prepare_resident_data(data, False)
+        dms = data["molecules_dev"]
+        tab = dms.gcn_tables(data["entry_ptr"], data["adjacency_list"], data["adjacency_weights"])
+        order = np.asarray(order, dtype=np.int64)
+        npg = dms.nodes_per_graph[order]
+        bounds = batch_boundaries(npg, self.params['batch_size'])
+        node_cum = np.concatenate([[0], np.cumsum(npg)])
+        entry_cum = np.concatenate([[0], np.cumsum(tab["entries_per_graph"][order])])
+        order_dev = dms.upload_order(order)
+        if order_dev.is_cuda:
+            order_dev.record_stream(torch.cuda.current_stream(order_dev.device))    # (allocated on the upload stream, read on this one)
+        epoch_tab = ops.gcn_epoch_table(tab["counts_t"], order_dev)
+        tids = dms.task_ids_dev(self.params['task_ids'])
+        D = self.params['hidden_size']
+        for s, e in zip(bounds[:-1], bounds[1:]):
+            graph, h0, gnl, graph_ptr, uid, tv, tm = ops.gcn_assemble_batch(
+                tab["node_ptr"], dms.node_feat, tab["csr"], tab["csr_t"], dms.targets, dms.label_mask, tids, epoch_tab, s, e - s,
+                int(node_cum[e] - node_cum[s]), int(entry_cum[e] - entry_cum[s]), D)
+            yield {
+                'initial_node_representation': h0,
+                'gcn_graph': graph,
+                'graph_nodes_list': gnl,
+                'graph_ptr': graph_ptr,
+                'graph_nodes_sorted': True,
+                'node_uid': uid,
+                'target_values': tv,
+                'target_mask': tm,
+                'num_graphs': int(e - s),
+                'graph_state_keep_prob': keep_prob,
+            }
+
     def make_minibatch_iterator(self, data: Any, is_training: bool):
         """chem_tensorflow_gcn.py:144-196: graphs packed while node_offset + n < batch_size (strict); training data reshuffled
-        every epoch (in place, so the orders compose), validation batches packed once and kept on the device."""
+        every epoch (in place, so the orders compose), validation batches packed once and kept on the device.  With
+        pack_on_device the batches are assembled on the GPU (device_batches), the same feeds bit for bit."""
         ms: MoleculeSet = data["molecules"]
         if not is_training and data["valid_batches"] is not None:
             yield from (dict(b) for b in data["valid_batches"])
@@ -255,8 +324,11 @@ class SparseGCNChemModel(ChemModel):
         else:
             order = np.arange(ms.num_graphs)
         keep = self.params['graph_state_dropout_keep_prob'] if is_training else 1.0
-        bounds = batch_boundaries(np.diff(ms.node_ptr)[order], self.params['batch_size'])
-        batches = (self.pack_batch(data, order[s:e], keep) for s, e in zip(bounds[:-1], bounds[1:]))
+        if self.params.get('pack_on_device'):
+            batches = self.device_batches(data, order, keep)
+        else:
+            bounds = batch_boundaries(np.diff(ms.node_ptr)[order], self.params['batch_size'])
+            batches = (self.pack_batch(data, order[s:e], keep) for s, e in zip(bounds[:-1], bounds[1:]))
         if is_training:
             yield from batches
         else:

@@ -1314,6 +1314,91 @@ def gcn_graph(adjacency_list, adjacency_weights, num_nodes: int, device) -> GCNG
     return GCNGraph(*[torch.from_numpy(p).to(device) for p in parts], num_nodes)
 
 
+def gcn_epoch_table(counts_t: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """Prefix sums of per-graph counts over an epoch's order, on the device (ggnn_pack_batch_tables, one launch per epoch).
+    counts_t int32 [2, Gd] (nodes, A_hat entries per graph), order int64 [Ge] -> int32 [Ge | Ge+1 | Ge+1]: the order as int32, then
+    node_cum and entry_cum, the totals of the graphs before each epoch position."""
+    lib = _lib.load()
+    _req(counts_t, torch.int32, "counts_t")
+    _req(order, torch.int64, "order")
+    if counts_t.dim() != 2 or counts_t.shape[0] != 2 or order.dim() != 1 or order.device != counts_t.device:
+        raise ValueError("counts_t must be [2, Gd] and order [Ge] on its device")
+    Ge = order.numel()
+    tab = torch.empty(3 * Ge + 2, dtype=torch.int32, device=order.device)
+    _launch("gcn_epoch_table", lambda: lib.ggnn_pack_batch_tables(_ptr(counts_t), counts_t.shape[1], 2, _ptr(order) if Ge else None, Ge,
+                                                                  None, None, 0, None, 0, _ptr(tab), None, None, _stream()))
+    return tab
+
+
+def gcn_assemble_batch(node_ptr: torch.Tensor, feat: torch.Tensor, csr: Sequence[torch.Tensor], csr_t: Sequence[torch.Tensor],
+                       targets: torch.Tensor, label_mask: Optional[torch.Tensor], task_ids: torch.Tensor, epoch_tab: torch.Tensor,
+                       start: int, num_graphs: int, num_nodes: int, nnz: int, hidden_size: int):
+    """One GCN batch, graphs [start, start + num_graphs) of the epoch whose gcn_epoch_table is `epoch_tab`, gathered from dataset-level
+    tables in one launch (ggnn_gcn_assemble_batch): node_ptr int32 [Gd+1], feat float32 [Nd, A], csr / csr_t = (row_ptr int32 [Nd+1],
+    col int32 [nnz_d], val float32 [nnz_d]) of A_hat and A_hat^T over global node ids, targets float32 [Gd, num_targets], label_mask
+    float32 [Gd, K] or None, task_ids int64 [K] (target columns).  num_nodes / nnz are the batch's totals, known on the host.
+    -> (GCNGraph, h0 [V, hidden_size], graph_nodes_list int32 [V], graph_ptr int32 [G+1], node_uid int64 [V],
+        target_values [K, G], target_mask [K, G]).  Nothing is read back; every argument is checked before the launch."""
+    def req(t, dtype, name):                         # (dtype and layout first, the device last: checkable without a GPU)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError("%s must be a %s tensor, got %s" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return t
+    req(node_ptr, torch.int32, "node_ptr")
+    req(feat, torch.float32, "feat")
+    rp, col, val = [req(t, dt, n) for t, dt, n in zip(csr, (torch.int32, torch.int32, torch.float32), ("row_ptr", "col", "val"))]
+    rpt, colt, valt = [req(t, dt, n) for t, dt, n in zip(csr_t, (torch.int32, torch.int32, torch.float32), ("row_ptr_t", "col_t", "val_t"))]
+    req(targets, torch.float32, "targets")
+    if label_mask is not None:
+        req(label_mask, torch.float32, "label_mask")
+    req(task_ids, torch.int64, "task_ids")
+    req(epoch_tab, torch.int32, "epoch_tab")
+    dev = feat.device
+    tensors = [node_ptr, rp, col, val, rpt, colt, valt, targets, task_ids, epoch_tab] + ([label_mask] if label_mask is not None else [])
+    if any(t.device != dev for t in tensors):
+        raise ValueError("gcn_assemble_batch: every table must be on %s" % dev)
+    Gd = node_ptr.numel() - 1
+    if node_ptr.dim() != 1 or Gd < 0 or feat.dim() != 2:
+        raise ValueError("node_ptr must be [Gd+1] and feat [Nd, A]")
+    Nd, A = feat.shape
+    nnz_d = col.numel()
+    if rp.numel() != Nd + 1 or rpt.numel() != Nd + 1 or val.numel() != nnz_d or colt.numel() != nnz_d or valt.numel() != nnz_d:
+        raise ValueError("A_hat tables: row_ptr [%d], col/val/col_t/val_t [nnz] expected, got %s" % (
+            Nd + 1, [t.numel() for t in (rp, col, val, rpt, colt, valt)]))
+    if targets.dim() != 2 or targets.shape[0] != Gd or task_ids.dim() != 1:
+        raise ValueError("targets must be [Gd, num_targets] and task_ids [K]")
+    K = task_ids.numel()
+    if label_mask is not None and tuple(label_mask.shape) != (Gd, K):
+        raise ValueError("label_mask must be [%d, %d], got %s" % (Gd, K, tuple(label_mask.shape)))
+    if epoch_tab.dim() != 1 or (epoch_tab.numel() - 2) % 3:
+        raise ValueError("epoch_tab must be gcn_epoch_table's [3 Ge + 2]")
+    Ge = (epoch_tab.numel() - 2) // 3
+    s, G, V, E, D = int(start), int(num_graphs), int(num_nodes), int(nnz), int(hidden_size)
+    if s < 0 or G < 0 or s + G > Ge:
+        raise ValueError("batch [%d, %d) outside the epoch's %d graphs" % (s, s + G, Ge))
+    if not 0 <= V <= Nd or not 0 <= E <= nnz_d or (G == 0 and (V or E)):
+        raise ValueError("batch totals V=%d nnz=%d outside the dataset's %d nodes / %d entries" % (V, E, Nd, nnz_d))
+    if D <= 0 or A > D:
+        raise ValueError("hidden_size %d must be positive and >= the annotation size %d" % (D, A))
+    if not feat.is_cuda:
+        raise TypeError("gcn_assemble_batch needs CUDA/HIP tensors (there is no CPU implementation)")
+    lib = _lib.load()
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    h0 = f32(V, D)
+    g_rp, g_col, g_val, g_rpt, g_colt, g_valt = i32(V + 1), i32(E), f32(E), i32(V + 1), i32(E), f32(E)
+    gnl, graph_ptr = i32(V), i32(G + 1)
+    uid = torch.empty(V, dtype=torch.int64, device=dev)
+    tv, tm = f32(K, G), f32(K, G)
+    nz = lambda t: _ptr(t) if t is not None and t.numel() else None
+    c_ds = (ctypes.c_void_p * 10)(*[nz(t) for t in (node_ptr, feat, rp, col, val, rpt, colt, valt, targets, label_mask)])
+    c_out = (ctypes.c_void_p * 12)(*[nz(t) for t in (h0, g_rp, g_col, g_val, g_rpt, g_colt, g_valt, gnl, graph_ptr, uid, tv, tm)])
+    _launch("gcn_assemble_batch", lambda: lib.ggnn_gcn_assemble_batch(c_ds, Gd, A, targets.shape[1], nz(task_ids), K, _ptr(epoch_tab), Ge,
+                                                                      s, G, V, E, D, c_out, _stream()))
+    return GCNGraph(g_rp, g_col, g_val, g_rpt, g_colt, g_valt, V), h0, gnl, graph_ptr, uid, tv, tm
+
+
 def gcn_fused_supported(D: int) -> bool:
     return bool(_lib.load().ggnn_gcn_fused_supported(int(D)))
 

@@ -549,6 +549,19 @@ int ggnn_assemble_batch(const void* const* ds_tables, int A, int T, const int64_
 int ggnn_pack_batch_tables(const int32_t* counts_t, int Gd, int rows, const int64_t* gids, int G, const float* targets,
                            const float* label_mask, int num_targets, const int64_t* task_ids, int K, int32_t* batch_tab,
                            float* target_values, float* target_mask, ggnn_stream_t stream);
+/* Sparse GCN batch from dataset-level tables (chem_tensorflow_gcn.py:154-196): graphs [s, s + G) of an epoch's order, one launch.
+ *   ds_tables [10]: 0 node_ptr i32[Gd+1]  1 node features f32[Nd, A]  2-4 A_hat as CSR over global node ids (row_ptr i32[Nd+1],
+ *     col i32[nnz_d], val f32[nnz_d])  5-7 the same for A_hat^T  8 targets f32[Gd, num_targets]  9 label mask f32[Gd, K] or NULL
+ *   task_ids: device i64[K], target column of each task.
+ *   epoch_tab: batch_tab of ggnn_pack_batch_tables over the whole epoch order with rows (nodes per graph, A_hat entries per graph):
+ *     gid[Ge] | node_cum[Ge+1] | entry_cum[Ge+1].  V and nnz are the batch's node and entry totals (the host's sums of the same counts).
+ *   out [12]: 0 h0 f32[V, D] (annotations zero-padded)  1-3 row_ptr i32[V+1], col i32[nnz], val f32[nnz]  4-6 the transpose
+ *     7 graph_nodes_list i32[V]  8 graph_ptr i32[G+1]  9 node_uid i64[V] = (graph id << 20) + local node
+ *     10 target_values f32[K, G] (0 where the mask is 0)  11 target_mask f32[K, G].
+ *   Any D > 0 with A <= D; G == 0 writes the three closing entries only. */
+int ggnn_gcn_assemble_batch(const void* const* ds_tables, int Gd, int A, int num_targets, const int64_t* task_ids, int K,
+                            const int32_t* epoch_tab, int Ge, int s, int G, int V, int nnz, int D, void* const* out,
+                            ggnn_stream_t stream);
 
 /* ---- the optimisation step of the default sparse model as native launch sequences (chem_tensorflow.py:183-191 over
  * chem_tensorflow_sparse.py:117-218; ggnn_train.hip) -----------------------------------------------------------------------------

@@ -7,11 +7,20 @@
   bytes_fused / bytes_composed         algorithmic HBM bytes of one layer (x read once, out written once, CSR; the composed path
                                        also writes and reads S and P), and the fraction of the 8 TB/s roof they reach.
 Run from the repository root:  python tools/gcn_bench.py [--graphs 5600] [--iters 200]
+
+--leg epoch: training epochs over synthetic QM9 (mean 18 atoms, batch_size 100000, `--epoch-graphs` molecules) with the batches
+packed on the host (pack_batch + gcn_csr_host + upload) and on the device (pack_on_device: ggnn_gcn_assemble_batch), in one run:
+  pack_ms_per_batch   packing alone, one epoch's batches produced back to back, device events around the loop
+  epoch_graphs_per_s  run_epoch's graphs/s (second of two epochs), the device path with and without the producer thread
+  ms_per_step         epoch time / steps;  step_ms: one training step on a resident batch
+  assemble            one ggnn_gcn_assemble_batch launch: algorithmic HBM bytes, device-event time, fraction of the 8 TB/s roof
+--leg pack: only device packing of `--iters` batches (for a kernel trace).
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -35,13 +44,89 @@ def timed(fn, iters):
     return s.elapsed_time(e) / iters          # ms
 
 
+def _epoch_model(ms, cfg, pack_on_device, threaded):
+    cfg = dict(cfg, pack_on_device=pack_on_device, threaded_batches=threaded)
+    return ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms, "--config": cfg})
+
+
+def _pack_ms(model, epochs=2):
+    """ms per batch of producing one training epoch's batches back to back (nothing else queued), last of `epochs` epochs."""
+    for _ in range(epochs):
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        n = 0
+        for _b in model.make_minibatch_iterator(model.train_data, is_training=True):
+            n += 1
+        e.record()
+        torch.cuda.synchronize()
+    return s.elapsed_time(e) / n, n
+
+
+def _epoch(model, epochs=2):
+    for _ in range(epochs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, _, graphs_per_s, steps = model.run_epoch("bench", model.train_data, True)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    return graphs_per_s, dt * 1e3 / steps, steps
+
+
+def epoch_leg(a):
+    ms = ggnn_amd.synthetic_qm9(a.epoch_graphs, mean_nodes=18, seed=0)
+    cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
+    out = {"metric": "sparse GCN training epoch, synthetic QM9", "graphs": ms.num_graphs, "nodes": int(ms.node_ptr[-1]), "D": a.hidden,
+           "layers": 4, "batch_size": 100000}
+    for name, on_dev, threaded in (("host", False, True), ("device", True, False), ("device_threaded", True, True)):
+        model = _epoch_model(ms, cfg, on_dev, threaded)
+        pack_ms, batches = _pack_ms(model)
+        gps, step_ms, steps = _epoch(model)
+        out[name] = {"pack_ms_per_batch": round(pack_ms, 4), "epoch_graphs_per_s": round(gps, 1), "ms_per_step": round(step_ms, 3),
+                     "batches": batches}
+        if on_dev and not threaded:
+            feed = dict(next(iter(model.make_minibatch_iterator(model.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
+            out["step_ms"] = round(timed(lambda: model.train_batch(feed), 20), 3)
+            V, D = feed["initial_node_representation"].shape
+            g, G = feed["gcn_graph"], feed["num_graphs"]
+            # h0 written; annotations read; both CSRs read and written (row_ptr, col, val); gnl, node_uid written; labels
+            A = model.train_data["molecules"].node_feat.shape[1]
+            b = V * D * 4 + V * A * 4 + 2 * 2 * ((V + 1) * 4 + g.nnz * 8) + V * (4 + 8) + G * 4 * 4
+            with ggnn_amd.ops.kernel_timing() as kt:
+                for _ in range(20):
+                    list(model.make_minibatch_iterator(model.train_data, is_training=True))
+            us = float(np.median(kt.results()["gcn_assemble_batch"])) * 1e3
+            out["assemble"] = {"V": int(V), "nnz": g.nnz, "bytes": int(b), "us_events": round(us, 2),
+                               "roof_fraction": round(b / HBM_ROOF / (us * 1e-6), 3)}
+        del model
+        torch.cuda.empty_cache()
+    out["pack_speedup"] = round(out["host"]["pack_ms_per_batch"] / out["device"]["pack_ms_per_batch"], 1)
+    out["epoch_speedup"] = round(out["device"]["epoch_graphs_per_s"] / out["host"]["epoch_graphs_per_s"], 2)
+    print(json.dumps(out))
+
+
+def pack_leg(a):
+    ms = ggnn_amd.synthetic_qm9(a.epoch_graphs, mean_nodes=18, seed=0)
+    model = _epoch_model(ms, {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}, True, False)
+    n = 0
+    while n < a.iters:
+        for _b in model.make_minibatch_iterator(model.train_data, is_training=True):
+            n += 1
+    torch.cuda.synchronize()
+    print(json.dumps({"metric": "GCN device packing", "batches": n}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=5600)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--hidden", type=int, default=100)
+    ap.add_argument("--leg", choices=("layer", "epoch", "pack"), default="layer")
+    ap.add_argument("--epoch-graphs", type=int, default=33600)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "gcn_bench needs a GPU"
+    if a.leg != "layer":
+        return (epoch_leg if a.leg == "epoch" else pack_leg)(a)
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
     cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
     model = ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms, "--config": cfg})
