@@ -151,6 +151,9 @@ SYMBOLS = {
                                        POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
     "ggnn_gcn_assemble_batch": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                         c_int, c_int, POINTER(c_void_p), c_void_p]),
+    "ggnn_dense_assemble_batch": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_void_p),
+                                          c_void_p]),
 }
 
 _lib = None

@@ -175,6 +175,21 @@ class DeviceMoleculeSet:
         self._complete(self._gcn["counts_t"])
         return self._gcn
 
+    def dense_tables(self, num_edge_types: int, tie_fwd_bkwd: bool) -> dict:
+        """Dataset-level tables of ggnn_dense_assemble_batch (DenseGGNNChemModel with pack_on_device): dense_tables_host's arrays on
+        the device, built once per (num_edge_types, tie_fwd_bkwd), on the current stream, complete on return.  The per-(graph, type)
+        message and pair counts stay on the host as well ('mc', 'pc'): a batch's sizes are sums over its graph ids."""
+        key = (int(num_edge_types), bool(tie_fwd_bkwd))
+        cache = self.__dict__.setdefault("_dense", {})
+        if key in cache:
+            return cache[key]
+        host = dense_tables_host(self.host, key[0], key[1])
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        tab = {k: (t(v) if k in ops.DENSE_GRAPH_TABLES else v) for k, v in host.items()}
+        self._complete(tab["counts_t"])
+        cache[key] = tab
+        return tab
+
     def static_backward_tables(self, num_edge_types: int, tie_fwd_bkwd: bool):
         """The same for the backward pass's transpose structures (by-source CSR, ops.CompactBackward), built lazily on the first
         training batch."""
@@ -236,6 +251,94 @@ class DeviceMoleculeSet:
             tab["c_type_row_off"] = (ctypes.c_int64 * (T + 1))(*tab["type_row_off"])
         self._static[key] = tab
         return tab
+
+
+def dense_tables_host(ms: MoleculeSet, num_edge_types: int, tie_fwd_bkwd: bool) -> Dict[str, np.ndarray]:
+    """Every graph's part of the dense model's batch structures, in LOCAL node ids, graph after graph (ggnn_dense_assemble_batch
+    shifts them by the graph's slot * v and its offsets in the batch).
+
+    A graph's messages are the nonzero entries of its adjacency block (data.pack_dense_batch, chem_tensorflow_dense.py:30-36): the
+    unique triples (type, dst, src) of both directions of every bond, the backward one with type + T/2 when the directions are
+    untied; a duplicate bond is one message, a self-loop bond one message when the types are tied.  They are ordered (type, dst, src),
+    the order np.nonzero gives them in a batch, so a batch's type-t list is the concatenation of its graphs' type-t lists.  The
+    other tables are orders of the same messages (by target, by (source, type), by compact row), the active (source, type) pairs of
+    the compacted transform and the offsets of every node's and pair's range in them: each is a per-graph piece of the structure
+    that ops.build_message_index / build_compact_sources / compact_backward build for a batch.
+
+    -> int32 / float32 arrays named as ops.DENSE_GRAPH_TABLES, plus 'mc' / 'pc' int64 [G, T] (messages and active pairs per graph
+    and type: the host's copies, a batch's sizes are sums over them)."""
+    T, tie = int(num_edge_types), bool(tie_fwd_bkwd)
+    if not 1 <= T <= 16:
+        raise ValueError("num_edge_types %d outside [1, 16]" % T)
+    F = T if tie else T // 2
+    node_ptr = np.asarray(ms.node_ptr, dtype=np.int64)
+    G = len(node_ptr) - 1
+    Nd = int(node_ptr[-1])
+    npg = np.diff(node_ptr)
+    nb = np.diff(np.asarray(ms.bond_ptr, dtype=np.int64))
+    bonds = np.asarray(ms.bonds, dtype=np.int64).reshape(-1, 3)
+    g_b = np.repeat(np.arange(G, dtype=np.int64), nb)
+    s, e, d = bonds[:, 0], bonds[:, 1] - 1, bonds[:, 2]
+    if len(bonds) and ((e < 0).any() or (e >= F).any()):
+        raise IndexError("bond type outside [1, %d]" % F)
+    n_b = npg[g_b]
+    if len(bonds) and ((s < 0) | (s >= n_b) | (d < 0) | (d >= n_b)).any():
+        raise IndexError("a bond mentions a vertex outside its graph")
+    gg = np.concatenate([g_b, g_b])
+    tt = np.concatenate([e, e + (0 if tie else F)])
+    dd = np.concatenate([d, s])                                   # amat[e-1, dest, src] and amat[e-1+off, src, dest]
+    ss = np.concatenate([s, d])
+    o = np.lexsort((ss, dd, tt, gg))
+    gg, tt, dd, ss = gg[o], tt[o], dd[o], ss[o]
+    keep = np.ones(len(gg), dtype=bool)
+    if len(gg) > 1:
+        keep[1:] = (np.diff(gg) != 0) | (np.diff(tt) != 0) | (np.diff(dd) != 0) | (np.diff(ss) != 0)
+    gg, tt, dd, ss = gg[keep], tt[keep], dd[keep], ss[keep]       # messages, graph-major, ordered (type, dst, src) inside a graph
+    Md = len(gg)
+    if Md >= 2 ** 31 - 1 or Nd * T >= 2 ** 31 - 1:
+        raise ValueError("dataset too large for 32-bit table indices (%d messages, %d nodes x %d types)" % (Md, Nd, T))
+    mc = np.bincount(gg * T + tt, minlength=G * T).reshape(G, T).astype(np.int64)
+    msg_ptr = np.concatenate([[0], np.cumsum(mc.sum(axis=1))]).astype(np.int64)
+    cm = np.cumsum(mc, axis=1) - mc                               # first message of type t inside its graph
+    j_of = np.arange(Md, dtype=np.int64) - msg_ptr[gg]            # local message position (type-major)
+    n0 = node_ptr[gg]
+    dst_g, src_g = n0 + dd, n0 + ss                               # dataset node ids
+    nin = np.bincount(dst_g * T + tt, minlength=Nd * T).reshape(Nd, T).astype(np.float32)
+    g_n = np.repeat(np.arange(G, dtype=np.int64), npg)            # graph of every dataset node
+    deg = np.bincount(dst_g, minlength=Nd)
+    in_ptr = np.cumsum(deg) - deg - msg_ptr[g_n]                  # first by-target slot of a node, inside its graph
+    by_dst = np.lexsort((np.arange(Md), dd, gg))                  # stable sort by target: slots, graph after graph
+    slot_msg = j_of[by_dst]
+    # active (source, type) pairs: type-major, node ascending inside a graph (ggnn_build_compact_sources per graph)
+    pkey = (gg * T + tt) * max(int(npg.max()) if G else 1, 1) + ss
+    ukey, first, inv = np.unique(pkey, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    Pd = len(ukey)
+    p_g, p_t, p_n = gg[first], tt[first], ss[first]
+    pc = np.bincount(p_g * T + p_t, minlength=G * T).reshape(G, T).astype(np.int64)
+    pair_ptr = np.concatenate([[0], np.cumsum(pc.sum(axis=1))]).astype(np.int64)
+    cp = np.cumsum(pc, axis=1) - pc
+    msg_crow = inv - pair_ptr[gg] - cp[gg, tt]                   # message -> rank of its pair among the graph's type-t pairs
+    outd = np.bincount(src_g * T + tt, minlength=Nd * T)          # by-(source, type) segment sizes
+    src_ptr = np.cumsum(outd) - outd - np.repeat(msg_ptr[g_n], T)
+    by_src = np.lexsort((np.arange(Md), tt, ss, gg))              # stable sort by (source, type): slots of the source index
+    src_msg = j_of[by_src]
+    by_row = np.lexsort((np.arange(Md), ss, tt, gg))              # stable sort by compact row (type, source)
+    rows_msg = j_of[by_row]
+    p_cnt = outd[(node_ptr[p_g] + p_n) * T + p_t]
+    pair_rows = np.cumsum(p_cnt) - p_cnt - msg_ptr[p_g] - cm[p_g, p_t]
+    per_node = np.bincount(node_ptr[p_g] + p_n, minlength=Nd)
+    node_pptr = np.cumsum(per_node) - per_node - pair_ptr[g_n]
+    by_node = np.lexsort((np.arange(Pd), p_n, p_g))               # compact rows by node, type ascending inside a node
+    node_order = by_node - pair_ptr[p_g[by_node]]
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return {
+        "node_ptr": i32(node_ptr), "counts_t": i32(np.concatenate([mc.T, pc.T], axis=0).reshape(2 * T, G)),
+        "msg_ptr": i32(msg_ptr), "msg": i32(np.stack([ss, dd], axis=1).reshape(Md, 2)), "nin": nin, "in_ptr": i32(in_ptr),
+        "slot_msg": i32(slot_msg), "pair_ptr": i32(pair_ptr), "pair_node": i32(p_n), "msg_crow": i32(msg_crow),
+        "src_ptr": i32(src_ptr), "src_msg": i32(src_msg), "rows_msg": i32(rows_msg), "pair_rows": i32(pair_rows),
+        "node_pptr": i32(node_pptr), "node_order": i32(node_order), "mc": mc, "pc": pc,
+    }
 
 
 def _assemble_from_tables(dms: DeviceMoleculeSet, tab: dict, gids_h: np.ndarray, hidden_size: int, training: bool = False,

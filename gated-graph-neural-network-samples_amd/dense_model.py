@@ -4,8 +4,10 @@ Per timestep (chem_tensorflow_dense.py:100-115):
     m_e  = h W_e (+ b_e)          for all e: ONE FP32-MFMA GEMM [b*v,D]x[D,e*D]  (ggnn_msg_transform_f32)
     acts = sum_e A_e m_e          batched [v,v]x[v,D] from LDS                   (ggnn_dense_aggregate_f32)
     h    = GRU(acts, h)           one GRU shared by all timesteps (:101-102)     (ggnn_gru_f32)
-Forward (inference / validation) path; the dense training path is not built (the sparse model is the
-north-star path).
+Inference / validation runs all timesteps in one graph-resident launch (ggnn_dense_propagate_f32).  Training runs the dense step as
+the sparse step it is on the b*v padded nodes (_compute_for_training: the hand-written backward of backward.PropagationStepFn).
+With params['pack_on_device'] the batches are assembled on the GPU from the resident dataset (ggnn_dense_assemble_batch), training
+batches together with that sparse form.
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ from typing import Any, Dict, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import formats, ops
 from .chem_model import ChemModel
 from .data import DENSE_BUCKET_SIZES, MoleculeSet, pack_dense_batch
 from .sparse_model import GRUCellWeights
@@ -42,10 +44,17 @@ class DenseGGNNChemModel(ChemModel):
             'use_edge_bias': True,
             'edge_weight_dropout_keep_prob': 1
         })
+        # (params['pack_on_device'], default False, is read with .get: a key in this dict would break restoring the reference's
+        # checkpoints, whose params must match key for key, chem_tensorflow.py:336-340)
         return params
 
     def prepare_specific_graph_model(self) -> None:
-        """chem_tensorflow_dense.py:68-91."""
+        """chem_tensorflow_dense.py:68-91.
+        params['pack_on_device'] (default False): batches are assembled on the GPU from the resident dataset
+        (DeviceMoleculeSet.dense_tables, ggnn_dense_assemble_batch) instead of packed in NumPy and uploaded -- the same feeds bit for
+        bit; a training feed also carries the sparse form its step needs ('_sparse_form').  Needs a CUDA/HIP device."""
+        if self.params.get('pack_on_device') and torch.device(self.device).type != 'cuda':
+            raise ValueError("pack_on_device=True assembles batches on the GPU; device %r is not a CUDA/HIP device" % (str(self.device),))
         h_dim = self.params['hidden_size']
         for name in ('initial_node_representation', 'node_mask', 'num_vertices', 'adjacency_matrix'):
             self.placeholders[name] = None
@@ -100,8 +109,9 @@ class DenseGGNNChemModel(ChemModel):
                 ts.append(self.weights['edge_biases'])
             mx = formats.weight_absmax(ts)
             S = formats.state_bound(formats.h0_absmax(self.placeholders), 'tanh')
-            # (|A| <= 1 for the reference's 0 / 1 adjacency; a weighted or multi-edge feed scales the sum: measured, cached per tensor)
-            a_max = formats.adjacency_absmax(self.placeholders['adjacency_matrix'])
+            # (|A| <= 1 for the reference's 0 / 1 adjacency; a weighted or multi-edge feed scales the sum: measured, cached per tensor,
+            # unless the device packer declared it for this very tensor)
+            a_max = formats.adjacency_absmax(self.placeholders['adjacency_matrix'], self.placeholders)
             acts = max(1.0, a_max) * v * self.num_edge_types * (self.params['hidden_size'] * mx[0] * S + (mx[3] if len(mx) > 3 else 0.0))
             if a_max != a_max:
                 acts = float("nan")
@@ -270,6 +280,18 @@ class DenseGGNNChemModel(ChemModel):
         return {"molecules": ms, "bucketed": dict(bucketed), "bucket_sizes": np.asarray(bucket_sizes),
                 "bucket_at_step": bucket_at_step, "device_batches": {}, "label_mask": label_mask}
 
+    def _epoch_order(self, bucketed, bucket_at_step):
+        """The graphs of make_minibatch_iterator's steps, concatenated (int64), and each step's first position in it."""
+        bs = self.params['batch_size']
+        counters = defaultdict(int)
+        parts = []
+        for bucket in bucket_at_step:
+            c = counters[bucket]
+            parts.append(np.asarray(bucketed[bucket][c * bs:(c + 1) * bs], dtype=np.int64))
+            counters[bucket] += 1
+        starts = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+        return (np.concatenate(parts) if parts else np.zeros(0, np.int64)), [int(x) for x in starts]
+
     def to_device_batch(self, db) -> Dict[str, Any]:
         dev = self.device
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -277,8 +299,76 @@ class DenseGGNNChemModel(ChemModel):
                 'node_mask': t(db.node_mask), 'num_vertices': db.num_vertices, 'target_values': t(db.target_values),
                 'target_mask': t(db.target_mask), 'num_graphs': db.num_graphs}
 
+    def prepare_resident_data(self, data: Any, is_training: bool) -> None:
+        """pack_on_device: upload the dataset and build the dataset-level tables on the CURRENT stream (run_epoch calls this before it
+        hands the epoch to the producer thread, whose stream is ordered behind it)."""
+        if not self.params.get('pack_on_device') or data is None:
+            return
+        if data.get("molecules_dev") is None:
+            from .data_device import DeviceMoleculeSet
+            data["molecules_dev"] = DeviceMoleculeSet(data["molecules"], self.device, data["label_mask"])
+        dms = data["molecules_dev"]
+        dms.dense_tables(self.num_edge_types, self.params['tie_fwd_bkwd'])
+        K = dms.targets.shape[1] if dms.targets.dim() == 2 else 0
+        if any(not 0 <= int(t) < K for t in self.params['task_ids']):
+            raise IndexError("task_ids %s outside the dataset's %d targets" % (self.params['task_ids'], K))
+        dms.task_ids_dev(self.params['task_ids'])
+
+    # run_epoch's producer thread with pack_on_device (threaded_batches 'auto'): the dense training step is the autograd path, whose
+    # Python the launching thread is busy with; packing on the producer thread's stream measured 2.30 against 2.91 ms per step inline
+    # (tools/dense_bench.py, profiles/dense_epoch.json)
+    DEVICE_PACK_THREADED = True
+
+    def threaded_batches_default(self) -> bool:
+        if self.params.get('pack_on_device'):
+            return self.DEVICE_PACK_THREADED
+        return super().threaded_batches_default()
+
+    def _device_compact(self) -> bool:
+        """Whether the training step transforms on the compacted (source, type) rows (backward.PropagationStepFn's own test)."""
+        from . import backward
+        D = self.params['hidden_size']
+        return bool(backward.USE_COMPACT_TRANSFORM and ops.compact_supported(D) and D <= 104)
+
+    def _device_epoch(self, data: Any, order: np.ndarray) -> torch.Tensor:
+        """The epoch's order on the device (one upload) and its per-(graph, type) prefix sums (one launch)."""
+        self.prepare_resident_data(data, False)
+        dms = data["molecules_dev"]
+        tab = dms.dense_tables(self.num_edge_types, self.params['tie_fwd_bkwd'])
+        order_dev = dms.upload_order(np.asarray(order, dtype=np.int64))
+        if order_dev.is_cuda:
+            order_dev.record_stream(torch.cuda.current_stream(order_dev.device))    # (allocated on the upload stream, read on this one)
+        return ops.dense_epoch_table(tab["counts_t"], order_dev)
+
+    def device_batch(self, data: Any, epoch_tab: torch.Tensor, start: int, ids: np.ndarray, v: int, is_training: bool) -> Dict[str, Any]:
+        """The batch of graphs `ids` = epoch positions [start, start + len(ids)), assembled on the GPU in one launch
+        (ops.dense_assemble_batch).  The host computes only the per-type sizes, from its own count tables; nothing is read back.
+        Feeds are to_device_batch(pack_dense_batch(...))'s; a training feed also carries '_sparse_form' = (A, index, nin), the form
+        _compute_for_training would derive from A, and both feeds declare max|h0| and max|A| (formats.py)."""
+        dms = data["molecules_dev"]
+        T = self.num_edge_types
+        tab = dms.dense_tables(T, self.params['tie_fwd_bkwd'])
+        ids = np.asarray(ids, dtype=np.int64)
+        mc = tab["mc"][ids].sum(axis=0)
+        compact = bool(is_training) and self._device_compact()
+        type_off = [0] + [int(x) for x in np.cumsum(mc)]
+        type_row_off = [0] + [int(x) for x in np.cumsum(tab["pc"][ids].sum(axis=0))] if compact else None
+        out = ops.dense_assemble_batch(tab, dms.node_feat, dms.targets, dms.label_mask, dms.task_ids_dev(self.params['task_ids']),
+                                       epoch_tab, start, len(ids), v, self.params['hidden_size'], type_off, type_row_off,
+                                       sparse=bool(is_training), compact=compact, arange=dms.arange_i32)
+        A = out['adjacency_matrix']
+        feed = {'initial_node_representation': out['initial_node_representation'], 'adjacency_matrix': A,
+                'node_mask': out['node_mask'], 'num_vertices': int(v), 'target_values': out['target_values'],
+                'target_mask': out['target_mask'], 'num_graphs': len(ids)}
+        if is_training:
+            feed['_sparse_form'] = (A, out['index'], out['nin'])
+        formats.declare_h0_absmax(feed, dms.node_feat_absmax)
+        # (every entry the packer wrote is 0 or 1: max|A| is 1 as soon as the batch has a message -- what a measurement would find)
+        return formats.declare_adjacency_absmax(feed, 1.0 if type_off[-1] else 0.0)
+
     def make_minibatch_iterator(self, data, is_training: bool):
-        """chem_tensorflow_dense.py:195-228."""
+        """chem_tensorflow_dense.py:195-228.  With pack_on_device the batches are assembled on the GPU (device_batch) from the same
+        shuffles, in the same order: the same feeds bit for bit."""
         ms: MoleculeSet = data["molecules"]
         bucketed, bucket_sizes, bucket_at_step = data["bucketed"], data["bucket_sizes"], data["bucket_at_step"]
         if is_training:                                   # :197-200 both shuffles are in place (orders compose over epochs)
@@ -288,16 +378,24 @@ class DenseGGNNChemModel(ChemModel):
         bucket_counters = defaultdict(int)
         dropout_keep_prob = self.params['graph_state_dropout_keep_prob'] if is_training else 1.
         bs = self.params['batch_size']
+        on_device = bool(self.params.get('pack_on_device'))
+        epoch_tab, starts = None, None                    # pack_on_device: the epoch's order on the device, formed at the first batch
         for step in range(len(bucket_at_step)):
             bucket = bucket_at_step[step]
             start_idx = bucket_counters[bucket] * bs
             ids = np.asarray(bucketed[bucket][start_idx:start_idx + bs])
             key = (bucket, bucket_counters[bucket])
             if is_training or key not in data["device_batches"]:
-                db = pack_dense_batch(ms, ids, int(bucket_sizes[bucket]), self.num_edge_types,
-                                      self.params['hidden_size'], self.params['tie_fwd_bkwd'], self.params['task_ids'],
-                                      label_mask=data.get("label_mask"))
-                feed = self.to_device_batch(db)
+                if on_device:
+                    if epoch_tab is None:
+                        order, starts = self._epoch_order(bucketed, bucket_at_step)
+                        epoch_tab = self._device_epoch(data, order)
+                    feed = self.device_batch(data, epoch_tab, starts[step], ids, int(bucket_sizes[bucket]), is_training)
+                else:
+                    db = pack_dense_batch(ms, ids, int(bucket_sizes[bucket]), self.num_edge_types,
+                                          self.params['hidden_size'], self.params['tie_fwd_bkwd'], self.params['task_ids'],
+                                          label_mask=data.get("label_mask"))
+                    feed = self.to_device_batch(db)
                 if not is_training:
                     data["device_batches"][key] = feed
             else:

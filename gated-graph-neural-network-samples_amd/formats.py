@@ -198,9 +198,23 @@ def nin_consistent(placeholders: Dict[str, Any], row_ptr: Optional[torch.Tensor]
 _ADJ_MAX = _MaxCache()
 
 
-def adjacency_absmax(A: torch.Tensor) -> float:
-    """max |A| of a dense model's fed adjacency tensor (cached per tensor and version): the bound on the aggregated activations
+def declare_adjacency_absmax(feed: Dict[str, Any], value: float) -> Dict[str, Any]:
+    """A dense packer's statement "max |A| of THIS adjacency tensor is `value`" (it wrote the 0 / 1 entries itself), stored next to
+    the tensor with its identity and version like declare_h0_absmax's: an adjacency tensor replaced or written afterwards is measured."""
+    A = feed['adjacency_matrix']
+    feed['adjacency_absmax'] = float(value)
+    feed['_adjacency_absmax_of'] = (weakref.ref(A), A._version)
+    return feed
+
+
+def adjacency_absmax(A: torch.Tensor, placeholders: Optional[Dict[str, Any]] = None) -> float:
+    """max |A| of a dense model's fed adjacency tensor: the packer's declaration in `placeholders` (declare_adjacency_absmax) while it
+    is about this tensor at this version, else measured (cached per tensor and version).  The bound on the aggregated activations
     assumes entries of magnitude <= 1 -- the reference's 0 / 1 matrices; a foreign feed may weight its edges."""
+    if placeholders is not None:
+        v, of = placeholders.get('adjacency_absmax'), placeholders.get('_adjacency_absmax_of')
+        if v is not None and of is not None and of[0]() is A and of[1] == A._version:
+            return float(v)
     if A.numel() == 0:
         return 0.0
     if A.dtype != torch.float32:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import torch
 
@@ -1397,6 +1397,149 @@ def gcn_assemble_batch(node_ptr: torch.Tensor, feat: torch.Tensor, csr: Sequence
     _launch("gcn_assemble_batch", lambda: lib.ggnn_gcn_assemble_batch(c_ds, Gd, A, targets.shape[1], nz(task_ids), K, _ptr(epoch_tab), Ge,
                                                                       s, G, V, E, D, c_out, _stream()))
     return GCNGraph(g_rp, g_col, g_val, g_rpt, g_colt, g_valt, V), h0, gnl, graph_ptr, uid, tv, tm
+
+
+# ---- dense GGNN batches from dataset-level tables (DenseGGNNChemModel with pack_on_device) --------------------------------------
+# data_device.dense_tables_host's device arrays that the assembly reads; the last nine are the compaction tables
+DENSE_GRAPH_TABLES = ("node_ptr", "counts_t", "msg_ptr", "msg", "nin", "in_ptr", "slot_msg", "pair_ptr", "pair_node", "msg_crow",
+                      "src_ptr", "src_msg", "rows_msg", "pair_rows", "node_pptr", "node_order")
+
+
+def dense_epoch_table(counts_t: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """Prefix sums of the per-graph message and pair counts over an epoch's order, on the device (ggnn_pack_batch_tables, one launch
+    per epoch).  counts_t int32 [2T, Gd] (messages per type, then active (source, type) pairs per type), order int64 [Ge] -> int32
+    [Ge | 2T x (Ge+1)]: the order as int32, then per row the totals of the graphs before each epoch position."""
+    lib = _lib.load()
+    _req(counts_t, torch.int32, "counts_t")
+    _req(order, torch.int64, "order")
+    rows = counts_t.shape[0] if counts_t.dim() == 2 else 0
+    if rows < 2 or rows % 2 or order.dim() != 1 or order.device != counts_t.device:
+        raise ValueError("counts_t must be [2T, Gd] and order [Ge] on its device")
+    Ge = order.numel()
+    tab = torch.empty(Ge + rows * (Ge + 1), dtype=torch.int32, device=order.device)
+    _launch("dense_epoch_table", lambda: lib.ggnn_pack_batch_tables(_ptr(counts_t), counts_t.shape[1], rows, _ptr(order) if Ge else None,
+                                                                    Ge, None, None, 0, None, 0, _ptr(tab), None, None, _stream()))
+    return tab
+
+
+def dense_assemble_batch(tables, feat: torch.Tensor, targets: torch.Tensor, label_mask: Optional[torch.Tensor], task_ids: torch.Tensor,
+                         epoch_tab: torch.Tensor, start: int, num_graphs: int, num_vertices: int, hidden_size: int,
+                         type_off: Optional[Sequence[int]] = None, type_row_off: Optional[Sequence[int]] = None, sparse: bool = False,
+                         compact: bool = False, arange=None) -> Dict[str, Any]:
+    """One dense batch, graphs [start, start + num_graphs) of the epoch whose dense_epoch_table is `epoch_tab`, each padded to
+    num_vertices nodes, in one launch (ggnn_dense_assemble_batch) from data_device.dense_tables_host's arrays on the device (`tables`,
+    by the names of DENSE_GRAPH_TABLES), feat float32 [Nd, A], targets float32 [Gd, num_targets], label_mask float32 [Gd, K] or None,
+    task_ids int64 [K] (target columns).
+    -> {'initial_node_representation' [G, v, D], 'adjacency_matrix' [G, T, v, v], 'node_mask' [G, v], 'target_values' [K, G],
+        'target_mask' [K, G]}: data.pack_dense_batch's arrays.  sparse: also 'nin' [G*v, T] and 'index', the MessageIndex that
+    build_message_index builds from the batch's A.nonzero() (type_off: the batch's per-type message offsets, host ints [T+1]);
+    compact: with the CompactSources, source index and CompactBackward that build_compact_sources / compact_backward attach to it
+    (type_row_off: per-type pair offsets; arange(n): an int32 ramp for the backward's identity rows, default torch.arange).
+    Nothing is read back; every argument is checked before the launch."""
+    def req(t, dtype, name):                         # (dtype and layout first, the device last: checkable without a GPU)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError("%s must be a %s tensor, got %s" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return t
+    if compact and not sparse:
+        raise ValueError("the compaction structures belong to the sparse form: compact needs sparse")
+    names = DENSE_GRAPH_TABLES if compact else DENSE_GRAPH_TABLES[:7]
+    tab = {}
+    for name in names:
+        if tables.get(name) is None:
+            raise ValueError("dense table %r missing" % name)
+        tab[name] = req(tables[name], torch.float32 if name == "nin" else torch.int32, name)
+    req(feat, torch.float32, "feat")
+    req(targets, torch.float32, "targets")
+    if label_mask is not None:
+        req(label_mask, torch.float32, "label_mask")
+    req(task_ids, torch.int64, "task_ids")
+    req(epoch_tab, torch.int32, "epoch_tab")
+    dev = feat.device
+    if any(t.device != dev for t in list(tab.values()) + [targets, task_ids, epoch_tab] + ([label_mask] if label_mask is not None else [])):
+        raise ValueError("dense_assemble_batch: every table must be on %s" % dev)
+    ct = tab["counts_t"]
+    if ct.dim() != 2 or ct.shape[0] % 2 or not 1 <= ct.shape[0] // 2 <= 16 or feat.dim() != 2 or tab["msg"].dim() != 2:
+        raise ValueError("counts_t must be [2T, Gd] with 1 <= T <= 16, feat [Nd, A] and msg [Md, 2]")
+    T, Gd = ct.shape[0] // 2, ct.shape[1]
+    Nd, A = feat.shape
+    Md = tab["msg"].shape[0]
+    shapes = {"node_ptr": (Gd + 1,), "msg_ptr": (Gd + 1,), "msg": (Md, 2), "nin": (Nd, T), "in_ptr": (Nd,), "slot_msg": (Md,)}
+    if compact:
+        Pd = tab["pair_node"].numel()
+        shapes.update(pair_ptr=(Gd + 1,), pair_node=(Pd,), msg_crow=(Md,), src_ptr=(Nd * T,), src_msg=(Md,), rows_msg=(Md,),
+                      pair_rows=(Pd,), node_pptr=(Nd,), node_order=(Pd,))
+    for name, shape in shapes.items():
+        if tuple(tab[name].shape) != shape:
+            raise ValueError("dense table %s must be %s, got %s" % (name, shape, tuple(tab[name].shape)))
+    if targets.dim() != 2 or targets.shape[0] != Gd or task_ids.dim() != 1:
+        raise ValueError("targets must be [%d, num_targets] and task_ids [K]" % Gd)
+    K = task_ids.numel()
+    if label_mask is not None and tuple(label_mask.shape) != (Gd, K):
+        raise ValueError("label_mask must be [%d, %d], got %s" % (Gd, K, tuple(label_mask.shape)))
+    if epoch_tab.dim() != 1 or epoch_tab.numel() < 2 * T or (epoch_tab.numel() - 2 * T) % (2 * T + 1):
+        raise ValueError("epoch_tab must be dense_epoch_table's [Ge + 2T (Ge + 1)]")
+    Ge = (epoch_tab.numel() - 2 * T) // (2 * T + 1)
+    s, G, v, D = int(start), int(num_graphs), int(num_vertices), int(hidden_size)
+    if s < 0 or G < 0 or s + G > Ge:
+        raise ValueError("batch [%d, %d) outside the epoch's %d graphs" % (s, s + G, Ge))
+    if v < 1:
+        raise ValueError("num_vertices %d: a dense batch has at least one vertex per graph" % v)
+    if D <= 0 or A > D:
+        raise ValueError("hidden_size %d must be positive and >= the annotation size %d" % (D, A))
+    if G * v * T >= 2 ** 31 - 1 or T * v * v >= 2 ** 31 or v * D >= 2 ** 31:
+        raise ValueError("batch too large for 32-bit indices: %d graphs of %d vertices, %d edge types, hidden size %d" % (G, v, T, D))
+
+    def offsets(off, name):
+        off = [int(x) for x in off] if off is not None else None
+        if off is None or len(off) != T + 1 or off[0] != 0 or any(b < a for a, b in zip(off[:-1], off[1:])) or off[-1] >= 2 ** 31 - 1:
+            raise ValueError("%s must be T + 1 = %d non-decreasing offsets from 0, got %s" % (name, T + 1, off))
+        return off
+    type_off = offsets(type_off, "type_off") if sparse else None
+    type_row_off = offsets(type_row_off, "type_row_off") if compact else None
+    M = type_off[-1] if sparse else 0
+    R = type_row_off[-1] if compact else 0
+    if not feat.is_cuda:
+        raise TypeError("dense_assemble_batch needs CUDA/HIP tensors (there is no CPU implementation)")
+    lib = _lib.load()
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    V = G * v
+    out = {'initial_node_representation': f32(G, v, D), 'adjacency_matrix': f32(G, T, v, v), 'node_mask': f32(G, v),
+           'target_values': f32(K, G), 'target_mask': f32(K, G)}
+    sp = [None] * 15
+    if sparse:
+        sp[:5] = [f32(V, T), i32(M, 2), i32(V + 1), i32(M), i32(M)]                  # nin, adj, row_ptr, gather_row, msg_perm
+    if compact:
+        sp[5:] = [i32(max(R, 1)), i32(M), i32(V * T + 1), i32(M), i32(M), i32(R + 1), i32(M), i32(M), i32(V + 1), i32(R)]
+    nz = lambda t: _ptr(t) if t is not None and t.numel() else None
+    # (counts_t is not passed: the epoch table holds its prefix sums)
+    ds = [tab["node_ptr"], feat, targets, label_mask] + [tab.get(n) for n in DENSE_GRAPH_TABLES[2:]]
+    c_ds = (ctypes.c_void_p * 18)(*[nz(t) for t in ds])
+    outs = [out[k] for k in ('initial_node_representation', 'adjacency_matrix', 'node_mask', 'target_values', 'target_mask')] + sp
+    c_out = (ctypes.c_void_p * 20)(*[nz(t) for t in outs])
+    c_to = (ctypes.c_int64 * (T + 1))(*(type_off or [0] * (T + 1)))
+    c_tro = (ctypes.c_int64 * (T + 1))(*(type_row_off or [0] * (T + 1)))
+    _launch("dense_assemble_batch", lambda: lib.ggnn_dense_assemble_batch(
+        c_ds, Gd, A, T, targets.shape[1], nz(task_ids), K, _ptr(epoch_tab), Ge, s, G, v, D, M, R, c_to, c_tro, 1 if sparse else 0, c_out,
+        _stream()))
+    if sparse:
+        nin, adj, row_ptr, gather_row, msg_perm = sp[:5]
+        index = MessageIndex(adj, type_off, row_ptr, gather_row, msg_perm, V, T)
+        if compact:
+            pair_node, gather_c, src_rp, src_g, src_m, rows_rp, rows_g, rows_m, node_rp, node_order = sp[5:]
+            comp = index._compact = CompactSources(pair_node[:max(R, 1)], type_row_off, gather_c)
+            index._source_index = MessageIndex(adj, type_off, src_rp, src_g, src_m, V * T, T)
+            bwd = object.__new__(CompactBackward)
+            bwd.rows_index = SegmentIndex(rows_rp, rows_g, R, rows_m)
+            bwd.source_node_index = SegmentIndex(src_rp[::T].contiguous(), src_g, V, src_m)
+            bwd.node_index = SegmentIndex(node_rp, node_order, V)
+            ramp = arange(max(R, 1)) if arange is not None else torch.arange(max(R, 1), dtype=torch.int32, device=dev)
+            bwd.identity = CompactSources(ramp, type_row_off, gather_c)
+            comp._bwd = bwd
+        out.update(nin=nin, index=index)
+    return out
 
 
 def gcn_fused_supported(D: int) -> bool:

@@ -562,6 +562,28 @@ int ggnn_pack_batch_tables(const int32_t* counts_t, int Gd, int rows, const int6
 int ggnn_gcn_assemble_batch(const void* const* ds_tables, int Gd, int A, int num_targets, const int64_t* task_ids, int K,
                             const int32_t* epoch_tab, int Ge, int s, int G, int V, int nnz, int D, void* const* out,
                             ggnn_stream_t stream);
+/* Dense GGNN batch from dataset-level tables (chem_tensorflow_dense.py:143-193 + :30-36): graphs [s, s + G) of an epoch's order, each
+ * padded to v vertices, one launch (one workgroup per graph).  With sparse != 0 also the sparse form of the batch's adjacency tensor
+ * over its G*v nodes, as ops.build_message_index builds it from A.nonzero() and build_compact_sources / compact_backward derive it.
+ *   ds_tables [18] (data_device.dense_tables_host, local node ids, graph after graph): 0 node_ptr i32[Gd+1]  1 node features
+ *     f32[Nd, A]  2 targets f32[Gd, num_targets]  3 label mask f32[Gd, K] or NULL  4 msg_ptr i32[Gd+1]  5 messages i32[Md, 2]
+ *     (src, dst), ordered (type, dst, src) inside a graph  6 nin f32[Nd, T]  7 in_ptr i32[Nd]  8 slot_msg i32[Md]; compaction
+ *     tables (NULL pair_ptr: none): 9 pair_ptr i32[Gd+1]  10 pair_node i32[Pd]  11 msg_crow i32[Md]  12 src_ptr i32[Nd*T]
+ *     13 src_msg i32[Md]  14 rows_msg i32[Md]  15 pair_rows i32[Pd]  16 node_pptr i32[Nd]  17 node_order i32[Pd].
+ *   task_ids: device i64[K], target column of each task.
+ *   epoch_tab: batch_tab of ggnn_pack_batch_tables over the whole epoch order with rows (messages per type, then active
+ *     (source, type) pairs per type): gid[Ge] | pre[2T][Ge+1].
+ *   M, R, type_off[T+1], type_row_off[T+1] (host): the batch's message / pair totals and per-type offsets (sparse; R and
+ *     type_row_off with compaction tables only).
+ *   out [20]: 0 h0 f32[G, v, D]  1 adjacency f32[G, T, v, v] (every entry, 0 / 1)  2 node mask f32[G, v]  3 target_values f32[K, G]
+ *     (label * mask)  4 target_mask f32[K, G];  sparse: 5 nin f32[G*v, T]  6 adj i32[M, 2] (type-major)  7 row_ptr i32[G*v+1]
+ *     8 gather_row i32[M] (src*T + type)  9 msg_perm i32[M];  compaction: 10 pair_node i32[R]  11 compact gather rows i32[M]
+ *     12 by-source row_ptr i32[G*v*T+1]  13 its gather rows (dst) i32[M]  14 its messages i32[M]  15 compact-row row_ptr i32[R+1]
+ *     16 its gather rows i32[M]  17 its messages i32[M]  18 node row_ptr i32[G*v+1]  19 node order i32[R].
+ *   Any v >= 1, D > 0 with A <= D, 1 <= T <= 16. */
+int ggnn_dense_assemble_batch(const void* const* ds_tables, int Gd, int A, int T, int num_targets, const int64_t* task_ids, int K,
+                              const int32_t* epoch_tab, int Ge, int s, int G, int v, int D, int M, int R, const int64_t* type_off,
+                              const int64_t* type_row_off, int sparse, void* const* out, ggnn_stream_t stream);
 
 /* ---- the optimisation step of the default sparse model as native launch sequences (chem_tensorflow.py:183-191 over
  * chem_tensorflow_sparse.py:117-218; ggnn_train.hip) -----------------------------------------------------------------------------
