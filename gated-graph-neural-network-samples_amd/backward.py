@@ -54,6 +54,19 @@ USE_NATIVE_STEP = os.environ.get("GGNN_NATIVE_STEP", "1") != "0"
 TRAIN_GATHER_IN_GRU = os.environ.get("GGNN_TRAIN_GATHER_IN_GRU", "1") != "0"
 
 
+def compact_training(D: int) -> bool:
+    """Whether a training step at node-state width D runs on the compacted message transform: wherever the width has one AND a
+    single-launch GRU backward (32 / 64 / 100 on whole weight blocks, 128 / 192 / 256 on column panels).  The gate was introduced
+    as `D <= 104` together with the compacted training route, when the fused backward existed for those widths only; no other
+    reason is recorded.  Widths with a compacted transform but no fused backward keep the dense form."""
+    return bool(USE_COMPACT_TRANSFORM and ops.compact_supported(D) and (D <= 104 or ops.gru_bwd_is_fused(D)))
+
+
+def xty_fits(D: int, N: int) -> bool:
+    """The shapes ONE ggnn_xty_f32 launch takes with its ones row (the fused kernels' small hidden sizes)."""
+    return D <= 104 and N <= 208
+
+
 class _WeightGradSink:
     def __init__(self):
         self.targets = None          # {data_ptr of a variable: float32 buffer of its shape}
@@ -171,7 +184,7 @@ def weight_grad(x_segs, dy: torch.Tensor):
     Shapes of the fused kernels' hidden sizes: ONE ggnn_xty_f32 launch, the bias gradient as its ones row.  Wider ones (hidden
     128 / 192 / 256): per segment on the row-split kernel ggnn_gemm_tn_f32, the bias gradient by ggnn_colsum_f32."""
     D, N = x_segs[0].shape[1], dy.shape[1]
-    if D <= 104 and N <= 208:
+    if xty_fits(D, N):
         K = len(x_segs) * D
         w = ops.xty(list(x_segs), dy, ones_row=True)
         return w[:K], w[K]
@@ -245,7 +258,7 @@ class PropagationStepFn(torch.autograd.Function):
         if ew_mask is not None:
             # `edge_weights` is the variable: multiply by its masked copy; backward() sends the gradient back through the mask
             edge_weights = _MASKED.get(edge_weights, float(ew_mask[0]), int(ew_mask[1]))
-        if USE_COMPACT_TRANSFORM and ops.compact_supported(D) and D <= 104:
+        if compact_training(D):
             # transform only the (node, type) pairs that emit a message (~1.2 V rows instead of T V)
             from .autograd import _PACKED
             comp = getattr(index, "_compact", None)
@@ -303,7 +316,12 @@ class PropagationStepFn(torch.autograd.Function):
             pW, pb, pWg, pbg, pWc, pbc = ctx.var_ptrs
             sW, sb, sWg, sbg, sWc, sbc = ctx.var_shapes
             tg = [_SINK.target(p_, s_) for p_, s_ in ((pWg, sWg), (pbg, sbg), (pWc, sWc), (pbc, sbc))]
-            if all(t is not None for t in tg):
+            if not xty_fits(D, 2 * D):
+                # 128 / 192 / 256: dpg is wider than one ggnn_xty_f32 launch takes -> per segment on the row-split kernel, whose
+                # products cannot add into the sink's buffers: returned to autograd like the unfused route's
+                dWc, dbc = weight_grad(xs + [rh], dpc)
+                dWg, dbg = weight_grad(xs + [h], dpg)
+            elif all(t is not None for t in tg):
                 def gru_weight_products():             # (the reduction kernel adds into the gradient buffers; bias = the ones row)
                     ops.xty(xs + [rh], dpc, ones_row=True, add_to=tg[2], add_bias_to=tg[3])
                     ops.xty(xs + [h], dpg, ones_row=True, add_to=tg[0], add_bias_to=tg[1])
@@ -318,7 +336,9 @@ class PropagationStepFn(torch.autograd.Function):
         dbias = None
         if ctx.has_bias:                                                       # :202-204  incoming += nin @ edge_biases
             tb = _SINK.target(ctx.var_ptrs[1], ctx.var_shapes[1])
-            if tb is not None:
+            if not xty_fits(D, T):
+                dbias = ops.gemm_tn(nin, dinc)                                 # 128 / 192 / 256: a K = D slab is too wide for ggnn_xty_f32
+            elif tb is not None:
                 _on_side_stream([dinc, nin], lambda: _SINK.add(ctx.var_ptrs[1], tb, ops.xty([dinc], nin).t()))
             else:
                 dbias = ops.xty([dinc], nin).t().contiguous()                  # (dinc^T nin)^T = nin^T dinc   [T, D]

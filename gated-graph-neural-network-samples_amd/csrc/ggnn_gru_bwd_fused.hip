@@ -20,6 +20,7 @@
 // Stage order per tile:   h block of Wc^T (-> drh, dpr);  h blocks of Wg_r^T, Wg_u^T (-> dh);
 //                         then per x segment: Wc^T, Wg_r^T, Wg_u^T blocks (-> dx_s)
 #include "ggnn_split.hpp"
+#include "ggnn_gru_bwd.hpp"
 #include <type_traits>
 
 // 1: the stage products recompute the lane parts of their LDS addresses per call (stage_mma_split's REMAT): 52-72 -> 36 B of scratch
@@ -29,18 +30,6 @@
 #endif
 
 namespace ggnn {
-
-struct GruBwdArgs {
-    const float* g; const float* h; const float* r; const float* u; const float* c;
-    float* dpc; float* dpg; float* rh; float* dh;
-    float* dx[3];                       // nx outputs [V,D]; the last one is d_incoming (scaled when use_avg)
-    const float* nin; int T; int use_avg;
-    int nx; int V; int act;
-    // optional: g_eff[v] = g[v] + sum over the (up to four) rows gz_heads[v] names of gz -- the per-node sum that closes the
-    // PREVIOUS timestep's transform backward (dh[v] += sum_t Z[row(v,t)]), taken on load here instead of by a launch of its own
-    const float* gz; const int* gz_heads;
-    unsigned long long* tdbg;           // debug: s_memtime stamps of workgroup 0 (GGNN_BWD_TPTR; tools/gru_bwd_timeline.py)
-};
 
 // image i of the packed backward weights (image[k][n] = B(k, n) with out[:, n] = sum_k A[:, k] B(k, n)):
 //   0: Wc^T h block      B(k,n) = Wc[nx*D + n][k]
@@ -577,9 +566,11 @@ static int dispatch_gru_bwd(const GruBwdArgs& a, const float* Wg, const float* W
 #ifndef GGNN_GRU_BWD_TU_SPLIT
 using namespace ggnn;
 
-extern "C" int ggnn_gru_bwd_is_fused(int D) { return D == 100 || D == 64 || D == 32; }
+// whole-block kernel (this file) for 32 / 64 / 100, column-panel kernel (ggnn_gru_bwd_panel.hip) for 128 / 192 / 256
+extern "C" int ggnn_gru_bwd_is_fused(int D) { return D == 100 || D == 64 || D == 32 || gru_bwd_panel_supported(D); }
 
 extern "C" size_t ggnn_gru_bwd_packed_bytes(int D, int nx) {
+    if (gru_bwd_panel_supported(D)) return gru_bwd_panel_packed_bytes(D, nx);
     size_t img = 0;
     const bool sp = split_matrix_path();
     switch (D) {
@@ -619,7 +610,8 @@ static int gru_bwd_fused_impl(const float* g, const float* gz, const int32_t* gz
                                       float* const* dx, const float* nin, int T, int use_avg, int nx, int V, int D, int act,
                                       ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V >= 0 && nx >= 1 && nx <= 3, "bad sizes V=%d nx=%d", V, nx);
-    if (!ggnn_gru_bwd_is_fused(D)) return fail(GGNN_E_UNSUPPORTED, "no fused GRU backward for hidden size %d", D);
+    if (!ggnn_gru_bwd_is_fused(D))
+        return fail(GGNN_E_UNSUPPORTED, "no fused GRU backward for hidden size %d (supported: 32, 64, 100, 128, 192, 256)", D);
     GGNN_CHECK_ARG(act == GGNN_ACT_TANH || act == GGNN_ACT_RELU, "unknown activation %d", act);
     GGNN_CHECK_ARG(packed && aligned16(packed) && (!Wg || Wc), "packed weights missing");
     GruBwdArgs a{};
@@ -639,6 +631,7 @@ static int gru_bwd_fused_impl(const float* g, const float* gz, const int32_t* gz
         }
     }
     hipStream_t st = (hipStream_t)stream;
+    if (gru_bwd_panel_supported(D)) return gru_bwd_panel_dispatch(D, a, Wg, Wc, packed, st);
     switch (D) {
         case 100: return dispatch_gru_bwd<100>(a, Wg, Wc, packed, st);
         case 64: return dispatch_gru_bwd<64>(a, Wg, Wc, packed, st);

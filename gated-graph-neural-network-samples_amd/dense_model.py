@@ -328,7 +328,7 @@ class DenseGGNNChemModel(ChemModel):
         """Whether the training step transforms on the compacted (source, type) rows (backward.PropagationStepFn's own test)."""
         from . import backward
         D = self.params['hidden_size']
-        return bool(backward.USE_COMPACT_TRANSFORM and ops.compact_supported(D) and D <= 104)
+        return backward.compact_training(D)
 
     def _device_epoch(self, data: Any, order: np.ndarray) -> torch.Tensor:
         """The epoch's order on the device (one upload) and its per-(graph, type) prefix sums (one launch)."""

@@ -107,9 +107,9 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
             dpc, dpg, rh, dh, dxs = ops.gru_bwd_fused(g, h, r, u, c, _PACKED.gru_bwd(cell[0], cell[2], nx, D), nin, ctx.use_avg, nx,
                                                       ctx.activation)
             dinc, d_res = dxs[-1], dxs[:-1]
-            wc = ops.xty(xs + [rh], dpc, ones_row=True)
-            wg = ops.xty(xs + [h], dpg, ones_row=True)
-            dcell = [wg[:Kx], wg[Kx], wc[:Kx], wc[Kx]]
+            dWc, dbc = weight_grad(xs + [rh], dpc)          # (one ggnn_xty_f32 launch each where the shapes fit, see weight_grad)
+            dWg, dbg = weight_grad(xs + [h], dpg)
+            dcell = [dWg, dbg, dWc, dbc]
         else:
             from .backward import _gru_backward_unfused
             from . import _lib

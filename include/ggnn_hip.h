@@ -473,15 +473,19 @@ int ggnn_cudnn_gru_train_f32(const float* const* x_segs, int nx, const float* h,
 int ggnn_cudnn_gru_bwd_stage_f32(const float* g, const float* h, const float* r, const float* u, const float* c, const float* hc,
                                  float* dpc, float* dpg, float* dh, float* dhc, int V, int D, ggnn_stream_t stream);
 
-/* The whole GRU backward of a timestep in ONE launch (D in {32, 64, 100}; ggnn_gru_bwd_fused.hip) -- the mirror image of the
+/* The whole GRU backward of a timestep in ONE launch -- D in {32, 64, 100}: whole transposed weight blocks, ggnn_gru_bwd_fused.hip;
+ * D in {128, 192, 256}: 64-column panels of them, ggnn_gru_bwd_panel.hip; ggnn_gru_bwd_is_fused(D) is 1 for these six and 0 for
+ * every other D, which the launch calls refuse with GGNN_E_UNSUPPORTED -- the mirror image of the
  * fused forward kernel: from g = dL/dh' and the saved h, r, u, c it computes, chained through registers,
  *   dpc = g (1-u) act'(c);  dpu = g (h-c) u (1-u);  drh = dpc Wc^T[h rows];  dpr = drh h r (1-r);
  *   dh  = g u + drh r + [dpr|dpu] Wg^T[h rows];   dx[s] = dpc Wc^T[x_s rows] + [dpr|dpu] Wg^T[x_s rows]   (s < nx)
  *   dx[nx-1] is divided by (sum_t nin + 1e-7) when use_avg (d_incoming of the mean aggregation, chem_tensorflow_sparse.py:206-209)
  * and writes dpc [V,D], dpg = [dpr|dpu] [V,2D] and rh = r*h [V,D] for the weight-gradient products (ggnn_xty_f32).
  *   Wg [(nx+1)D, 2D], Wc [(nx+1)D, D] or NULL: with weights given, their transposed-block stage images are (re)built into
- *   `packed` (ggnn_gru_bwd_packed_bytes(D, nx) bytes) first; NULL: `packed` holds them already.  g == NULL: pack only.
- *   dx: HOST array of nx device pointers [V,D]. */
+ *   `packed` (ggnn_gru_bwd_packed_bytes(D, nx) bytes; 0 for an unsupported D) first; NULL: `packed` holds them already.
+ *   g == NULL: pack only.  dx: HOST array of nx device pointers [V,D].  nx in 1..3; V * 2D < 2^30 (32-bit byte offsets), beyond
+ *   it GGNN_E_UNSUPPORTED.  At D in {128, 192, 256} the weight-gradient products that read dpc / dpg / rh are ggnn_gemm_tn_f32's
+ *   (dpg is 2D = up to 512 columns wide; ggnn_xty_f32 takes 256). */
 int ggnn_gru_bwd_is_fused(int D);
 size_t ggnn_gru_bwd_packed_bytes(int D, int nx);
 int ggnn_gru_bwd_fused_f32(const float* g, const float* h, const float* r, const float* u, const float* c, const float* Wg,
