@@ -357,6 +357,71 @@ class PropagationStepFn(torch.autograd.Function):
         return (dh, None, None, dW, dbias, None, None, dWg, dbg, dWc, dbc, None, None, *d_res)
 
 
+class DensePropagateFn(torch.autograd.Function):
+    """ALL timesteps of the dense model (chem_tensorflow_dense.py:93-117) as one differentiable op on the graph-resident kernels:
+    forward = the saving launch (ops.dense_propagate_save), backward = one launch that walks the timesteps in reverse
+    (ops.dense_propagate_bwd) and then the weight and bias gradients, once per variable on rows stacked over the timesteps -- the
+    model shares one GRU and one edge-weight tensor across timesteps (:84-102):
+        dWg  = [x | h]^T dpg       dbg  = colsum(dpg)
+        dWc  = [x | r*h]^T dpc     dbc  = colsum(dpc)
+        dW_e = h^T dM_e            db_e = sum_rows nin_e * dx          (nin_e[dst] = sum_src A_e[dst, src])
+    Inside weight_gradient_sink the products go to the optimiser's flat gradient buffer on the side stream, as GCNLayerFn's do."""
+
+    @staticmethod
+    def forward(ctx, h0, A, nin, W, bias, Wg, bg, Wc, bc, steps, fmt):
+        from .autograd import _PACKED
+        D = h0.shape[2]
+        out, saved = ops.dense_propagate_save(h0, A, _PACKED.dense_edge(W), _PACKED.dense_gru(Wg, Wc, D), bias, bg, bc, steps, fmt)
+        ctx.var_ptrs = tuple(None if t is None else t.data_ptr() for t in (W, bias, Wg, bg, Wc, bc))
+        ctx.var_shapes = tuple(None if t is None else tuple(t.shape) for t in (W, bias, Wg, bg, Wc, bc))
+        ctx.save_for_backward(A, nin, W, Wg, Wc, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .autograd import _PACKED
+        A, nin, W, Wg, Wc, saved = ctx.saved_tensors
+        steps, N, D = saved.shape[1], saved.shape[1] * saved.shape[2], saved.shape[3]
+        E = W.shape[0]
+        need = ctx.needs_input_grad
+        d_h0, dpc, dpg, dx, dM = ops.dense_propagate_bwd(g.contiguous(), A, _PACKED.dense_bwd(W, Wg, Wc), saved, need_d_h0=need[0])
+        h, x, rh = (saved[k].view(N, D) for k in (0, 1, 5))            # stacked over the timesteps
+        dpc, dpg, dx, dM = dpc.view(N, D), dpg.view(N, 2 * D), dx.view(N, D), dM.view(N, E * D)
+        pW, pb, pWg, pbg, pWc, pbc = ctx.var_ptrs
+        sW, sb, sWg, sbg, sWc, sbc = ctx.var_shapes
+        dW = dbias = dWg = dbg = dWc = dbc = None
+        # ---- the GRU's four variables: two products, the bias gradients as their ones rows ------------------------------------
+        if any(need[i] for i in (5, 6, 7, 8)):
+            tg = [_SINK.target(p_, s_) for p_, s_ in ((pWg, sWg), (pbg, sbg), (pWc, sWc), (pbc, sbc))]
+            if all(t is not None for t in tg) and xty_fits(D, 2 * D):
+                def gru_weight_products():
+                    ops.xty([x, rh], dpc, ones_row=True, add_to=tg[2], add_bias_to=tg[3])
+                    ops.xty([x, h], dpg, ones_row=True, add_to=tg[0], add_bias_to=tg[1])
+                    _SINK.mark(pWg, pbg, pWc, pbc)
+                _on_side_stream([saved, dpc, dpg], gru_weight_products)
+            else:
+                dWc, dbc = weight_grad([x, rh], dpc)
+                dWg, dbg = weight_grad([x, h], dpg)
+        # ---- the edge weights: h^T [dM_0 | dM_1 | ..] on the row-split kernel, [D, E D] -> [E, D, D] ----------------------------
+        if need[3]:
+            edge_product = lambda: _tn(h, dM).view(D, E, D).permute(1, 0, 2).contiguous()
+            tW = _SINK.target(pW, sW)
+            if tW is not None:
+                _on_side_stream([saved, dM], lambda: _SINK.add(pW, tW, edge_product()))
+            else:
+                dW = edge_product().view(sW)
+        # ---- the edge biases: acts += nin @ b_e in every timestep (:107-108) --------------------------------------------------------
+        if pb is not None and need[4]:
+            nin_rows = nin.repeat(steps, 1)                            # [steps b v, E]: the same in-degrees in every timestep
+            bias_product = lambda: _tn(nin_rows, dx)                   # nin^T dx [E, D] (any E: ggnn_xty_f32 takes N % 4 == 0 only)
+            tb = _SINK.target(pb, sb)
+            if tb is not None:
+                _on_side_stream([dx, nin_rows], lambda: _SINK.add(pb, tb, bias_product()))
+            else:
+                dbias = bias_product().view(sb)
+        return d_h0, None, None, dW, dbias, dWg, dbg, dWc, dbc, None, None
+
+
 def transform_backward(index, comp, h, W, dinc, dh, message_weights=None, sink=None):
     """Backward of  incoming[v] = sum over the messages into v of (w_m *) h[src_m] W_type(m)  given dinc = dL/d incoming:
     adds the state gradient to `dh` in place and returns dW [T,D,D].  On the compact (source node, type) rows whatever form

@@ -346,9 +346,19 @@ extern "C" int ggnn_dense_propagate_is_split(int v, int E, int D) {
     return (want_split && split_matrix_path() && ggnn_dense_propagate_supported(v, E, D) && dense_split_supported(v, E, D)) ? 1 : 0;
 }
 
-extern "C" int ggnn_dense_propagate_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
-                                        const float* edge_bias, const float* bg, const float* bc, float* out, int b, int v, int E,
-                                        int D, int steps, int fmt, ggnn_stream_t stream) {
+extern "C" int ggnn_dense_train_supported(int v, int E, int D) {
+    return (ggnn_dense_propagate_is_split(v, E, D) && dense_bwd_supported(v, E, D)) ? 1 : 0;
+}
+
+extern "C" size_t ggnn_dense_train_saved_bytes(int b, int v, int D, int steps) {
+    if (b <= 0 || v <= 0 || D <= 0 || steps <= 0) return 0;
+    return (size_t)6 * steps * b * v * D * sizeof(float);
+}
+
+// saved != NULL: the saving launch of the training route (split kernel only)
+static int dense_propagate(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
+                           const float* edge_bias, const float* bg, const float* bc, float* out, int b, int v, int E,
+                           int D, int steps, int fmt, float* saved, hipStream_t st) {
     GGNN_CHECK_ARG(b >= 0 && steps >= 1, "bad sizes b=%d steps=%d", b, steps);
     GGNN_CHECK_ARG(fmt == 0 || fmt == GGNN_GRU_FMT_F16X2 || fmt == GGNN_GRU_FMT_BF16X3, "fmt %d is not a GGNN_GRU_FMT_* value", fmt);
     if (!ggnn_dense_propagate_supported(v, E, D))
@@ -357,9 +367,8 @@ extern "C" int ggnn_dense_propagate_f32(const float* h0, const float* A, const f
     GGNN_CHECK_ARG(h0 && A && edge_packed && gru_packed && bg && bc && out, "null pointer");
     GGNN_CHECK_ARG(aligned16(h0) && aligned16(out) && aligned16(edge_packed) && aligned16(gru_packed) && (!edge_bias || aligned16(edge_bias)),
                    "pointers must be 16-byte aligned");
-    DenseGraphArgs a{h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, steps, nullptr};
+    DenseGraphArgs a{h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, steps, nullptr, saved};
     { const char* e = getenv("GGNN_DG_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
-    hipStream_t st = (hipStream_t)stream;
     if (ggnn_dense_propagate_is_split(v, E, D)) {
         DenseGraphArgs s = a;
         s.eimg = edge_packed + (dense_edge_f32_bytes(D, E) + dense_split_images_offset(D, E, fmt)) / sizeof(float);
@@ -372,4 +381,24 @@ extern "C" int ggnn_dense_propagate_f32(const float* h0, const float* A, const f
     GGNN_DG_CASE(32, 4) GGNN_DG_CASE(32, 8) GGNN_DG_CASE(32, 2) GGNN_DG_CASE(32, 6)
 #undef GGNN_DG_CASE
     return fail(GGNN_E_UNSUPPORTED, "graph-resident dense forward: unsupported shape");
+}
+
+extern "C" int ggnn_dense_propagate_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
+                                        const float* edge_bias, const float* bg, const float* bc, float* out, int b, int v, int E,
+                                        int D, int steps, int fmt, ggnn_stream_t stream) {
+    return dense_propagate(h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, E, D, steps, fmt, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int ggnn_dense_propagate_save_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
+                                             const float* edge_bias, const float* bg, const float* bc, float* out, int b, int v, int E,
+                                             int D, int steps, int fmt, float* saved, size_t saved_bytes, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(b >= 0 && steps >= 1, "bad sizes b=%d steps=%d", b, steps);
+    if (!ggnn_dense_train_supported(v, E, D))
+        return fail(GGNN_E_UNSUPPORTED, "graph-resident dense training: split matrix path, v <= 32, E in {2,4,6,8}, hidden size 32/64/100 "
+                                        "(got v=%d E=%d D=%d)", v, E, D);
+    if (b == 0) return GGNN_OK;
+    GGNN_CHECK_ARG(saved && aligned16(saved), "saved: null or misaligned pointer");
+    GGNN_CHECK_ARG(saved_bytes >= ggnn_dense_train_saved_bytes(b, v, D, steps), "saved_bytes %zu < %zu", saved_bytes,
+                   ggnn_dense_train_saved_bytes(b, v, D, steps));
+    return dense_propagate(h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, E, D, steps, fmt, saved, (hipStream_t)stream);
 }

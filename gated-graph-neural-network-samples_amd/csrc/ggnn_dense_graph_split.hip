@@ -58,7 +58,11 @@ __global__ void dense_split_pack_kernel(const float* __restrict__ W, const float
 // pieces, three products, two operand planes) when the caller has PROVEN its range for the launch (dense_model.py / formats.py:
 // states tanh-bounded, |acts| <= v E (D max|W| S + max|b|), weights <= 255.875).  Accumulators then hold 2^8 x the sums
 // (SplitFmt<FMT>::acc_scale is applied where they are consumed).
-template <int D, int E, int NW, int FMT>
+// SAVE (training, ggnn_dense_propagate_save_f32): the launch also stores, per timestep and for the rows i < v, what the backward
+// launch (ggnn_dense_graph_bwd.hip) and the weight-gradient products read -- a.saved [6][steps][b v, D] (each tensor stacked over the
+// timesteps: a row operand of the weight-gradient products): the state h_t entering the step, the aggregated messages x_t, r, u, c,
+// r*h.  Stores only: the arithmetic, and `out`, are those of the plain launch bit for bit.
+template <int D, int E, int NW, int FMT, bool SAVE = false>
 __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGraphArgs a) {
     using C = StageCfg<D>;
     using SC = SplitCfg<D, FMT>;
@@ -110,6 +114,13 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGr
         *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
         *reinterpret_cast<u32x2*>(dst + NC2 * 4 * PSLOT) = u32x2{m0, m1};
         if constexpr (NP > 2) *reinterpret_cast<u32x2*>(dst + 2 * NC2 * 4 * PSLOT) = u32x2{l0, l1};
+    };
+
+    // (SAVE) this wave's four columns of row tile t -> tensor k of timestep `step`
+    auto save_tile = [&](int step, int k, int t, f32x4 val) {
+        const int i = t * 16 + li;
+        if (mm && i < v && col0 < D)
+            *reinterpret_cast<f32x4*>(a.saved + (((size_t)k * a.steps + step) * a.b * v + (size_t)g * v + i) * D + col0) = val;
     };
 
     for (int idx = tid; idx < E * 32 * 32; idx += NW * 64) {
@@ -202,6 +213,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGr
     for (int step = 0; step < a.steps; ++step) {
         const bool last = step + 1 == a.steps;
         GGNN_DGS_T(0)
+        if constexpr (SAVE) { save_tile(step, 0, 0, htile[0]); save_tile(step, 0, 1, htile[1]); }
 #define GGNN_DGS_STAGE(S, ACC, BLK, ZERO)                                                                  \
         {                                                                                                  \
             __builtin_amdgcn_sched_barrier(0);   /* (the look-ahead stays at ONE stage: 37 weight registers in flight) */ \
@@ -251,6 +263,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGr
             }
         }
         tile_to_planes(Xblk, 0, aa[0]); tile_to_planes(Xblk, 1, aa[1]);
+        if constexpr (SAVE) { save_tile(step, 1, 0, aa[0]); save_tile(step, 1, 1, aa[1]); }
         GGNN_DGS_T(3)
         __syncthreads();                                               // (2) acts complete, split
         GGNN_DGS_T(4)
@@ -265,6 +278,14 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGr
 #pragma unroll
             for (int e = 0; e < 4; ++e) { r4[e] = sigm(ar[t][e] * ASC + b_r[e]); u4[t][e] = sigm(au[t][e] * ASC + b_u[e]); }
             tile_to_planes(Rblk, t, r4 * htile[t]);                    // r * h tile
+            if constexpr (SAVE) {
+                // the saved r*h is a product of ITS OWN (r through an empty asm: not the expression above to the compiler): the operand's
+                // r*h stays single-use, so its split contracts to fma(r, h, -hi) exactly where the plain instantiation's does -- a
+                // shared product would feed the split the ROUNDED r*h and change the mid / lo pieces, i.e. the bits of `out`
+                f32x4 rs = r4;
+                asm volatile("" : "+v"(rs));
+                save_tile(step, 2, t, r4); save_tile(step, 3, t, u4[t]); save_tile(step, 5, t, rs * htile[t]);
+            }
         }
         GGNN_DGS_T(5)
         __syncthreads();                                               // (3) r*h complete, split
@@ -273,12 +294,14 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_split_kernel(DenseGr
         GGNN_DGS_T(7)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            f32x4 hn;
+            f32x4 hn, c4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float c = tanhf_(ac[t][e] * ASC + b_c[e]);
                 hn[e] = u4[t][e] * htile[t][e] + (1.0f - u4[t][e]) * c;
+                c4[e] = c;
             }
+            if constexpr (SAVE) save_tile(step, 4, t, c4);
             if (col0 >= D) hn = f32x4{0.f, 0.f, 0.f, 0.f};              // (the padding columns of the last tile stay zero operands)
             htile[t] = hn;
             if (last) {
@@ -349,21 +372,27 @@ int dense_split_pack_gru(const float* Wg, const float* Wc, int D, float* packed,
     return GGNN_OK;
 }
 
-template <int D, int E, int FMT>
+template <int D, int E, int FMT, bool SAVE>
 static int launch_split(const DenseGraphArgs& a, hipStream_t st) {
     constexpr int NW = 8;
     const size_t ldsb = split_lds_bytes(D, E, SplitFmt<FMT>::NP);
     static std::atomic<unsigned long long> lds_ok{0};
-    if (ldsb > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&ggnn_dense_graph_split_kernel<D, E, NW, FMT>, ldsb, lds_ok)));
-    hipLaunchKernelGGL((ggnn_dense_graph_split_kernel<D, E, NW, FMT>), dim3(a.b), dim3(NW * 64), ldsb, st, a);
+    if (ldsb > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&ggnn_dense_graph_split_kernel<D, E, NW, FMT, SAVE>, ldsb, lds_ok)));
+    hipLaunchKernelGGL((ggnn_dense_graph_split_kernel<D, E, NW, FMT, SAVE>), dim3(a.b), dim3(NW * 64), ldsb, st, a);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
 
-// a.eimg / a.gimg: the images of the format `fmt` (dense_split_images_offset into the split section of the packed buffers)
+template <int D, int E, int FMT>
+static int launch_split_fmt(const DenseGraphArgs& a, hipStream_t st) {
+    return a.saved ? launch_split<D, E, FMT, true>(a, st) : launch_split<D, E, FMT, false>(a, st);
+}
+
+// a.eimg / a.gimg: the images of the format `fmt` (dense_split_images_offset into the split section of the packed buffers);
+// a.saved != NULL: the saving instantiation (training)
 int dense_split_launch(const DenseGraphArgs& a, int E, int D, int fmt, hipStream_t st) {
     const bool f2 = gru_launch_fmt(fmt) == kSplitF16x2;
-#define GGNN_DGS_CASE(DD, EE) if (D == DD && E == EE) return f2 ? launch_split<DD, EE, kSplitF16x2>(a, st) : launch_split<DD, EE, kSplitBf16x3>(a, st);
+#define GGNN_DGS_CASE(DD, EE) if (D == DD && E == EE) return f2 ? launch_split_fmt<DD, EE, kSplitF16x2>(a, st) : launch_split_fmt<DD, EE, kSplitBf16x3>(a, st);
     GGNN_DGS_CASE(100, 4) GGNN_DGS_CASE(100, 2) GGNN_DGS_CASE(100, 6) GGNN_DGS_CASE(100, 8)
     GGNN_DGS_CASE(64, 4) GGNN_DGS_CASE(64, 8) GGNN_DGS_CASE(64, 2) GGNN_DGS_CASE(64, 6)
     GGNN_DGS_CASE(32, 4) GGNN_DGS_CASE(32, 8) GGNN_DGS_CASE(32, 2) GGNN_DGS_CASE(32, 6)

@@ -5,7 +5,8 @@ Per timestep (chem_tensorflow_dense.py:100-115):
     acts = sum_e A_e m_e          batched [v,v]x[v,D] from LDS                   (ggnn_dense_aggregate_f32)
     h    = GRU(acts, h)           one GRU shared by all timesteps (:101-102)     (ggnn_gru_f32)
 Inference / validation runs all timesteps in one graph-resident launch (ggnn_dense_propagate_f32).  Training runs the dense step as
-the sparse step it is on the b*v padded nodes (_compute_for_training: the hand-written backward of backward.PropagationStepFn).
+the sparse step it is on the b*v padded nodes (_compute_for_training: the hand-written backward of backward.PropagationStepFn), or,
+with params['graph_resident_training'], on the graph-resident forward and backward launches (backward.DensePropagateFn).
 With params['pack_on_device'] the batches are assembled on the GPU from the resident dataset (ggnn_dense_assemble_batch), training
 batches together with that sparse form.
 """
@@ -44,8 +45,8 @@ class DenseGGNNChemModel(ChemModel):
             'use_edge_bias': True,
             'edge_weight_dropout_keep_prob': 1
         })
-        # (params['pack_on_device'], default False, is read with .get: a key in this dict would break restoring the reference's
-        # checkpoints, whose params must match key for key, chem_tensorflow.py:336-340)
+        # (params['pack_on_device'] and params['graph_resident_training'], default False, are read with .get: a key in this dict would
+        # break restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340)
         return params
 
     def prepare_specific_graph_model(self) -> None:
@@ -167,7 +168,10 @@ class DenseGGNNChemModel(ChemModel):
         tensor is turned into per-type (src, dst) lists once per batch and every timestep runs through the same
         differentiable step as the sparse model (backward.PropagationStepFn: hand-written backward kernels).  Padded
         vertices are isolated nodes there -- their state still evolves through the GRU biases, as in the reference,
-        and is masked only at the readout (:126)."""
+        and is masked only at the readout (:126).
+        params['graph_resident_training'] (default False): where the graph-resident kernels exist for the batch (_graph_resident_step)
+        all timesteps run as ONE differentiable op instead -- one saving forward launch, one backward launch, the weight gradients
+        once per variable (backward.DensePropagateFn); every other batch takes the route above."""
         from .autograd import propagation_step
         ph = self.placeholders
         v = int(ph['num_vertices'])
@@ -175,6 +179,8 @@ class DenseGGNNChemModel(ChemModel):
         h0 = ph['initial_node_representation']
         b = h0.shape[0]
         A = ph['adjacency_matrix']                                      # [b, e, dst, src]
+        if self._graph_resident_step(v, h0, A):
+            return self._compute_graph_resident(v, h0, A)
         sparse_form = ph.get('_sparse_form')
         if sparse_form is None or sparse_form[0] is not A:
             nz = A.nonzero()                                            # rows (b, e, dst, src), lexicographic
@@ -197,6 +203,35 @@ class DenseGGNNChemModel(ChemModel):
                                  ew_mask=ew_mask)
             h = tf_dropout(h, keep_s, self.dropout_seed('state', i))
         return h.reshape(b, v, h_dim)
+
+    def _graph_resident_step(self, v: int, h0: torch.Tensor, A: torch.Tensor) -> bool:
+        """Whether this training batch takes the graph-resident route: asked for, on the GPU, kernels for the shape on the split matrix
+        path, no weight or state dropout (the dense defaults), and no per-launch timing (which wants the per-timestep launches)."""
+        ph = self.placeholders
+        return bool(self.params.get('graph_resident_training', False)) and h0.is_cuda and A.is_cuda and ops._timing is None \
+            and float(ph.get('edge_weight_dropout_keep_prob', 1.0)) >= 1.0 and float(ph.get('graph_state_keep_prob', 1.0)) >= 1.0 \
+            and formats.split_path() and ops.dense_train_supported(v, self.num_edge_types, self.params['hidden_size'])
+
+    def _compute_graph_resident(self, v: int, h0: torch.Tensor, A: torch.Tensor) -> torch.Tensor:
+        from .backward import DensePropagateFn
+        ph = self.placeholders
+        h_dim, T = self.params['hidden_size'], self.num_edge_types
+        b = h0.shape[0]
+        nin = None
+        if self.params['use_edge_bias']:                                # in-degrees per (vertex, type): the edge biases' gradient
+            sparse_form, cached = ph.get('_sparse_form'), ph.get('_dense_nin')
+            if sparse_form is not None and sparse_form[0] is A:
+                nin = sparse_form[2]
+            elif cached is not None and cached[0] is A:
+                nin = cached[1]
+            else:
+                nin = A.sum(dim=3).permute(0, 2, 1).reshape(b * v, T).to(torch.float32).contiguous()
+                ph['_dense_nin'] = (A, nin)
+        bias = self.weights['edge_biases'].reshape(T, h_dim) if self.params['use_edge_bias'] else None
+        cell = self.weights['node_gru']
+        return DensePropagateFn.apply(h0.reshape(b, v, h_dim).contiguous(), A.contiguous(), nin, self.weights['edge_weights'], bias,
+                                      cell.gates_kernel, cell.gates_bias, cell.candidate_kernel, cell.candidate_bias,
+                                      self.params['num_timesteps'], self.propagate_format(v))
 
     def gated_regression_with_loss(self, last_h, regression_gate, regression_transform, target_values, target_mask):
         """chem_tensorflow_dense.py:119-129 + chem_tensorflow.py:161-166 on the fused readout kernels: graph g owns the

@@ -681,6 +681,91 @@ def dense_propagate(h0: torch.Tensor, adjacency: torch.Tensor, edge_packed: torc
     return out
 
 
+def dense_train_supported(v: int, E: int, D: int) -> bool:
+    """Whether the graph-resident training route (dense_propagate_save / dense_propagate_bwd) exists for the shape: the split-form
+    forward's shapes on the split matrix path, where the backward kernel's LDS blocks fit."""
+    return bool(_lib.load().ggnn_dense_train_supported(int(v), int(E), int(D)))
+
+
+def dense_propagate_save(h0: torch.Tensor, adjacency: torch.Tensor, edge_packed: torch.Tensor, gru_packed: torch.Tensor,
+                         edge_biases: Optional[torch.Tensor], bg: torch.Tensor, bc: torch.Tensor, steps: int,
+                         fmt: int = GRU_FMT_EXACT):
+    """dense_propagate that also keeps what the backward needs (ggnn_dense_propagate_save_f32) -> (out [b,v,D], saved
+    [6, steps, b*v, D]: the entering state h_t, the aggregated messages x_t, r, u, c, r*h_t, each stacked over the timesteps).  `out` is
+    dense_propagate's bit for bit in the same format."""
+    lib = _lib.load()
+    _req(h0, torch.float32, "h0"); _req(adjacency, torch.float32, "adjacency")
+    if h0.dim() != 3 or adjacency.dim() != 4:
+        raise ValueError("h0 must be [b,v,D] and adjacency [b,e,v,v]")
+    b, v, D = h0.shape
+    E = adjacency.shape[1]
+    if adjacency.shape != (b, E, v, v):
+        raise ValueError("adjacency must be [b,e,v,v]")
+    for t, n, name in ((bg, 2 * D, "bg"), (bc, D, "bc")):
+        _req(t, torch.float32, name)
+        if t.numel() != n:
+            raise ValueError("%s must have %d elements" % (name, n))
+    if edge_biases is not None:
+        _req(edge_biases, torch.float32, "edge_biases")
+        if edge_biases.numel() != E * D:
+            raise ValueError("edge_biases must be [e,D]")
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    out = torch.empty_like(h0)
+    saved = torch.empty((6, steps, b * v, D), dtype=torch.float32, device=h0.device)
+    _launch("dense_propagate_save[steps=%d]" % steps, lambda: lib.ggnn_dense_propagate_save_f32(
+        _ptr(h0), _ptr(adjacency), _ptr(edge_packed), _ptr(gru_packed), _ptr(edge_biases), _ptr(bg), _ptr(bc), _ptr(out), b, v, E, D,
+        steps, int(fmt), _ptr(saved), saved.numel() * 4, _stream()))
+    return out, saved
+
+
+def dense_bwd_pack(W: torch.Tensor, Wg: torch.Tensor, Wc: torch.Tensor) -> torch.Tensor:
+    """The 6 + E transposed split images the graph-resident backward consumes (ggnn_dense_bwd_pack_f32); W [E,D,D], Wg [2D,2D],
+    Wc [2D,D].  PackedWeights.dense_bwd caches them per weight version."""
+    lib = _lib.load()
+    _req(W, torch.float32, "edge_weights"); _req(Wg, torch.float32, "Wg"); _req(Wc, torch.float32, "Wc")
+    if W.dim() != 3 or W.shape[1] != W.shape[2]:
+        raise ValueError("edge_weights must be [e,D,D]")
+    E, D = W.shape[0], W.shape[1]
+    if tuple(Wg.shape) != (2 * D, 2 * D) or tuple(Wc.shape) != (2 * D, D):
+        raise ValueError("Wg must be [2D,2D] and Wc [2D,D]")
+    nbytes = lib.ggnn_dense_bwd_packed_bytes(D, E)
+    if not nbytes:
+        raise ValueError("no graph-resident dense backward for hidden size %d" % D)
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=W.device)
+    check(lib.ggnn_dense_bwd_pack_f32(_ptr(W), _ptr(Wg), _ptr(Wc), E, D, _ptr(packed), _stream()))
+    return packed
+
+
+def dense_propagate_bwd(d_out: torch.Tensor, adjacency: torch.Tensor, bwd_packed: torch.Tensor, saved: torch.Tensor,
+                        need_d_h0: bool = True):
+    """The backward of dense_propagate_save in one launch (ggnn_dense_propagate_bwd_f32) -> (d_h0 [b,v,D] or None, dpc [steps,b*v,D],
+    dpg = [dpr|dpu] [steps,b*v,2D], dx [steps,b*v,D], dM [steps,b*v,E*D]): the gradient of the initial state and, stacked over the
+    timesteps, the operands of the weight-gradient products."""
+    lib = _lib.load()
+    _req(d_out, torch.float32, "d_out"); _req(adjacency, torch.float32, "adjacency"); _req(saved, torch.float32, "saved")
+    if d_out.dim() != 3 or adjacency.dim() != 4:
+        raise ValueError("d_out must be [b,v,D] and adjacency [b,e,v,v]")
+    b, v, D = d_out.shape
+    E = adjacency.shape[1]
+    if adjacency.shape != (b, E, v, v):
+        raise ValueError("adjacency must be [b,e,v,v]")
+    if saved.dim() != 4 or saved.shape[0] != 6 or saved.shape[2:] != (b * v, D):
+        raise ValueError("saved must be dense_propagate_save's [6, steps, b*v, D]")
+    steps = saved.shape[1]
+    dev = d_out.device
+    d_h0 = torch.empty_like(d_out) if need_d_h0 else None
+    dpc = torch.empty((steps, b * v, D), dtype=torch.float32, device=dev)
+    dpg = torch.empty((steps, b * v, 2 * D), dtype=torch.float32, device=dev)
+    dx = torch.empty((steps, b * v, D), dtype=torch.float32, device=dev)
+    dM = torch.empty((steps, b * v, E * D), dtype=torch.float32, device=dev)
+    _launch("dense_propagate_bwd[steps=%d]" % steps, lambda: lib.ggnn_dense_propagate_bwd_f32(
+        _ptr(d_out), _ptr(adjacency), _ptr(bwd_packed), _ptr(saved), b, v, E, D, steps, _ptr(d_h0), _ptr(dpc), _ptr(dpg), _ptr(dx),
+        _ptr(dM), _stream()))
+    return d_h0, dpc, dpg, dx, dM
+
+
 # ---- source-compacted message transform -----------------------------------------------------------------
 @dataclass
 class CompactSources:
@@ -965,6 +1050,16 @@ class PackedWeights:
             packed = torch.empty(lib.ggnn_dense_gru_packed_bytes(D) // 4, dtype=torch.float32, device=Wg.device)
             check(lib.ggnn_dense_gru_pack_f32(_ptr(Wg), _ptr(Wc), D, _ptr(packed), _stream()))
             hit = self._store(self._dense_gru, key, (Wg, Wc), packed)
+        return hit
+
+    def dense_bwd(self, W: torch.Tensor, Wg: torch.Tensor, Wc: torch.Tensor) -> torch.Tensor:
+        """The transposed split images of the graph-resident dense backward (dense_bwd_pack), once per weight version."""
+        if not hasattr(self, "_dense_bwd"):
+            self._dense_bwd = {}
+        key = self._key(W, Wg, Wc)
+        hit = self._lookup(self._dense_bwd, key, (W, Wg, Wc))
+        if hit is None:
+            hit = self._store(self._dense_bwd, key, (W, Wg, Wc), dense_bwd_pack(W, Wg, Wc))
         return hit
 
     def gru_bwd(self, Wg: torch.Tensor, Wc: torch.Tensor, nx: int, D: int) -> torch.Tensor:

@@ -404,6 +404,32 @@ int ggnn_dense_gru_pack_f32(const float* Wg, const float* Wc, int D, float* pack
 int ggnn_dense_propagate_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed, const float* edge_bias,
                              const float* bg, const float* bc, float* out, int b, int v, int E, int D, int steps, int fmt,
                              ggnn_stream_t stream);
+/* TRAINING on the graph-resident kernels (the backward TF autodiff derives from chem_tensorflow_dense.py:93-117 through
+ * compute_gradients, chem_tensorflow.py:184; the dense model shares ONE GRU and ONE edge-weight tensor across timesteps, :84-102).
+ *   ggnn_dense_train_supported(v, E, D): 1 where ggnn_dense_propagate_is_split(v, E, D) holds and the backward kernel's LDS blocks
+ *   fit (v <= 32, E in {2,4,6,8}, D in {32,64,100}, split matrix path); every entry below returns GGNN_E_UNSUPPORTED otherwise.
+ *   ggnn_dense_propagate_save_f32: ggnn_dense_propagate_f32 (same arguments, same `out` bit for bit) that also writes what the
+ *   backward reads into `saved` (16-byte aligned, saved_bytes >= ggnn_dense_train_saved_bytes(b, v, D, steps)):
+ *       saved [6][steps][b*v, D] f32 -- each tensor stacked over the timesteps, i.e. a [steps*b*v, D] row operand of the
+ *       weight-gradient products;  tensor k at timestep t: 0 = h_t (the state ENTERING the step; saved[0][0] = h0),
+ *       1 = x_t = sum_e A_e (h_t W_e + b_e) (:103-112), 2 = r, 3 = u, 4 = c, 5 = r*h_t of the GRU (:115).
+ *   ggnn_dense_bwd_pack_f32: the 6 + E transposed split images of Wg [2D,2D], Wc [2D,D], W [E,D,D] in the order the backward consumes
+ *   them (Wc[h]^T, Wg[x,r]^T, Wg[x,u]^T, Wc[x]^T, Wg[h,r]^T, Wg[h,u]^T, W_e^T); ggnn_dense_bwd_packed_bytes(D, E) bytes (0: no kernel).
+ *   ggnn_dense_propagate_bwd_f32: one workgroup per graph walks the timesteps in reverse, every product in the exact bf16x3 format,
+ *   no atomics (the same inputs give the same bits).  d_out [b,v,D] = dL/d out;  d_h0 [b,v,D] or NULL.  Per timestep, stacked
+ *   [steps, b*v, .] in caller-owned buffers, the operands of the weight-gradient products (ggnn_xty_f32 / ggnn_gemm_tn_f32):
+ *       dpc [.., D]  (dWc = [x | r*h]^T dpc),  dpg = [dpr | dpu] [.., 2D]  (dWg = [x | h]^T dpg),
+ *       dx [.., D]   (db_e = sum_rows nin_e * dx),  dM [.., E*D]  (dW_e = h^T dM_e;  dM_e[src] = sum_dst A_e[dst,src] dx[dst]).
+ *   b == 0 is a no-op for both launches. */
+int ggnn_dense_train_supported(int v, int E, int D);
+size_t ggnn_dense_train_saved_bytes(int b, int v, int D, int steps);
+int ggnn_dense_propagate_save_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
+                                  const float* edge_bias, const float* bg, const float* bc, float* out, int b, int v, int E, int D,
+                                  int steps, int fmt, float* saved, size_t saved_bytes, ggnn_stream_t stream);
+size_t ggnn_dense_bwd_packed_bytes(int D, int E);
+int ggnn_dense_bwd_pack_f32(const float* W, const float* Wg, const float* Wc, int E, int D, float* packed, ggnn_stream_t stream);
+int ggnn_dense_propagate_bwd_f32(const float* d_out, const float* A, const float* bwd_packed, const float* saved, int b, int v, int E,
+                                 int D, int steps, float* d_h0, float* dpc, float* dpg, float* dx, float* dM, ggnn_stream_t stream);
 int ggnn_dense_aggregate_f32(const float* A, const float* Hm, const float* bias, float* acts, int b, int v,
                              int e, int D, ggnn_stream_t stream);
 

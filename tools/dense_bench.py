@@ -10,6 +10,13 @@ training and validation), the dense model's default params (batch_size 256, hidd
                           the 8 TB/s roof
 Run from the repository root:  python tools/dense_bench.py [--graphs 50000]
 --leg pack: only device packing of `--iters` batches (for a kernel trace).
+--graph-resident: the epoch leg with params['graph_resident_training'] (the graph-resident forward and backward launches).
+--leg step: one training step of a 256-graph batch at v = 16 and v = 29 (D 100, 4 edge types, 4 timesteps) on today's per-timestep
+  route and on the graph-resident route, in ONE process with the routes alternating in interleaved rounds; device events around whole
+  steps that end in a synchronise; median / min / max per route -> one JSON line (and --out FILE).
+--leg trace: `--iters` graph-resident steps at v = 29 (for rocprofv3 --kernel-trace --stats, the program after `--`).
+--leg roof --kernel-stats FILE: the saving forward's and the backward launch's average time from that run's kernel-stats CSV against
+  their algorithmic bytes and flops (computed here from the shapes) -> the share of the bounding roof.
 """
 import argparse
 import json
@@ -77,8 +84,8 @@ def _assemble_bytes(feed, A_ann, T):
 
 def epoch_leg(a):
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
-    cfg = {"random_seed": 0}
-    out = {"metric": "dense GGNN training epoch, synthetic QM9", "graphs": ms.num_graphs, "nodes": int(ms.node_ptr[-1]), "D": 100,
+    cfg = {"random_seed": 0, "graph_resident_training": True} if a.graph_resident else {"random_seed": 0}
+    out = {"metric": "dense GGNN training epoch, synthetic QM9", "graph_resident_training": bool(a.graph_resident), "graphs": ms.num_graphs, "nodes": int(ms.node_ptr[-1]), "D": 100,
            "timesteps": 4, "batch_size": 256, "reference_dense_epoch": REFERENCE}
     for name, on_dev, threaded in (("host", False, "auto"), ("device", True, False), ("device_threaded", True, True)):
         model = _model(ms, cfg, on_dev, threaded)
@@ -113,14 +120,121 @@ def pack_leg(a):
     print(json.dumps({"metric": "dense device packing", "batches": n}))
 
 
+def _step_feed(model, ms, v, batch=256):
+    """A training feed of `batch` graphs with at most v vertices in a bucket of v (pack_dense_batch, as make_minibatch_iterator's)."""
+    ids = np.nonzero(ms.nodes_per_graph() <= v)[0][:batch]
+    assert len(ids) == batch, "not enough graphs of <= %d vertices" % v
+    db = ggnn_amd.data.pack_dense_batch(ms, ids, v, model.num_edge_types, model.params['hidden_size'], model.params['tie_fwd_bkwd'],
+                                        model.params['task_ids'])
+    feed = model.to_device_batch(db)
+    feed['graph_state_keep_prob'] = feed['edge_weight_dropout_keep_prob'] = 1.0
+    return feed
+
+
+def _timed_step(model, feed):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    model.train_batch(feed)
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def _step_models(ms):
+    cfg = {"random_seed": 0}
+    return {"per_timestep": _model(ms, cfg, False, False), "graph_resident": _model(ms, dict(cfg, graph_resident_training=True), False, False)}
+
+
+def step_leg(a):
+    ms = ggnn_amd.synthetic_qm9(max(a.graphs, 4000), mean_nodes=14, seed=0)
+    models = _step_models(ms)
+    out = {"metric": "dense GGNN training step, 256 graphs, D 100, 4 edge types, 4 timesteps", "unit": "ms per step (device events)",
+           "rounds": a.rounds, "steps_per_round": a.reps, "shapes": {}}
+    for v in (16, 29):
+        feeds = {k: _step_feed(m, ms, v) for k, m in models.items()}
+        for k, m in models.items():                                    # warm up every shape on every route
+            for _ in range(5):
+                _timed_step(m, feeds[k])
+        ms_ = {k: [] for k in models}
+        for r in range(a.rounds):                                      # interleaved rounds, the order alternating
+            for k in (list(models) if r % 2 == 0 else list(models)[::-1]):
+                ms_[k] += [_timed_step(models[k], feeds[k]) for _ in range(a.reps)]
+        res = {k: {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)} for k, t in ms_.items()}
+        res["speedup_median"] = round(res["per_timestep"]["median"] / res["graph_resident"]["median"], 2)
+        res["node_rows"] = 256 * v
+        out["shapes"]["v%d" % v] = res
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+def trace_leg(a):
+    ms = ggnn_amd.synthetic_qm9(4000, mean_nodes=14, seed=0)
+    model = _step_models(ms)["graph_resident"]
+    feed = _step_feed(model, ms, 29)
+    for _ in range(a.iters):
+        model.train_batch(feed)
+    torch.cuda.synchronize()
+    print(json.dumps({"metric": "graph-resident dense training steps", "steps": a.iters}))
+
+
+MATRIX_ROOF_BF16 = 2.5e15          # flop/s of v_mfma_f32_16x16x32_bf16 on the whole chip (csrc/ggnn_split.hpp)
+
+
+def roof_leg(a):
+    """Algorithmic traffic and work of the two launches at b 256, v 29, E 4, D 100, 4 timesteps.  A D x D product runs on 32-row
+    tiles as six bf16 MFMA products in the exact format (the backward, and a forward launched with fmt 3) or as three f16 ones (a
+    forward launched with fmt 2: the format is read from the traced instantiation's name), so the matrix-pipe time is 6 x or 3 x the
+    padded flops at the 16-bit rate; the adjacency products are f32 MFMAs and are left out.  Only the SAVING instantiation
+    <100, 4, 8, fmt, true> of the forward counts; a trace that holds it in both formats is refused."""
+    import csv
+    import re
+    b, v, E, D, steps = 256, 29, 4, 100, 4
+    rows = b * v
+    f = 4
+    w_bytes = (E * D * D + 4 * D * D + 2 * D * D) * f
+    fwd_bytes = (2 * rows * D + b * E * v * v + 6 * steps * rows * D) * f + w_bytes
+    bwd_bytes = (2 * rows * D + b * E * v * v + 4 * steps * rows * D + steps * rows * (4 + E) * D) * f + w_bytes
+    flops = 2.0 * b * steps * (6 + E) * v * D * D                       # algorithmic, either direction
+    padded = 2.0 * b * steps * (6 + E) * 32 * 112 * 112                # one product on 32-row tiles, 7 x 16 columns
+    pats = {"forward_save": re.compile(r"ggnn_dense_graph_split_kernel<\s*%d,\s*%d,\s*8,\s*([23]),\s*true\s*>" % (D, E)),
+            "backward": re.compile(r"ggnn_dense_graph_bwd_kernel<\s*%d,\s*%d,\s*8\s*>" % (D, E))}
+    found = {}
+    with open(a.kernel_stats) as fh:
+        for row in csv.DictReader(fh):
+            for key, pat in pats.items():
+                m = pat.search(row.get("Name", ""))
+                if m:
+                    assert key not in found, "the trace holds more than one instantiation of the %s launch" % key
+                    found[key] = (float(row["AverageNs"]) * 1e-9, int(row["Calls"]), int(m.group(1)) if m.groups() else 3)
+    out = {"shape": {"b": b, "v": v, "E": E, "D": D, "steps": steps}}
+    for key, nbytes in (("forward_save", fwd_bytes), ("backward", bwd_bytes)):
+        t, calls, fmt = found[key]
+        products = 6 if fmt == 3 else 3
+        hbm, mat = nbytes / HBM_ROOF / t, products * padded / MATRIX_ROOF_BF16 / t
+        out[key] = {"kernel_us": round(t * 1e6, 2), "calls": calls, "operand_format": "bf16x3" if fmt == 3 else "f16x2",
+                    "algorithmic_bytes": int(nbytes), "algorithmic_flops": int(flops), "hbm_roof_share": round(hbm, 3),
+                    "matrix_roof_share": round(mat, 3), "bounding_roof": "hbm" if hbm > mat else "16-bit matrix pipe"}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=50000)
     ap.add_argument("--iters", type=int, default=400)
-    ap.add_argument("--leg", choices=("epoch", "pack"), default="epoch")
+    ap.add_argument("--leg", choices=("epoch", "pack", "step", "trace", "roof"), default="epoch")
+    ap.add_argument("--graph-resident", action="store_true", help="epoch leg: params['graph_resident_training']")
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-stats", default=None)
     a = ap.parse_args()
+    if a.leg == "roof":
+        return roof_leg(a)
     assert torch.cuda.is_available(), "dense_bench needs a GPU"
-    (epoch_leg if a.leg == "epoch" else pack_leg)(a)
+    {"epoch": epoch_leg, "pack": pack_leg, "step": step_leg, "trace": trace_leg}[a.leg](a)
 
 
 if __name__ == "__main__":
