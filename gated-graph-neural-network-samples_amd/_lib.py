@@ -105,6 +105,16 @@ SYMBOLS = {
     "ggnn_dense_bwd_pack_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ggnn_dense_propagate_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    # edge-weight / edge-bias gradients of the dense model (chem_tensorflow_dense.py:103-112 through chem_tensorflow.py:184)
+    "ggnn_dense_edge_grad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ggnn_dense_edge_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_size_t, c_void_p]),
+    # the dense model's optimisation step as two native calls (chem_tensorflow_dense.py:93-117, chem_tensorflow.py:183-191)
+    "ggnn_dense_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ggnn_dense_train_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                             c_int, c_int, c_int, c_void_p, c_size_t, POINTER(c_int64), c_void_p]),
+    "ggnn_dense_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ggnn_assemble_batch_backward": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_int, POINTER(c_int64), POINTER(c_int64), c_void_p,
                                              c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64),
                                              POINTER(c_void_p), c_void_p]),

@@ -31,6 +31,10 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Number of CUs of the current device (cached per process; MI355X = 256).
 int num_cus();
 
+// `waiter` waits (on the device) for everything queued on `producer` so far: an event of the per-device pool of ggnn_train.hip is
+// recorded on `producer` and waited for on `waiter`.  A no-op when the two are the same stream.
+int stream_order_after(hipStream_t waiter, hipStream_t producer);
+
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): `done` is a per-kernel bitmask of the devices that have
 // it (the attribute is per device; one process may drive several).  Thread-safe; a lost race only repeats the call.
 template <class Kernel>

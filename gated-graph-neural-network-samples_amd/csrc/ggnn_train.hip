@@ -205,6 +205,10 @@ int plan_layers(int num_layers, const int32_t* layer_timesteps, const int32_t* r
 }
 
 }  // namespace
+
+// the same event pool for the other native launch sequences (ggnn_dense_train.hip)
+int stream_order_after(hipStream_t waiter, hipStream_t producer) { return order_after(waiter, producer); }
+
 }  // namespace ggnn
 
 using namespace ggnn;

@@ -6,7 +6,8 @@ Per timestep (chem_tensorflow_dense.py:100-115):
     h    = GRU(acts, h)           one GRU shared by all timesteps (:101-102)     (ggnn_gru_f32)
 Inference / validation runs all timesteps in one graph-resident launch (ggnn_dense_propagate_f32).  Training runs the dense step as
 the sparse step it is on the b*v padded nodes (_compute_for_training: the hand-written backward of backward.PropagationStepFn), or,
-with params['graph_resident_training'], on the graph-resident forward and backward launches (backward.DensePropagateFn).
+with params['graph_resident_training'], on the graph-resident forward and backward launches (backward.DensePropagateFn); with the
+value 'native' of that key the whole optimisation step is two native calls without torch.autograd (train_native.native_dense_train_step).
 With params['pack_on_device'] the batches are assembled on the GPU from the resident dataset (ggnn_dense_assemble_batch), training
 batches together with that sparse form.
 """
@@ -92,11 +93,14 @@ class DenseGGNNChemModel(ChemModel):
             c.gates_kernel.copy_(as_t(gru['Wg'])); c.gates_bias.copy_(as_t(gru['bg']))
             c.candidate_kernel.copy_(as_t(gru['Wc'])); c.candidate_bias.copy_(as_t(gru['bc']))
 
-    def propagate_format(self, v: int) -> int:
+    def propagate_format(self, v: int, tracked_weights: bool = False) -> int:
         """Operand format of the graph-resident dense forward for the fed batch (formats.py: the two-piece f16 format only where its
         range is PROVEN, the exact bf16x3 split otherwise).  The dense cell is the tanh GRU (chem_tensorflow_dense.py:88), so every
         state stays <= S = max(1, max|h0|); a vertex sums over at most v * E (source, type) pairs: |acts| <= v E (D max|W_e| S +
-        max|b_e|) (:103-112); the weights must lie within the x 2^8 packing's range.  Kept in self.last_format / last_format_bounds."""
+        max|b_e|) (:103-112); the weights must lie within the x 2^8 packing's range.  Kept in self.last_format / last_format_bounds.
+        tracked_weights (the native training step): the weights' maxima come from formats.TrainingWeightBounds -- measured every
+        REMEASURE_STEPS optimizer steps and bounded by Adam's step bound in between -- instead of one measurement per weight version,
+        so a steady-state step reads nothing back; the bounds and the decision are computed from them in the same way."""
         from . import formats
         pol = formats.policy()
         if not formats.split_path() or pol == "exact":
@@ -108,7 +112,12 @@ class DenseGGNNChemModel(ChemModel):
             ts = [self.weights['edge_weights'], cell.gates_kernel, cell.candidate_kernel]
             if self.params['use_edge_bias']:
                 ts.append(self.weights['edge_biases'])
-            mx = formats.weight_absmax(ts)
+            if tracked_weights:
+                if getattr(self, "_train_weight_bounds", None) is None:
+                    self._train_weight_bounds = formats.TrainingWeightBounds()
+                mx = self._train_weight_bounds.get(ts, self.optimizer)
+            else:
+                mx = formats.weight_absmax(ts)
             S = formats.state_bound(formats.h0_absmax(self.placeholders), 'tanh')
             # (|A| <= 1 for the reference's 0 / 1 adjacency; a weighted or multi-edge feed scales the sum: measured, cached per tensor,
             # unless the device packer declared it for this very tensor)
@@ -171,7 +180,9 @@ class DenseGGNNChemModel(ChemModel):
         and is masked only at the readout (:126).
         params['graph_resident_training'] (default False): where the graph-resident kernels exist for the batch (_graph_resident_step)
         all timesteps run as ONE differentiable op instead -- one saving forward launch, one backward launch, the weight gradients
-        once per variable (backward.DensePropagateFn); every other batch takes the route above."""
+        once per variable (backward.DensePropagateFn); every other batch takes the route above.  The value 'native' of the key asks
+        for train_native.native_dense_train_step, which train.train_step dispatches to before this function is reached; being truthy, it
+        sends a batch the native step cannot take through the graph-resident route here, and from there to the route above."""
         from .autograd import propagation_step
         ph = self.placeholders
         v = int(ph['num_vertices'])
@@ -204,34 +215,50 @@ class DenseGGNNChemModel(ChemModel):
             h = tf_dropout(h, keep_s, self.dropout_seed('state', i))
         return h.reshape(b, v, h_dim)
 
-    def _graph_resident_step(self, v: int, h0: torch.Tensor, A: torch.Tensor) -> bool:
+    def _graph_resident_step(self, v: int, h0: torch.Tensor, A: torch.Tensor, feed: Dict[str, Any] = None) -> bool:
         """Whether this training batch takes the graph-resident route: asked for, on the GPU, kernels for the shape on the split matrix
-        path, no weight or state dropout (the dense defaults), and no per-launch timing (which wants the per-timestep launches)."""
+        path, no weight or state dropout (the dense defaults), and no per-launch timing (which wants the per-timestep launches).
+        feed: a batch that is about to be fed (train_native.dense_eligible asks before model.feed): its keep-probs count, the
+        placeholders' where it brings none -- what the placeholders hold once it is fed."""
         ph = self.placeholders
+        keep = lambda k: float(feed[k] if feed is not None and k in feed else ph.get(k, 1.0))
         return bool(self.params.get('graph_resident_training', False)) and h0.is_cuda and A.is_cuda and ops._timing is None \
-            and float(ph.get('edge_weight_dropout_keep_prob', 1.0)) >= 1.0 and float(ph.get('graph_state_keep_prob', 1.0)) >= 1.0 \
+            and keep('edge_weight_dropout_keep_prob') >= 1.0 and keep('graph_state_keep_prob') >= 1.0 \
             and formats.split_path() and ops.dense_train_supported(v, self.num_edge_types, self.params['hidden_size'])
+
+    def _in_degrees(self, A: torch.Tensor, b: int, v: int) -> torch.Tensor:
+        """In-degrees per (vertex, type) [b*v, E] of the fed adjacency tensor: the operand of the edge biases' gradient.  The device
+        packer's ('_sparse_form'), else counted once per fed tensor ('_dense_nin')."""
+        ph = self.placeholders
+        sparse_form, cached = ph.get('_sparse_form'), ph.get('_dense_nin')
+        if sparse_form is not None and sparse_form[0] is A:
+            return sparse_form[2]
+        if cached is not None and cached[0] is A:
+            return cached[1]
+        nin = A.sum(dim=3).permute(0, 2, 1).reshape(b * v, self.num_edge_types).to(torch.float32).contiguous()
+        ph['_dense_nin'] = (A, nin)
+        return nin
 
     def _compute_graph_resident(self, v: int, h0: torch.Tensor, A: torch.Tensor) -> torch.Tensor:
         from .backward import DensePropagateFn
-        ph = self.placeholders
         h_dim, T = self.params['hidden_size'], self.num_edge_types
         b = h0.shape[0]
-        nin = None
-        if self.params['use_edge_bias']:                                # in-degrees per (vertex, type): the edge biases' gradient
-            sparse_form, cached = ph.get('_sparse_form'), ph.get('_dense_nin')
-            if sparse_form is not None and sparse_form[0] is A:
-                nin = sparse_form[2]
-            elif cached is not None and cached[0] is A:
-                nin = cached[1]
-            else:
-                nin = A.sum(dim=3).permute(0, 2, 1).reshape(b * v, T).to(torch.float32).contiguous()
-                ph['_dense_nin'] = (A, nin)
+        nin = self._in_degrees(A, b, v) if self.params['use_edge_bias'] else None
         bias = self.weights['edge_biases'].reshape(T, h_dim) if self.params['use_edge_bias'] else None
         cell = self.weights['node_gru']
         return DensePropagateFn.apply(h0.reshape(b, v, h_dim).contiguous(), A.contiguous(), nin, self.weights['edge_weights'], bias,
                                       cell.gates_kernel, cell.gates_bias, cell.candidate_kernel, cell.candidate_bias,
                                       self.params['num_timesteps'], self.propagate_format(v))
+
+    def _readout_rows(self, b: int, v: int, device):
+        """(graph of every row, first row of every graph) of the flattened [b*v, h] states, cached per (b, v, device)."""
+        key = (b, v, str(device))
+        cached = getattr(self, '_readout_index', None)
+        if cached is None or cached[0] != key:
+            gnl = torch.arange(b, dtype=torch.int32, device=device).repeat_interleave(v).contiguous()
+            gptr = (torch.arange(b + 1, dtype=torch.int32, device=device) * v).contiguous()
+            self._readout_index = cached = (key, gnl, gptr)
+        return cached[1], cached[2]
 
     def gated_regression_with_loss(self, last_h, regression_gate, regression_transform, target_values, target_mask):
         """chem_tensorflow_dense.py:119-129 + chem_tensorflow.py:161-166 on the fused readout kernels: graph g owns the
@@ -243,15 +270,9 @@ class DenseGGNNChemModel(ChemModel):
         if not last_h.is_cuda or h_dim > 256 or len(g["weights"]) != 1 or len(t["weights"]) != 1:
             return None
         b, v = last_h.shape[0], int(ph['num_vertices'])
-        key = (b, v, str(last_h.device))
-        cached = getattr(self, '_readout_index', None)
-        if cached is None or cached[0] != key:
-            gnl = torch.arange(b, dtype=torch.int32, device=last_h.device).repeat_interleave(v).contiguous()
-            gptr = (torch.arange(b + 1, dtype=torch.int32, device=last_h.device) * v).contiguous()
-            self._readout_index = cached = (key, gnl, gptr)
-        keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
+        gnl, gptr = self._readout_rows(b, v, last_h.device)
         out, num, ab, ms = readout_loss(last_h.reshape(-1, h_dim), ph['initial_node_representation'].reshape(-1, h_dim).contiguous(),
-                                        cached[1], cached[2], ph['node_mask'].reshape(-1).contiguous(), b,
+                                        gnl, gptr, ph['node_mask'].reshape(-1).contiguous(), b,
                                         regression_gate.dropped_weight(0), g["biases"][0], regression_transform.dropped_weight(0),
                                         t["biases"][0], target_values.contiguous(), target_mask.contiguous())
         self.output = out

@@ -766,6 +766,66 @@ def dense_propagate_bwd(d_out: torch.Tensor, adjacency: torch.Tensor, bwd_packed
     return d_h0, dpc, dpg, dx, dM
 
 
+def dense_edge_grad_supported(E: int, D: int) -> bool:
+    """The shapes ggnn_dense_edge_grad_f32 has kernels for (the graph-resident route's: hidden size 32 / 64 / 100, 2 / 4 / 6 / 8 edge
+    types)."""
+    return int(D) in (32, 64, 100) and int(E) in (2, 4, 6, 8)
+
+
+def dense_edge_grad(h: torch.Tensor, dM: torch.Tensor, nin: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None,
+                    dW: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None, accumulate: bool = False,
+                    ws: Optional[torch.Tensor] = None):
+    """Edge-weight and edge-bias gradients of the dense model in one deterministic product (ggnn_dense_edge_grad_f32):
+    dW [E,D,D] = per edge type h^T dM_e, db [E,D] = nin^T dx with row n of the stack using nin[n % rows_per_step].
+    h, dx [N,D] and dM [N,E*D] are dense_propagate_save's saved[0] and dense_propagate_bwd's dx / dM stacked over the timesteps
+    (N = steps*b*v); nin [b*v, E] the in-degrees of ONE timestep, or None for a model without edge biases (then dx and db are unused).
+    dW / db given: the results go there (contiguous float32, E*D*D / E*D elements), ADDED to their contents with accumulate.
+    ws: a uint8 workspace of at least ggnn_dense_edge_grad_workspace_bytes(N, E, D) bytes (allocated when None).  -> (dW, db or None)."""
+    lib = _lib.load()
+    tensors = [("h", h), ("dM", dM)] + ([("nin", nin), ("dx", dx)] if nin is not None else []) + \
+              [(n, t) for n, t in (("dW", dW), ("db", db if nin is not None else None)) if t is not None]
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 CUDA/HIP tensor (the GGNN hot path has no CPU implementation)" % name)
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+    if h.dim() != 2 or dM.dim() != 2 or dM.shape[0] != h.shape[0] or h.shape[1] == 0 or dM.shape[1] % h.shape[1]:
+        raise ValueError("h must be [N,D] and dM [N,E*D]")
+    N, D = h.shape
+    E = dM.shape[1] // D
+    if not dense_edge_grad_supported(E, D):
+        raise ValueError("dense_edge_grad: hidden size 32 / 64 / 100 and 2 / 4 / 6 / 8 edge types (got E=%d D=%d)" % (E, D))
+    rows_per_step = 1
+    if nin is not None:
+        if nin.dim() != 2 or nin.shape[1] != E or nin.shape[0] < 1 or tuple(dx.shape) != (N, D):
+            raise ValueError("nin must be [rows_per_step, E] with at least one row and dx [N, D]")
+        rows_per_step = nin.shape[0]
+    dev = h.device
+    if dW is None:
+        if accumulate:
+            raise ValueError("accumulate needs the destination dW")
+        dW = torch.empty((E, D, D), dtype=torch.float32, device=dev)
+    elif dW.numel() != E * D * D:
+        raise ValueError("dW must have E*D*D elements")
+    if nin is None:
+        db = None
+    elif db is None:
+        if accumulate:
+            raise ValueError("accumulate needs the destination db")
+        db = torch.empty((E, D), dtype=torch.float32, device=dev)
+    elif db.numel() != E * D:
+        raise ValueError("db must have E*D elements")
+    ws_bytes = lib.ggnn_dense_edge_grad_workspace_bytes(N, E, D)
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < ws_bytes or ws.data_ptr() % 16:
+        raise ValueError("ws must be a contiguous, 16-byte aligned uint8 CUDA/HIP tensor of at least %d bytes" % ws_bytes)
+    _launch("dense_edge_grad[E=%d,D=%d]" % (E, D), lambda: lib.ggnn_dense_edge_grad_f32(
+        _ptr(h), _ptr(dM), _ptr(nin), _ptr(dx), N, rows_per_step, E, D, _ptr(dW), _ptr(db), 1 if accumulate else 0, _ptr(ws), ws.numel(),
+        _stream()))
+    return dW, db
+
+
 # ---- source-compacted message transform -----------------------------------------------------------------
 @dataclass
 class CompactSources:

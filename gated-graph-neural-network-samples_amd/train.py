@@ -217,7 +217,10 @@ def train_step(model, batch_data) -> torch.Tensor:
     if train_native.eligible(model, batch_data):
         # the default model: forward, backward and weight-gradient products as native launch sequences (csrc/ggnn_train.hip)
         return train_native.native_train_step(model, batch_data)
-    variables = list(model.trainable_variables.values())
+    if train_native.dense_eligible(model, batch_data):
+        # the dense model with graph_resident_training == 'native': the same on the graph-resident kernels (csrc/ggnn_dense_train.hip)
+        return train_native.native_dense_train_step(model, batch_data)
+    variables =list(model.trainable_variables.values())
     for v in variables:
         v.requires_grad_(True)
         v.grad = None

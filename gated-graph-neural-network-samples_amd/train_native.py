@@ -9,6 +9,10 @@ else keeps the autograd path (backward.PropagationStepFn, variants.py), which is
 
 Per step the host makes two C calls for the propagation, one ops call per task for the readout forward and one for its backward, a
 handful of launches for the weight images and masks, and the optimizer's two launches: ~1 ms of host time instead of ~4.4 ms.
+
+The dense model (chem_tensorflow_dense.py:93-117) has the same step on csrc/ggnn_dense_train.hip (ggnn_dense_train_forward_f32 /
+ggnn_dense_train_backward_f32) when its config asks for it with graph_resident_training = 'native': dense_eligible /
+native_dense_train_step at the end of this file.
 """
 from __future__ import annotations
 
@@ -256,6 +260,163 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         # ---- (all-reduce) -> per-variable clip -> Adam ---------------------------------------------------------------------
         if sharded:
             dist.all_reduce_sum_(opt._flat["g"])
+        opt.mark_all_active()
+        opt.clip_and_apply(p['clamp_gradient_norm'])
+    return loss.detach()
+
+
+# ---- the dense model (chem_tensorflow_dense.py:93-117) on ggnn_dense_train_forward_f32 / ggnn_dense_train_backward_f32 ---------------
+def dense_model_eligible(model) -> bool:
+    """The part of `dense_eligible` that depends on the model only: a dense model that asks for the native step
+    (params['graph_resident_training'] == 'native'; True keeps the autograd graph-resident route) on a GPU, the fused optimizer over
+    exactly the trainable variables, nothing frozen, one-layer readout MLPs, no active data-parallel context."""
+    p = getattr(model, "params", None)
+    if p is None or p.get('graph_resident_training') != 'native' or not hasattr(model, "_graph_resident_step"):
+        return False
+    if not torch.cuda.is_available() or torch.device(model.device).type != 'cuda' or not backward.USE_NATIVE_STEP or not p['use_graph']:
+        return False
+    if not ops.dense_edge_grad_supported(model.num_edge_types, p['hidden_size']) or int(p['num_timesteps']) < 1:
+        return False
+    dist = getattr(model, "dist", None)
+    if dist is not None and dist.active:
+        return False
+    opt = model.optimizer
+    variables = list(model.trainable_variables.values())
+    if not (opt.fused and len(opt.vars) == len(variables) and all(a is b for a, b in zip(opt.vars, variables))):
+        return False
+    have = {v.data_ptr() for v in variables}
+    if any(v.data_ptr() not in have for v in model.named_variables().values()):        # (--freeze-graph-model)
+        return False
+    for task_id in p['task_ids']:
+        for kind in ('regression_gate_task%i', 'regression_transform_task%i'):
+            if len(model.weights[kind % task_id].params["weights"]) != 1:
+                return False
+    return True
+
+
+def dense_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """True when this step of a dense model can run on the native sequences: dense_model_eligible, no per-launch timing, and a batch
+    the graph-resident route takes (DenseGGNNChemModel._graph_resident_step: kernels for the shape, no dropout on the propagation)."""
+    if ops._timing is not None or not dense_model_eligible(model):
+        return False
+    h0, A, v = batch_data.get('initial_node_representation'), batch_data.get('adjacency_matrix'), batch_data.get('num_vertices')
+    if h0 is None or A is None or v is None or h0.dim() != 3 or A.dim() != 4 or h0.shape[0] == 0:
+        return False
+    D, E = model.params['hidden_size'], model.num_edge_types
+    if h0.dtype != torch.float32 or A.dtype != torch.float32 or tuple(h0.shape[1:]) != (int(v), D) \
+            or tuple(A.shape) != (h0.shape[0], E, int(v), int(v)):
+        return False
+    return model._graph_resident_step(int(v), h0, A, feed=batch_data)
+
+
+class _DenseWorkspace:
+    """One growing device buffer per model: the saved tensors and temporaries of a step (ggnn_dense_train_workspace_bytes)."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None
+
+    def get(self, nbytes: int, device) -> torch.Tensor:
+        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
+            self.buf = torch.empty(int(nbytes * 1.05) + 256, dtype=torch.uint8, device=device)
+        return self.buf
+
+
+def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    """native_train_step for the dense model: two C calls for the propagation and every graph-model gradient, the readout + loss
+    per task between them, clip + Adam.  No torch.autograd, and in a steady state no read-back."""
+    from .autograd import _PACKED
+    lib = _lib.load()
+    p = model.params
+    opt = model.optimizer
+    model.feed(batch_data)
+    ph = model.placeholders
+    v = int(ph['num_vertices'])
+    D, E, steps = p['hidden_size'], model.num_edge_types, int(p['num_timesteps'])
+    h0 = ph['initial_node_representation']
+    b = h0.shape[0]
+    A_fed = ph['adjacency_matrix']
+    st = torch.cuda.current_stream()
+    side = backward.side_stream(h0.device)
+    dev = h0.device
+
+    with torch.no_grad():
+        # ---- operand format of the forward (proven bounds, formats.py; the weights' maxima tracked across optimizer steps) ----
+        fmt = model.propagate_format(v, tracked_weights=True)
+        # ---- this step's weight images, once per weight version ----
+        W = model.weights['edge_weights']
+        cell = model.weights['node_gru']
+        has_bias = bool(p['use_edge_bias'])
+        bias = model.weights['edge_biases'].reshape(E, D) if has_bias else None
+        edge_packed = _PACKED.dense_edge(W)
+        gru_packed = _PACKED.dense_gru(cell.gates_kernel, cell.candidate_kernel, D)
+        bwd_packed = _PACKED.dense_bwd(W, cell.gates_kernel, cell.candidate_kernel)
+        nin = model._in_degrees(A_fed, b, v) if has_bias else None
+        h0 = h0.reshape(b, v, D).contiguous()
+        A = A_fed.contiguous()
+
+        # ---- forward ------------------------------------------------------------------------------------------------------
+        if getattr(model, "_native_ws", None) is None:
+            model._native_ws = _DenseWorkspace()
+        ws = model._native_ws.get(lib.ggnn_dense_train_workspace_bytes(b, v, E, D, steps), dev)
+        final_off = ctypes.c_int64(0)
+        ops._launch("dense_train_forward[steps=%d]" % steps, lambda: lib.ggnn_dense_train_forward_f32(
+            h0.data_ptr(), A.data_ptr(), edge_packed.data_ptr(), gru_packed.data_ptr(), ops._ptr(bias), cell.gates_bias.data_ptr(),
+            cell.candidate_bias.data_ptr(), b, v, E, D, steps, int(fmt), ws.data_ptr(), ws.numel(), ctypes.byref(final_off),
+            st.cuda_stream))
+        off = int(final_off.value)
+        final = ws[off:off + b * v * D * 4].view(torch.float32).view(b * v, D)
+        model.ops['final_node_representations'] = final.view(b, v, D)
+
+        # ---- gated regression on the real vertices + masked loss per task (chem_tensorflow_dense.py:119-129, chem_tensorflow.py:158-170)
+        h0_rows = h0.view(b * v, D)
+        gnl, gptr = model._readout_rows(b, v, dev)
+        node_mask = ph['node_mask'].reshape(-1).contiguous()
+        saved, losses = [], []
+        for internal_id, task_id in enumerate(p['task_ids']):
+            gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
+            gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
+            target = ph['target_values'][internal_id, :].contiguous()
+            mask = ph['target_mask'][internal_id, :].contiguous()
+            out, ngate, nval, stats = ops.readout_loss_fwd(final, h0_rows, gnl, gptr, node_mask, b, gW, gate.params["biases"][0].reshape(-1),
+                                                           tW, tr.params["biases"][0].reshape(-1), target, mask)
+            saved.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
+            num, ab, ms = stats[0], stats[1], stats[2]
+            den = ms + SMALL_NUMBER
+            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
+            model.ops['accuracy_task%i' % task_id] = ab / den
+            model.ops['loss_numerator_task%i' % task_id] = num
+            model.ops['abs_error_sum_task%i' % task_id] = ab
+            model.ops['loss_denominator_task%i' % task_id] = ms
+            losses.append(num / den * ratio)
+            model.output = out
+        model.ops['losses'] = losses
+        loss = torch.stack(losses).sum()
+        model.ops['loss'] = loss
+        dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
+
+        # ---- backward -----------------------------------------------------------------------------------------------------
+        opt._flat["g"].zero_()
+        gviews = opt.sink_targets()
+        d_final = None
+        for internal_id, task_id in enumerate(p['task_ids']):
+            gate, tr, gW, tW, ngate, nval, out, target, mask = saved[internal_id]
+            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
+            d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=dev)]).contiguous()
+            dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
+                   gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
+            d_final = ops.readout_loss_bwd(final, h0_rows, gnl, node_mask, b, gW, tW, ngate, nval, out, target, mask, None, d_stats,
+                                           d_last_h=d_final, grad_out=dst)[0]
+            keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
+            if keep < 1.0:                                                              # utils.py:68: the masks of the forward
+                ops.dropout(dst[0], keep, gate.dropout_seed(0), out=dst[0])
+                ops.dropout(dst[2], keep, tr.dropout_seed(0), out=dst[2])
+        gv = lambda t: gviews[t.data_ptr()].data_ptr()
+        ops._launch("dense_train_backward[steps=%d]" % steps, lambda: lib.ggnn_dense_train_backward_f32(
+            d_final.data_ptr(), A.data_ptr(), ops._ptr(nin), bwd_packed.data_ptr(), b, v, E, D, steps, gv(W),
+            gv(model.weights['edge_biases']) if has_bias else None, gv(cell.gates_kernel), gv(cell.gates_bias),
+            gv(cell.candidate_kernel), gv(cell.candidate_bias), ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
+
+        # ---- per-variable clip -> Adam --------------------------------------------------------------------------------------
         opt.mark_all_active()
         opt.clip_and_apply(p['clamp_gradient_norm'])
     return loss.detach()

@@ -430,6 +430,37 @@ size_t ggnn_dense_bwd_packed_bytes(int D, int E);
 int ggnn_dense_bwd_pack_f32(const float* W, const float* Wg, const float* Wc, int E, int D, float* packed, ggnn_stream_t stream);
 int ggnn_dense_propagate_bwd_f32(const float* d_out, const float* A, const float* bwd_packed, const float* saved, int b, int v, int E,
                                  int D, int steps, float* d_h0, float* dpc, float* dpg, float* dx, float* dM, ggnn_stream_t stream);
+/* Edge-weight and edge-bias gradients of the dense model on the backward launch's stacked operands (TF autodiff of
+ * chem_tensorflow_dense.py:103-112, chem_tensorflow.py:184), one product launch + one reduce launch, deterministic (fixed-order
+ * sums, no atomics), f32 MFMA:
+ *     dW[e][k][n] = sum_rows h[row][k] * dM[row][e*D + n]   -> dW [E, D, D], the variable's layout
+ *     db[e][n]    = sum_rows nin[row % rows_per_step][e] * dx[row][n]   -> db [E, D]
+ *   h, dx [N, D] (saved[0] and dx of ggnn_dense_propagate_bwd_f32), dM [N, E*D], N = steps*b*v;  nin [rows_per_step, E] the
+ *   in-degrees of one timestep (rows_per_step = b*v), NULL = no edge biases (db, dx unused).  accumulate != 0: the results are ADDED
+ *   to the destinations' contents.  D in {32, 64, 100}, E in {2, 4, 6, 8} (GGNN_E_UNSUPPORTED else);  N == 0 writes zeros, or
+ *   nothing under accumulate.  Pointers 16-byte aligned;  ws: ggnn_dense_edge_grad_workspace_bytes(N, E, D) bytes, its contents
+ *   before the call do not matter. */
+size_t ggnn_dense_edge_grad_workspace_bytes(int N, int E, int D);
+int ggnn_dense_edge_grad_f32(const float* h, const float* dM, const float* nin, const float* dx, int N, int rows_per_step, int E, int D,
+                             float* dW, float* db, int accumulate, void* ws, size_t ws_bytes, ggnn_stream_t stream);
+/* The dense model's optimisation step as two native launch sequences (chem_tensorflow.py:183-191 over
+ * chem_tensorflow_dense.py:93-117), the dense twin of ggnn_sparse_train_*: one caller-provided workspace (256-byte aligned,
+ * ggnn_dense_train_workspace_bytes(b, v, E, D, steps) bytes, the same one for both calls of a step), nothing allocated, nothing
+ * synchronised.  Both refuse what ggnn_dense_train_supported(v, E, D) refuses (GGNN_E_UNSUPPORTED); b == 0 is a no-op.
+ *   forward: ggnn_dense_propagate_save_f32 into the workspace; *final_off = byte offset of the final states [b*v, D] in it.
+ *   backward: d_final [b*v, D] = dL/d final states.  ggnn_dense_propagate_bwd_f32 (no gradient of h0), then ADDED into the caller's
+ *   (zeroed) gradient buffers: g_Wc [2D,D], g_bc [D] += [x | r*h]^T dpc and g_Wg [2D,2D], g_bg [2D] += [x | h]^T dpg with their ones
+ *   rows on side_stream (NULL: the main stream), g_W [E,D,D], g_b [E,D] by ggnn_dense_edge_grad_f32 (nin [b*v, E] and g_b both NULL
+ *   without edge biases).  Returns with `stream` waiting for the side stream's last product.
+ * A binding's step: forward -> ggnn_readout_loss_fwd_f32 per task -> zero the gradient buffers -> ggnn_readout_loss_bwd_f32 per
+ * task (d_final) -> backward -> ggnn_clip_adam_f32. */
+size_t ggnn_dense_train_workspace_bytes(int b, int v, int E, int D, int steps);
+int ggnn_dense_train_forward_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,
+                                 const float* edge_bias, const float* bg, const float* bc, int b, int v, int E, int D, int steps, int fmt,
+                                 void* ws, size_t ws_bytes, int64_t* final_off, ggnn_stream_t stream);
+int ggnn_dense_train_backward_f32(const float* d_final, const float* A, const float* nin, const float* bwd_packed, int b, int v, int E,
+                                  int D, int steps, float* g_W, float* g_b, float* g_Wg, float* g_bg, float* g_Wc, float* g_bc,
+                                  void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
 int ggnn_dense_aggregate_f32(const float* A, const float* Hm, const float* bias, float* acts, int b, int v,
                              int e, int D, ggnn_stream_t stream);
 

@@ -10,11 +10,16 @@ training and validation), the dense model's default params (batch_size 256, hidd
                           the 8 TB/s roof
 Run from the repository root:  python tools/dense_bench.py [--graphs 50000]
 --leg pack: only device packing of `--iters` batches (for a kernel trace).
---graph-resident: the epoch leg with params['graph_resident_training'] (the graph-resident forward and backward launches).
---leg step: one training step of a 256-graph batch at v = 16 and v = 29 (D 100, 4 edge types, 4 timesteps) on today's per-timestep
-  route and on the graph-resident route, in ONE process with the routes alternating in interleaved rounds; device events around whole
-  steps that end in a synchronise; median / min / max per route -> one JSON line (and --out FILE).
---leg trace: `--iters` graph-resident steps at v = 29 (for rocprofv3 --kernel-trace --stats, the program after `--`).
+--graph-resident [native]: the epoch leg with params['graph_resident_training'] True (the graph-resident forward and backward
+  launches under torch.autograd) or 'native' (the native step, train_native.native_dense_train_step).
+--leg step: one training step of a 256-graph batch at v = 16 and v = 29 (D 100, 4 edge types, 4 timesteps) on the per-timestep
+  route, on the graph-resident route and on the native step, in ONE process with the routes alternating in interleaved rounds; device
+  events around whole steps that end in a synchronise; median / min / max per route and the median of every round, plus the host time
+  to enqueue a step (as tools/host_profile.py measures it) -> one JSON line (and --out FILE).
+--leg trace: `--iters` graph-resident steps at v = 29 (for rocprofv3 --kernel-trace --stats, the program after `--`); with
+  --graph-resident native the native step's.
+--leg edge-grad: ggnn_dense_edge_grad_f32 against what it replaces on the same operands (two ggnn_gemm_tn_f32 calls and the permute
+  copy) at N = 29 696 and N = 16 384 rows (D 100, 4 edge types): HIP events, warm-up, interleaved rounds in alternating order.
 --leg roof --kernel-stats FILE: the saving forward's and the backward launch's average time from that run's kernel-stats CSV against
   their algorithmic bytes and flops (computed here from the shapes) -> the share of the bounding roof.
 """
@@ -84,8 +89,8 @@ def _assemble_bytes(feed, A_ann, T):
 
 def epoch_leg(a):
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
-    cfg = {"random_seed": 0, "graph_resident_training": True} if a.graph_resident else {"random_seed": 0}
-    out = {"metric": "dense GGNN training epoch, synthetic QM9", "graph_resident_training": bool(a.graph_resident), "graphs": ms.num_graphs, "nodes": int(ms.node_ptr[-1]), "D": 100,
+    cfg = {"random_seed": 0, "graph_resident_training": a.graph_resident} if a.graph_resident else {"random_seed": 0}
+    out = {"metric": "dense GGNN training epoch, synthetic QM9", "graph_resident_training": a.graph_resident, "graphs": ms.num_graphs, "nodes": int(ms.node_ptr[-1]), "D": 100,
            "timesteps": 4, "batch_size": 256, "reference_dense_epoch": REFERENCE}
     for name, on_dev, threaded in (("host", False, "auto"), ("device", True, False), ("device_threaded", True, True)):
         model = _model(ms, cfg, on_dev, threaded)
@@ -142,7 +147,19 @@ def _timed_step(model, feed):
 
 def _step_models(ms):
     cfg = {"random_seed": 0}
-    return {"per_timestep": _model(ms, cfg, False, False), "graph_resident": _model(ms, dict(cfg, graph_resident_training=True), False, False)}
+    return {"per_timestep": _model(ms, cfg, False, False), "graph_resident": _model(ms, dict(cfg, graph_resident_training=True), False, False),
+            "native": _model(ms, dict(cfg, graph_resident_training="native"), False, False)}
+
+
+def _enqueue_ms(model, feed, n=30):
+    """Host time to enqueue a step (tools/host_profile.py): n steps back to back, the clock stopped before the device is drained."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        model.train_batch(feed)
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    return (t1 - t0) / n * 1e3
 
 
 def step_leg(a):
@@ -156,11 +173,17 @@ def step_leg(a):
             for _ in range(5):
                 _timed_step(m, feeds[k])
         ms_ = {k: [] for k in models}
+        per_round = {k: [] for k in models}
         for r in range(a.rounds):                                      # interleaved rounds, the order alternating
             for k in (list(models) if r % 2 == 0 else list(models)[::-1]):
-                ms_[k] += [_timed_step(models[k], feeds[k]) for _ in range(a.reps)]
-        res = {k: {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)} for k, t in ms_.items()}
+                t = [_timed_step(models[k], feeds[k]) for _ in range(a.reps)]
+                ms_[k] += t
+                per_round[k].append(round(float(np.median(t)), 4))
+        res = {k: {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4),
+                   "round_medians": per_round[k], "host_enqueue_ms": round(_enqueue_ms(models[k], feeds[k]), 4)} for k, t in ms_.items()}
         res["speedup_median"] = round(res["per_timestep"]["median"] / res["graph_resident"]["median"], 2)
+        res["native_speedup_median"] = round(res["graph_resident"]["median"] / res["native"]["median"], 2)
+        res["native_below_graph_resident_in_every_round"] = all(n < g for n, g in zip(per_round["native"], per_round["graph_resident"]))
         res["node_rows"] = 256 * v
         out["shapes"]["v%d" % v] = res
     line = json.dumps(out)
@@ -172,12 +195,71 @@ def step_leg(a):
 
 def trace_leg(a):
     ms = ggnn_amd.synthetic_qm9(4000, mean_nodes=14, seed=0)
-    model = _step_models(ms)["graph_resident"]
+    route = "native" if a.graph_resident == "native" else "graph_resident"
+    model = _model(ms, {"random_seed": 0, "graph_resident_training": "native" if route == "native" else True}, False, False)
     feed = _step_feed(model, ms, 29)
     for _ in range(a.iters):
         model.train_batch(feed)
     torch.cuda.synchronize()
-    print(json.dumps({"metric": "graph-resident dense training steps", "steps": a.iters}))
+    print(json.dumps({"metric": "%s dense training steps" % route.replace("_", "-"), "steps": a.iters}))
+
+
+MATRIX_ROOF_F32 = 157e12           # flop/s of v_mfma_f32_16x16x4_f32 on the whole chip
+
+
+def edge_grad_leg(a):
+    """ggnn_dense_edge_grad_f32 against the two ggnn_gemm_tn_f32 calls + permute copy it replaces, on the same operands."""
+    ops = ggnn_amd.ops
+    E, D = 4, 100
+    out = {"metric": "dense edge-weight + edge-bias gradients, E 4, D 100", "unit": "us per call group (device events)",
+           "rounds": a.rounds, "calls_per_round": a.reps, "shapes": {}}
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    for N, rps in ((4 * 256 * 29, 256 * 29), (4 * 256 * 16, 256 * 16)):
+        h = torch.rand((N, D), generator=gen).cuda() * 2 - 1
+        dM, dx = torch.randn((N, E * D), generator=gen).cuda(), torch.randn((N, D), generator=gen).cuda()
+        nin = torch.randint(0, 4, (rps, E), generator=gen).float().cuda()
+        ws = torch.empty(ggnn_amd._lib.load().ggnn_dense_edge_grad_workspace_bytes(N, E, D), dtype=torch.uint8, device="cuda")
+        dW, db = torch.empty((E, D, D), device="cuda"), torch.empty((E, D), device="cuda")
+        nin_rows = nin.repeat(N // rps, 1)                           # (the autograd route's copy is made outside the timed region)
+
+        def new():
+            ops.dense_edge_grad(h, dM, nin, dx, dW=dW, db=db, ws=ws)
+
+        def replaced():                                              # backward.DensePropagateFn's edge products
+            ops.gemm_tn(h, dM).view(D, E, D).permute(1, 0, 2).contiguous()
+            ops.gemm_tn(nin_rows, dx)
+
+        def timed(fn):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.reps):
+                fn()
+            e.record()
+            torch.cuda.synchronize()
+            return s.elapsed_time(e) * 1e3 / a.reps
+
+        arms = {"dense_edge_grad": new, "gemm_tn_x2_permute": replaced}
+        for fn in arms.values():
+            timed(fn)
+        rounds = {k: [] for k in arms}
+        for r in range(a.rounds):
+            for k in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+                rounds[k].append(round(timed(arms[k]), 2))
+        nbytes = 4 * (N * D * (2 + E) + rps * E + E * D * D + E * D)
+        flops = 2.0 * N * D * (E * D + E)
+        med = float(np.median(rounds["dense_edge_grad"]))
+        out["shapes"]["N%d" % N] = {
+            "round_us": rounds, "median_us": {k: round(float(np.median(t)), 2) for k, t in rounds.items()},
+            "lower_in_every_round": all(x < y for x, y in zip(rounds["dense_edge_grad"], rounds["gemm_tn_x2_permute"])),
+            "operand_bytes": nbytes, "flops": int(flops), "hbm_roof_us": round(nbytes / HBM_ROOF * 1e6, 2),
+            "f32_mfma_roof_us": round(flops / MATRIX_ROOF_F32 * 1e6, 2),
+            "share_of_f32_mfma_roof": round(flops / MATRIX_ROOF_F32 * 1e6 / med, 3),
+            "note": "events around back-to-back calls on one stream: launch gaps and the reduce launch are inside the figure"}
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
 
 
 MATRIX_ROOF_BF16 = 2.5e15          # flop/s of v_mfma_f32_16x16x32_bf16 on the whole chip (csrc/ggnn_split.hpp)
@@ -224,8 +306,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=50000)
     ap.add_argument("--iters", type=int, default=400)
-    ap.add_argument("--leg", choices=("epoch", "pack", "step", "trace", "roof"), default="epoch")
-    ap.add_argument("--graph-resident", action="store_true", help="epoch leg: params['graph_resident_training']")
+    ap.add_argument("--leg", choices=("epoch", "pack", "step", "trace", "roof", "edge-grad"), default="epoch")
+    ap.add_argument("--graph-resident", nargs="?", const=True, default=False, choices=(True, "native"),
+                    help="epoch / trace leg: params['graph_resident_training'] (no value: True; 'native': the native step)")
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
@@ -234,7 +317,7 @@ def main():
     if a.leg == "roof":
         return roof_leg(a)
     assert torch.cuda.is_available(), "dense_bench needs a GPU"
-    {"epoch": epoch_leg, "pack": pack_leg, "step": step_leg, "trace": trace_leg}[a.leg](a)
+    {"epoch": epoch_leg, "pack": pack_leg, "step": step_leg, "trace": trace_leg, "edge-grad": edge_grad_leg}[a.leg](a)
 
 
 if __name__ == "__main__":
