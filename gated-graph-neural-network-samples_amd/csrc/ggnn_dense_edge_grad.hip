@@ -21,6 +21,7 @@
 // The reduce launch adds the S partials of every output: 64 outputs x 4 quarter-ranges of the splits per workgroup, each quarter
 // summed in order, the quarters as (q0 + q1) + (q2 + q3); `accumulate` adds the destination's contents last (one f32 add).
 #include "ggnn_common.h"
+#include "ggnn_dense_graph.hpp"
 
 namespace ggnn {
 namespace {
@@ -302,12 +303,9 @@ extern "C" int ggnn_dense_edge_grad_f32(const float* h, const float* dM, const f
     if (ws_bytes < need) return fail(GGNN_E_WORKSPACE, "dense edge gradients: workspace too small: %zu < %zu", ws_bytes, need);
     EgArgs a{h, dM, nin, dx, static_cast<float*>(ws), N, nin ? rows_per_step : 1, E, 0, 0};
     edge_grad_splits(N, E, &a.rows_per_split, &a.S);
-    int rc;
-    switch (D) {
-        case 100: rc = nin ? launch_edge_grad<100, true>(a, st) : launch_edge_grad<100, false>(a, st); break;
-        case 64: rc = nin ? launch_edge_grad<64, true>(a, st) : launch_edge_grad<64, false>(a, st); break;
-        default: rc = nin ? launch_edge_grad<32, true>(a, st) : launch_edge_grad<32, false>(a, st); break;
-    }
+    const int rc = dense_for_D(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        return nin ? launch_edge_grad<DD, true>(a, st) : launch_edge_grad<DD, false>(a, st); });
     if (rc) return rc;
     // without edge biases the partials' [E][D] tails are never written and never read: the reduce covers the [E][D][D] heads only
     const int nout = (int)(nw + nb);

@@ -17,9 +17,9 @@
 //     term is nin_e[i] b_e (the row sums of A_e, formed once).
 //   * GRU (TF-1.3 GRUCell, :115): r, u = sigmoid([acts|h] Wg + bg), c = tanh([acts | r*h] Wc + bc), h' = u h + (1-u) c; the r*h tile of
 //     a wave is r times chunk w of its h fragment (output tile nt == activation chunk nt, as in the fused GRU).
-#include "ggnn_stage.hpp"
+// What this kernel shares with the split forward and the backward (LDS layout DenseF32Lds, prologue, aggregation, stage macro) is in
+// ggnn_dense_graph.hpp; its register-fragment load_w / mma_pair are its own.
 #include "ggnn_dense_graph.hpp"
-#include "ggnn_split.hpp"
 
 namespace ggnn {
 
@@ -35,19 +35,15 @@ __global__ void dense_gru_pack_kernel(const float* __restrict__ Wg, const float*
 template <int D, int E, int NW>
 __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArgs a) {
     using C = StageCfg<D>;
+    using L = DenseF32Lds<D, E>;
     constexpr int NT = C::NT, NC = C::NC, NR = C::NR;
-    constexpr int MP = C::BN + 4;                                      // row pitch of the LDS blocks (floats)
+    constexpr int MP = L::T::MP;                                       // row pitch of the LDS blocks (floats)
     constexpr int NS = E + 6;                                          // stages per timestep
-    constexpr int AP = 33;                                             // pitch of an adjacency row in LDS (16 rows x one column: 16 banks)
     static_assert(NT <= NW && NS % 2 == 0, "one column tile per wave; the two weight slots alternate with a fixed phase per timestep");
-    extern __shared__ __attribute__((aligned(16))) float lds[];        // Mbuf [E][32][MP] | Xbuf, Rbuf, Hbuf [32][MP] | Abuf [E][32][AP] | ...
-    float* Mbuf = lds;
-    float* Xbuf = lds + (size_t)E * 32 * MP;                           // exchange blocks: acts, r*h, the new state -- one each, so that a
-    float* Rbuf = Xbuf + (size_t)32 * MP;                              // block is rewritten a whole timestep after it was last read and
-    float* Hbuf = Rbuf + (size_t)32 * MP;                              // "everyone has read it" needs no barrier of its own
-    float* Abuf = Hbuf + (size_t)32 * MP;                              // the graph's adjacency rows: read once, used by every timestep
-    float* Nbuf = Abuf + (size_t)E * 32 * AP;                          // [E][32] incoming edges per type (row sums of A_e)
-    float* Bbuf = Nbuf + E * 32;                                       // [E][BN] edge biases, zero-padded
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* Mbuf = lds + L::M;                                          // [E][32][MP] the transformed states
+    float* Xbuf = lds + L::X, * Rbuf = lds + L::R, * Hbuf = lds + L::H;   // exchange blocks: acts, r*h, the new state
+    float* Abuf = lds + L::A, * Nbuf = lds + L::N, * Bbuf = lds + L::B;   // adjacency rows, in-degrees per type, edge biases
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
@@ -56,9 +52,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
     const bool mm = wave < NT;                                         // this wave owns a column tile
     const int tile = mm ? wave : 0;
 
-    auto image = [&](int s) -> const float* {                          // stage s of a timestep
-        return s < E ? a.eimg + (size_t)s * C::IMG : a.gimg + (size_t)(s - E) * C::IMG;
-    };
+    auto image = [&](int s) { return dense_stage_image<E, C::IMG>(a, s); };
     // fragment (rows t*16 + li, k = 16c + 4kq ..) of a [32][MP] LDS block
     auto frag_from_lds = [&](Frag<D>& f, const float* blk, int t) {
         const float* rowp = blk + (size_t)(t * 16 + li) * MP + 4 * kq;
@@ -67,25 +61,12 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
 #pragma unroll
         for (int q = 0; q < NR; ++q) f.r[q] = rowp[16 * NC + 4 * q - 4 * kq + kq];
     };
-    // accumulator tile (lane (li,kq): row t*16+li, columns 16*tile + 4kq ..) -> LDS block
-    auto tile_to_lds = [&](float* blk, int t, f32x4 val) {
-        *reinterpret_cast<f32x4*>(blk + (size_t)(t * 16 + li) * MP + 16 * tile + 4 * kq) = val;
-    };
+    auto to_lds = [&](float* blk, int t, f32x4 val) { tile_to_lds<D>(blk, t, val, li, kq, tile); };
 
-    for (int idx = tid; idx < E * 32 * 32; idx += NW * 64) {
-        const int j = idx & 31, i = (idx >> 5) & 31, e = idx >> 10;
-        Abuf[(e * 32 + i) * AP + j] = (i < a.v && j < a.v) ? a.A[(((size_t)blockIdx.x * E + e) * a.v + i) * a.v + j] : 0.f;
-    }
-    for (int idx = tid; idx < E * C::BN; idx += NW * 64) {
-        const int e = idx / C::BN, n = idx - e * C::BN;
-        Bbuf[idx] = (a.ebias && n < D) ? a.ebias[(size_t)e * D + n] : 0.f;
-    }
+    dense_load_adjacency<E, NW>(Abuf, a.A, v, tid);
+    dense_load_edge_bias<D, E, NW>(Bbuf, a.ebias, tid);
     __syncthreads();
-    if (tid < E * 32) {
-        float sum = 0.f;
-        for (int j = 0; j < 32; ++j) sum += Abuf[tid * AP + j];
-        Nbuf[tid] = sum;
-    }
+    dense_in_degrees<E>(Nbuf, Abuf, tid);
     Frag<D> hf[2], xf[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -98,13 +79,9 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
             for (int q = 0; q < (NR > 0 ? NR : 1); ++q) hf[t].r[q] = 0.f;
         }
     }
-    // this lane's four columns of the gate / candidate biases
     const int col0 = 16 * tile + 4 * kq;
-    f32x4 b_r = {0.f, 0.f, 0.f, 0.f}, b_u = b_r, b_c = b_r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if (col0 + e < D) { b_r[e] = a.bg[col0 + e]; b_u[e] = a.bg[D + col0 + e]; b_c[e] = a.bc[col0 + e]; }
-    }
+    f32x4 b_r, b_u, b_c;
+    dense_gate_bias<D>(b_r, b_u, b_c, a.bg, a.bc, col0);
 
     // this wave's column tile of a stage image, straight from L2: ONE per-lane byte offset for every image (scalar base + 32-bit
     // offset + immediate; per-load 64-bit lane addresses get hoisted for all ten images of a timestep and spill)
@@ -143,71 +120,38 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
     TileWeights<D> tw[2];
     if (mm) load_w(tw[0], image(0));
 
-#define GGNN_DG_T(K) if (a.tdbg && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 6) && step < 8) \
-        a.tdbg[(step * 2 + (wave ? 1 : 0)) * 8 + (K)] = __builtin_amdgcn_s_memtime();
     for (int step = 0; step < a.steps; ++step) {
         const bool last = step + 1 == a.steps;
-        GGNN_DG_T(0)
-        // one stage: request the next stage's weight slice, multiply both row tiles by this stage's
-#define GGNN_DG_STAGE(S, ACC, FR, ZERO)                                                                    \
-        {                                                                                                  \
-            __builtin_amdgcn_sched_barrier(0);   /* (keeps the look-ahead at ONE stage: 25 weight registers in flight, not 250) */ \
-            if (mm && !(last && (S) + 1 == NS)) load_w(tw[((S) + 1) & 1], image(((S) + 1) % NS));                         \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (mm) mma_pair(std::integral_constant<bool, ZERO>{}, ACC, FR, tw[(S) & 1]);                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-        }
+        GGNN_DENSE_STAMP(step, 0)
         // ---- E transform stages: M_e = h W_e, column tile `tile`, into LDS ------------------------------------------------------
         f32x4 acc[2];
 #define GGNN_DG_XFORM(S)                                                                                   \
         if constexpr ((S) < E) {                                                                           \
-            GGNN_DG_STAGE(S, acc, hf, true)                                                                \
-            if (mm) { tile_to_lds(Mbuf + (size_t)(S) * 32 * MP, 0, acc[0]); tile_to_lds(Mbuf + (size_t)(S) * 32 * MP, 1, acc[1]); } \
+            GGNN_DENSE_STAGE(S, acc, hf, true)                                                                \
+            if (mm) { to_lds(Mbuf + (size_t)(S) * 32 * MP, 0, acc[0]); to_lds(Mbuf + (size_t)(S) * 32 * MP, 1, acc[1]); } \
         }
         GGNN_DG_XFORM(0) GGNN_DG_XFORM(1) GGNN_DG_XFORM(2) GGNN_DG_XFORM(3) GGNN_DG_XFORM(4) GGNN_DG_XFORM(5) GGNN_DG_XFORM(6) GGNN_DG_XFORM(7)
 #undef GGNN_DG_XFORM
-        GGNN_DG_T(1)
+        GGNN_DENSE_STAMP(step, 1)
         __syncthreads();                                               // (1) every M_e is complete
-        GGNN_DG_T(2)
-        // ---- aggregation on the matrix pipe: acts^T tile = sum_e M_e^T[columns of this tile][src] . A_e^T[src][dst], K = 32 source
-        //      vertices = 8 MFMAs per (edge type, row tile); the bias term sum_j A_e[i,j] b_e = nin_e[i] b_e in the epilogue.  (A
-        //      lane-per-column walk over the non-zeros of each adjacency row -- the form of ggnn_dense_aggregate_f32 -- is a chain of
-        //      dependent LDS reads: 9.3k clocks per timestep against 2.5k here.)
+        GGNN_DENSE_STAMP(step, 2)
+        // ---- aggregation on the matrix pipe (GGNN_DENSE_AGGREGATE) -----------------------------------------------------------------
         f32x4 aa[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         if (mm) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const float* mcol = Mbuf + (size_t)e * 32 * MP + 16 * tile + li;          // M_e[.][column li of this tile]
-                const float* arow0 = Abuf + (e * 32 + li) * AP + kq;                       // A_e[row li][.]
-                const float* arow1 = arow0 + 16 * AP;
-#pragma unroll
-                for (int s4 = 0; s4 < 8; ++s4) {
-                    const float wv = mcol[(size_t)(4 * s4 + kq) * MP];
-                    aa[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, arow0[4 * s4], aa[0], 0, 0, 0);
-                    aa[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, arow1[4 * s4], aa[1], 0, 0, 0);
-                }
-            }
-            if (a.ebias) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const f32x4 be = *reinterpret_cast<const f32x4*>(Bbuf + e * C::BN + 16 * tile + 4 * kq);
-                    aa[0] += Nbuf[e * 32 + li] * be;
-                    aa[1] += Nbuf[e * 32 + 16 + li] * be;
-                }
-            }
-            tile_to_lds(Xbuf, 0, aa[0]); tile_to_lds(Xbuf, 1, aa[1]);
+            GGNN_DENSE_AGGREGATE(aa)
+            to_lds(Xbuf, 0, aa[0]); to_lds(Xbuf, 1, aa[1]);
         }
-        GGNN_DG_T(3)
+        GGNN_DENSE_STAMP(step, 3)
         __syncthreads();                                               // (2) acts complete
         frag_from_lds(xf[0], Xbuf, 0); frag_from_lds(xf[1], Xbuf, 1);
-        GGNN_DG_T(4)
+        GGNN_DENSE_STAMP(step, 4)
         // ---- gates --------------------------------------------------------------------------------------------------------------
         f32x4 ar[2], au[2], ac[2];
-        GGNN_DG_STAGE(E + 0, ar, xf, true)
-        GGNN_DG_STAGE(E + 1, ar, hf, false)
-        GGNN_DG_STAGE(E + 2, au, xf, true)
-        GGNN_DG_STAGE(E + 3, au, hf, false)
-        GGNN_DG_STAGE(E + 4, ac, xf, true)                             // candidate, acts part (acts are still in xf)
+        GGNN_DENSE_STAGE(E + 0, ar, xf, true)
+        GGNN_DENSE_STAGE(E + 1, ar, hf, false)
+        GGNN_DENSE_STAGE(E + 2, au, xf, true)
+        GGNN_DENSE_STAGE(E + 3, au, hf, false)
+        GGNN_DENSE_STAGE(E + 4, ac, xf, true)                             // candidate, acts part (acts are still in xf)
         f32x4 htile[2], u4[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -222,13 +166,13 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
             for (int e = 0; e < 4; ++e) { r4[e] = sigmoid_f(ar[t][e] + b_r[e]); u4[t][e] = sigmoid_f(au[t][e] + b_u[e]); }
             ar[t] = r4 * hv;                                           // r * h tile
         }
-        GGNN_DG_T(5)
-        if (mm) { tile_to_lds(Rbuf, 0, ar[0]); tile_to_lds(Rbuf, 1, ar[1]); }
+        GGNN_DENSE_STAMP(step, 5)
+        if (mm) { to_lds(Rbuf, 0, ar[0]); to_lds(Rbuf, 1, ar[1]); }
         __syncthreads();                                               // (3) r*h complete
         frag_from_lds(xf[0], Rbuf, 0); frag_from_lds(xf[1], Rbuf, 1);
-        GGNN_DG_T(6)
-        GGNN_DG_STAGE(E + 5, ac, xf, false)                            // candidate, r*h part
-        GGNN_DG_T(7)
+        GGNN_DENSE_STAMP(step, 6)
+        GGNN_DENSE_STAGE(E + 5, ac, xf, false)                            // candidate, r*h part
+        GGNN_DENSE_STAMP(step, 7)
         f32x4 hn[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -247,24 +191,11 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_kernel(DenseGraphArg
                 }
             }
         } else {
-            if (mm) { tile_to_lds(Hbuf, 0, hn[0]); tile_to_lds(Hbuf, 1, hn[1]); }
+            if (mm) { to_lds(Hbuf, 0, hn[0]); to_lds(Hbuf, 1, hn[1]); }
             __syncthreads();                                           // (4) new state complete
             frag_from_lds(hf[0], Hbuf, 0); frag_from_lds(hf[1], Hbuf, 1);
         }
-#undef GGNN_DG_STAGE
     }
-}
-
-template <int D, int E>
-static int launch_dense_graph(const DenseGraphArgs& a, hipStream_t st) {
-    using C = StageCfg<D>;
-    constexpr int NW = 8;
-    const size_t ldsb = ((size_t)(E + 3) * 32 * (C::BN + 4) + (size_t)E * 32 * 33 + (size_t)E * 32 + (size_t)E * C::BN) * sizeof(float);
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (ldsb > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&ggnn_dense_graph_kernel<D, E, NW>, ldsb, lds_ok)));
-    hipLaunchKernelGGL((ggnn_dense_graph_kernel<D, E, NW>), dim3(a.b), dim3(NW * 64), ldsb, st, a);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
 }
 
 }  // namespace ggnn
@@ -272,10 +203,8 @@ static int launch_dense_graph(const DenseGraphArgs& a, hipStream_t st) {
 using namespace ggnn;
 
 extern "C" int ggnn_dense_propagate_supported(int v, int E, int D) {
-    if (!(v >= 1 && v <= 32 && (E == 2 || E == 4 || E == 6 || E == 8) && (D == 100 || D == 64 || D == 32))) return 0;
-    const int bn = (D + 15) / 16 * 16;
-    const size_t ldsb = ((size_t)(E + 3) * 32 * (bn + 4) + (size_t)E * 32 * 33 + (size_t)E * 32 + (size_t)E * bn) * sizeof(float);   // M_e, exchange block, adjacency rows, in-degrees, biases
-    return ldsb <= (size_t)160 * 1024;
+    return dense_shape_ok(v, E, D) && dense_dispatch(D, E, [](auto d, auto e) {
+        return DenseF32Lds<decltype(d)::value, decltype(e)::value>::BYTES <= kDenseLdsLimit; });
 }
 
 // The E edge-weight stage images of the graph-resident kernel: always the f32 stage image (this kernel reads its weights as f32
@@ -287,57 +216,41 @@ __global__ void dense_edge_pack_kernel(const float* __restrict__ W, float* __res
                         gridDim.x * blockDim.x);
 }
 
-static size_t dense_edge_f32_bytes(int D, int T) {
-    switch (D) {
-        case 100: return (size_t)T * StageCfg<100>::IMG * sizeof(float);
-        case 64: return (size_t)T * StageCfg<64>::IMG * sizeof(float);
-        case 32: return (size_t)T * StageCfg<32>::IMG * sizeof(float);
-        default: return 0;
-    }
+// bytes of T f32 stage images (0: no kernel for the hidden size)
+static size_t dense_f32_images_bytes(int D, int T) {
+    return dense_for_D(D, [&](auto d) { return (size_t)T * StageCfg<decltype(d)::value>::IMG * sizeof(float); });
 }
 // (the packed buffers hold the f32 stage images FOLLOWED by the split ones: which kernel runs is decided per launch -- matrix
 // path of the process, and whether the split kernel's LDS blocks fit the launch's number of edge types)
 extern "C" size_t ggnn_dense_edge_packed_bytes(int D, int T) {
-    if (T <= 0 || !dense_edge_f32_bytes(D, T)) return 0;
-    return dense_edge_f32_bytes(D, T) + dense_split_edge_bytes(D, T);
+    if (T <= 0 || !dense_f32_images_bytes(D, T)) return 0;
+    return dense_f32_images_bytes(D, T) + dense_split_edge_bytes(D, T);
 }
 
 extern "C" int ggnn_dense_edge_pack_f32(const float* W, int T, int D, float* packed, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(W && packed && aligned16(packed) && T > 0 && T <= 64, "null or misaligned pointer, or T = %d outside 1..64", T);
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 100: hipLaunchKernelGGL((dense_edge_pack_kernel<100>), dim3(8, T), dim3(256), 0, st, W, packed); break;
-        case 64: hipLaunchKernelGGL((dense_edge_pack_kernel<64>), dim3(8, T), dim3(256), 0, st, W, packed); break;
-        case 32: hipLaunchKernelGGL((dense_edge_pack_kernel<32>), dim3(8, T), dim3(256), 0, st, W, packed); break;
-        default: return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense kernel for hidden size %d", D);
-    }
+    if (!dense_f32_images_bytes(D, T)) return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense kernel for hidden size %d", D);
+    dense_for_D(D, [&](auto d) {
+        hipLaunchKernelGGL((dense_edge_pack_kernel<decltype(d)::value>), dim3(8, T), dim3(256), 0, st, W, packed);
+        return 0; });
     GGNN_CHECK_HIP(hipGetLastError());
-    return dense_split_pack_edge(W, T, D, packed + dense_edge_f32_bytes(D, T) / sizeof(float), st);
+    return dense_split_pack_edge(W, T, D, packed + dense_f32_images_bytes(D, T) / sizeof(float), st);
 }
 
-static size_t dense_gru_f32_bytes(int D) {
-    switch (D) {
-        case 100: return (size_t)6 * StageCfg<100>::IMG * sizeof(float);
-        case 64: return (size_t)6 * StageCfg<64>::IMG * sizeof(float);
-        case 32: return (size_t)6 * StageCfg<32>::IMG * sizeof(float);
-        default: return 0;
-    }
-}
 extern "C" size_t ggnn_dense_gru_packed_bytes(int D) {
-    return dense_gru_f32_bytes(D) ? dense_gru_f32_bytes(D) + dense_split_gru_bytes(D) : 0;
+    return dense_f32_images_bytes(D, 6) ? dense_f32_images_bytes(D, 6) + dense_split_gru_bytes(D) : 0;
 }
 
 extern "C" int ggnn_dense_gru_pack_f32(const float* Wg, const float* Wc, int D, float* packed, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(Wg && Wc && packed && aligned16(packed), "null or misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 100: hipLaunchKernelGGL((dense_gru_pack_kernel<100>), dim3(8, 6), dim3(256), 0, st, Wg, Wc, packed); break;
-        case 64: hipLaunchKernelGGL((dense_gru_pack_kernel<64>), dim3(8, 6), dim3(256), 0, st, Wg, Wc, packed); break;
-        case 32: hipLaunchKernelGGL((dense_gru_pack_kernel<32>), dim3(8, 6), dim3(256), 0, st, Wg, Wc, packed); break;
-        default: return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense kernel for hidden size %d", D);
-    }
+    if (!dense_f32_images_bytes(D, 6)) return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense kernel for hidden size %d", D);
+    dense_for_D(D, [&](auto d) {
+        hipLaunchKernelGGL((dense_gru_pack_kernel<decltype(d)::value>), dim3(8, 6), dim3(256), 0, st, Wg, Wc, packed);
+        return 0; });
     GGNN_CHECK_HIP(hipGetLastError());
-    return dense_split_pack_gru(Wg, Wc, D, packed + dense_gru_f32_bytes(D) / sizeof(float), st);
+    return dense_split_pack_gru(Wg, Wc, D, packed + dense_f32_images_bytes(D, 6) / sizeof(float), st);
 }
 
 // split form (bf16 pipe, ggnn_dense_graph_split.hip) where it exists and fits; GGNN_DENSE_SPLIT=0 keeps the f32-MFMA kernel
@@ -367,20 +280,16 @@ static int dense_propagate(const float* h0, const float* A, const float* edge_pa
     GGNN_CHECK_ARG(h0 && A && edge_packed && gru_packed && bg && bc && out, "null pointer");
     GGNN_CHECK_ARG(aligned16(h0) && aligned16(out) && aligned16(edge_packed) && aligned16(gru_packed) && (!edge_bias || aligned16(edge_bias)),
                    "pointers must be 16-byte aligned");
-    DenseGraphArgs a{h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, steps, nullptr, saved};
-    { const char* e = getenv("GGNN_DG_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
+    const DenseGraphArgs a{h0, A, edge_packed, gru_packed, edge_bias, bg, bc, out, b, v, steps, stamp_ptr_from_env("GGNN_DG_TPTR"), saved};
     if (ggnn_dense_propagate_is_split(v, E, D)) {
         DenseGraphArgs s = a;
-        s.eimg = edge_packed + (dense_edge_f32_bytes(D, E) + dense_split_images_offset(D, E, fmt)) / sizeof(float);
-        s.gimg = gru_packed + (dense_gru_f32_bytes(D) + dense_split_images_offset(D, 6, fmt)) / sizeof(float);
+        s.eimg = edge_packed + (dense_f32_images_bytes(D, E) + dense_split_images_offset(D, E, fmt)) / sizeof(float);
+        s.gimg = gru_packed + (dense_f32_images_bytes(D, 6) + dense_split_images_offset(D, 6, fmt)) / sizeof(float);
         return dense_split_launch(s, E, D, fmt, st);
     }
-#define GGNN_DG_CASE(DD, EE) if (D == DD && E == EE) return launch_dense_graph<DD, EE>(a, st);
-    GGNN_DG_CASE(100, 4) GGNN_DG_CASE(100, 8) GGNN_DG_CASE(100, 2) GGNN_DG_CASE(100, 6)
-    GGNN_DG_CASE(64, 4) GGNN_DG_CASE(64, 8) GGNN_DG_CASE(64, 2) GGNN_DG_CASE(64, 6)
-    GGNN_DG_CASE(32, 4) GGNN_DG_CASE(32, 8) GGNN_DG_CASE(32, 2) GGNN_DG_CASE(32, 6)
-#undef GGNN_DG_CASE
-    return fail(GGNN_E_UNSUPPORTED, "graph-resident dense forward: unsupported shape");
+    return dense_dispatch(D, E, [&](auto d, auto e) {
+        constexpr int DD = decltype(d)::value, EE = decltype(e)::value;
+        return dense_graph_launch<&ggnn_dense_graph_kernel<DD, EE, kDenseWaves>>(DenseF32Lds<DD, EE>::BYTES, a, st); });
 }
 
 extern "C" int ggnn_dense_propagate_f32(const float* h0, const float* A, const float* edge_packed, const float* gru_packed,

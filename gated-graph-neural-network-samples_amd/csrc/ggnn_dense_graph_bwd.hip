@@ -2,7 +2,8 @@
 // it through compute_gradients, chem_tensorflow.py:184).  One workgroup per graph walks the timesteps in REVERSE on what the saving
 // forward launch wrote (ggnn_dense_graph_split.hip, SAVE): the gradient of the graph's states never leaves its CU.
 //
-// The structure is the forward's: operands in LDS already split into MFMA planes ([plane][32-chunk][lane group][row][8 x bf16], written
+// The structure is the forward's, on the shared tile layer of ggnn_dense_graph.hpp (TileW, load_w, tile_to_planes, mma_pair; the LDS
+// layout is DenseBwdLds): operands in LDS already split into MFMA planes ([plane][32-chunk][lane group][row][8 x bf16], written
 // by the wave that produced them), one column tile per wave, each wave's weight slice of a stage -- its column tile of a TRANSPOSED
 // split image (dense_bwd_pack_kernel) -- fetched from L2 one stage ahead.  Every product runs in the exact bf16x3 format, as every
 // backward product of this library does.  Per timestep t = steps-1 .. 0, with g = dL/dh_{t+1}:
@@ -18,21 +19,8 @@
 // Rows i >= v of the 32-row tiles and columns >= D of the last column tile are zero operands throughout (g, and every saved tensor,
 // load as zero there, and every formula above is linear in g).  No atomics: the same inputs give the same bits.
 #include "ggnn_dense_graph.hpp"
-#include "ggnn_split.hpp"
-#include <type_traits>
 
 namespace ggnn {
-
-namespace {
-
-// this wave's column tile of one bf16x3 split stage image: three planes x NC2 chunks of 8 halves per lane + the remainder rows
-template <int D>
-struct TileWB {
-    u32x4 p[3][SplitCfg<D>::NC2 > 0 ? SplitCfg<D>::NC2 : 1];
-    float r[StageCfg<D>::NR > 0 ? StageCfg<D>::NR : 1];
-};
-
-}  // namespace
 
 // 6 + E transposed images in the order the kernel consumes them: Wc[h]^T, Wg[x,r]^T, Wg[x,u]^T, Wc[x]^T, Wg[h,r]^T, Wg[h,u]^T, W_e^T
 // (Wg rows [x | h], columns [r | u];  Wc rows [x | r*h])
@@ -56,19 +44,16 @@ template <int D, int E, int NW>
 __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGraphBwdArgs a) {
     using C = StageCfg<D>;
     using SC = SplitCfg<D>;
-    constexpr int NP = 3;
-    constexpr int NT = C::NT, NC = C::NC, NR = C::NR, NC2 = SC::NC2;
-    constexpr int MP = C::BN + 4;                                      // row pitch of the f32 dx block (floats)
+    using L = DenseBwdLds<D, E>;
+    constexpr int FMT = kSplitBf16x3;                                  // every backward product runs in the exact format
+    constexpr int NT = C::NT, NC = C::NC, NR = C::NR;
+    constexpr int MP = L::T::MP, AP = L::T::AP, PBLK = L::T::PBLK;     // pitch of the f32 dx block, of an adjacency row; one operand block
     constexpr int NS = E + 6;                                          // stages per timestep
-    constexpr int AP = 33;
-    constexpr int PSLOT = 32 * 4;                                      // floats of one (plane, chunk, g) slab: 32 rows x 16 bytes
-    constexpr int PBLK = NP * NC2 * 4 * PSLOT + 32 * 4;                // floats of one split operand block (+ the remainder columns [32][4])
-    constexpr int NB = 4;                                              // operand blocks: dpc | dpu | dpr, then four dM_e at a time
     static_assert(NT <= NW && NS % 2 == 0 && NR <= 1, "one column tile per wave; two weight slots with a fixed phase per timestep");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* DXbuf = lds;                                                // [32][MP] f32: dx, the aggregation's operand
-    float* Pblk = DXbuf + 32 * MP;                                     // [NB] split operand blocks
-    float* Abuf = Pblk + (size_t)NB * PBLK;                            // [E][32][AP] adjacency rows
+    float* DXbuf = lds + L::DX;                                        // [32][MP] f32: dx, the aggregation's operand
+    float* Pblk = lds + L::P;                                          // [NB] split operand blocks
+    float* Abuf = lds + L::A;                                          // [E][32][AP] adjacency rows
     float* Bc = Pblk, * Bu = Pblk + PBLK, * Br = Pblk + 2 * PBLK;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -81,27 +66,9 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
     const bool tail = NR > 0 && tile == NC;                            // the tile of the D % 16 remainder columns (kq == 0 lanes hold them)
     const size_t bv = (size_t)a.b * v;
 
-    auto tile_to_lds = [&](float* blk, int t, f32x4 val) {
-        *reinterpret_cast<f32x4*>(blk + (size_t)(t * 16 + li) * MP + 16 * tile + 4 * kq) = val;
-    };
-    // this wave's four columns of row tile t, split, into an operand block (the forward's slot arithmetic)
-    auto tile_to_planes = [&](float* blk, int t, f32x4 val) {
-        if (!mm) return;
-        const int row = t * 16 + li;
-        if (tail) {
-            if (kq == 0) *reinterpret_cast<f32x4*>(blk + NP * NC2 * 4 * PSLOT + row * 4) = val;      // f32 remainder columns
-            return;
-        }
-        unsigned h0, m0, l0, h1, m1, l1;
-        split_pair<kSplitBf16x3>(val.x, val.y, h0, m0, l0);
-        split_pair<kSplitBf16x3>(val.z, val.w, h1, m1, l1);
-        const int c2 = tile >> 1;
-        float* dst = blk + ((size_t)(c2 * 4 + kq)) * PSLOT + row * 4 + 2 * (tile & 1);
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
-        *reinterpret_cast<u32x2*>(dst + NC2 * 4 * PSLOT) = u32x2{m0, m1};
-        *reinterpret_cast<u32x2*>(dst + 2 * NC2 * 4 * PSLOT) = u32x2{l0, l1};
-    };
+    auto image = [&](int s) { return a.img + (size_t)s * SC::IMG; };
+    auto to_lds = [&](float* blk, int t, f32x4 val) { tile_to_lds<D>(blk, t, val, li, kq, tile); };
+    auto to_planes = [&](float* blk, int t, f32x4 val) { tile_to_planes<D, FMT>(blk, t, val, li, kq, tile, mm, tail); };
     // this wave's four columns of row tile t of a [.., ld] tensor of this graph: zero outside the graph's rows and the D columns
     auto in_range = [&](int t) { return mm && t * 16 + li < v && col0 < D; };
     auto load_tile = [&](const float* base, int ld, int t) {
@@ -113,61 +80,19 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
         if (in_range(t)) *reinterpret_cast<f32x4*>(base + ((size_t)g * v + t * 16 + li) * ld + col0) = x;
     };
 
-    for (int idx = tid; idx < E * 32 * 32; idx += NW * 64) {
-        const int j = idx & 31, i = (idx >> 5) & 31, e = idx >> 10;
-        Abuf[(e * 32 + i) * AP + j] = (i < a.v && j < a.v) ? a.A[(((size_t)blockIdx.x * E + e) * a.v + i) * a.v + j] : 0.f;
-    }
+    dense_load_adjacency<E, NW>(Abuf, a.A, v, tid);
     f32x4 gt[2] = {load_tile(a.d_out, D, 0), load_tile(a.d_out, D, 1)};
 
-    // byte offsets of this wave's weight slice inside a split image (two column halves, ggnn_split.hpp)
-    const bool hb = tile >= SC::TA;
-    const int nth = hb ? NT - SC::TA : SC::TA, til = hb ? tile - SC::TA : tile;
-    const unsigned w_base = (hb ? (unsigned)SC::HA_BYTES : 0u) + (unsigned)(kq * nth * 16 + li + til * 16) * 16u;
-    const unsigned w_cst = (unsigned)(4 * nth * 16) * 16u, w_pst = (unsigned)NC2 * w_cst;          // chunk / plane pitch in bytes
-    const unsigned wr_base = (hb ? (unsigned)SC::HA_BYTES : 0u) + (unsigned)NP * w_pst + (unsigned)(kq * nth * 16 + li + til * 16) * 4u;
-    auto load_w = [&](TileWB<D>& w, const float* gimg) {
-        const unsigned long long p = reinterpret_cast<unsigned long long>(gimg);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
-        const float* sb = reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-            for (int c2 = 0; c2 < NC2; ++c2)
-                w.p[pl][c2] = __builtin_bit_cast(u32x4, ld4_b(sb, w_base + (unsigned)pl * w_pst + (unsigned)c2 * w_cst));
-#pragma unroll
-        for (int q = 0; q < NR; ++q) w.r[q] = ld1_b(sb, wr_base + (unsigned)(q * 4 * nth * 16) * 4u);
+    const int nth = tile_w_nth<D, FMT>(tile);
+    const unsigned w_base = tile_w_base<D, FMT>(li, kq, tile), wr_base = tile_wr_base<D, FMT>(li, kq, tile);
+    const unsigned w_cst = tile_w_cst(nth), w_pst = (unsigned)SC::NC2 * w_cst;                     // chunk / plane pitch in bytes
+    auto load_w = [&](TileW<D, FMT>& w, const float* gimg) { ggnn::load_w<D, FMT>(w, gimg, w_base, w_cst, w_pst, wr_base, nth); };
+    auto mma_pair = [&](auto zero_c, f32x4 (&acc)[2], const float* blk, const TileW<D, FMT>& w) {
+        ggnn::mma_pair<D, FMT, decltype(zero_c)::value>(acc, blk, w, li, kq);
     };
-    // both row tiles of an operand block against one weight slice: per chunk 6 operand reads feed 12 MFMAs (two accumulator chains)
-    auto mma_pair = [&](auto zero_c, f32x4 (&acc)[2], const float* blk, const TileWB<D>& w) {
-        constexpr bool ZERO = decltype(zero_c)::value;
-        f32x4 c0 = acc[0], c1 = acc[1];
-        if constexpr (ZERO) { c0 = f32x4{0.f, 0.f, 0.f, 0.f}; c1 = c0; }
-        const u32x4* ob = reinterpret_cast<const u32x4*>(blk) + kq * 32 + li;            // (plane, chunk) slabs are 128 slots apart
-#pragma unroll
-        for (int c2 = 0; c2 < NC2; ++c2) {
-            const u32x4 ah0 = ob[(0 * NC2 + c2) * 128], ah1 = ob[(0 * NC2 + c2) * 128 + 16];
-            const u32x4 am0 = ob[(1 * NC2 + c2) * 128], am1 = ob[(1 * NC2 + c2) * 128 + 16];
-            const u32x4 al0 = ob[(2 * NC2 + c2) * 128], al1 = ob[(2 * NC2 + c2) * 128 + 16];
-            const u32x4 wh = w.p[0][c2], wm = w.p[1][c2], wl = w.p[2][c2];
-            c0 = mfma_bf16(wl, ah0, c0); c1 = mfma_bf16(wl, ah1, c1);
-            c0 = mfma_bf16(wm, am0, c0); c1 = mfma_bf16(wm, am1, c1);
-            c0 = mfma_bf16(wm, ah0, c0); c1 = mfma_bf16(wm, ah1, c1);
-            c0 = mfma_bf16(wh, al0, c0); c1 = mfma_bf16(wh, al1, c1);
-            c0 = mfma_bf16(wh, am0, c0); c1 = mfma_bf16(wh, am1, c1);
-            c0 = mfma_bf16(wh, ah0, c0); c1 = mfma_bf16(wh, ah1, c1);
-        }
-        if constexpr (NR > 0) {
-            const float* rb = blk + NP * NC2 * 4 * PSLOT;                                  // [32][4] remainder columns
-            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.r[0], rb[li * 4 + kq], c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.r[0], rb[(16 + li) * 4 + kq], c1, 0, 0, 0);
-        }
-        acc[0] = c0; acc[1] = c1;
-    };
-    TileWB<D> tw[2];
-    if (mm) load_w(tw[0], a.img);
+    TileW<D, FMT> tw[2];
+    if (mm) load_w(tw[0], image(0));
 
-#define GGNN_DGB_T(K) if (a.tdbg && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 6) && rstep < 8) \
-        a.tdbg[(rstep * 2 + (wave ? 1 : 0)) * 8 + (K)] = __builtin_amdgcn_s_memtime();
     for (int step = a.steps - 1; step >= 0; --step) {
         const int rstep = a.steps - 1 - step;
         const bool last = step == 0;
@@ -175,15 +100,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
         const size_t TS = (size_t)a.steps * bv * D;                    // (saved [6][steps][b v, D]: h_t | x_t | r | u | c | r*h)
         float* o_dpc = a.dpc + (size_t)step * bv * D;
         float* o_dpg = a.dpg + (size_t)step * bv * 2 * D;
-        GGNN_DGB_T(0)
-#define GGNN_DGB_STAGE(S, ACC, BLK, ZERO)                                                                  \
-        {                                                                                                  \
-            __builtin_amdgcn_sched_barrier(0);   /* (the look-ahead stays at ONE stage, as in the forward) */ \
-            if (mm && !(last && (S) + 1 == NS)) load_w(tw[((S) + 1) & 1], a.img + (size_t)(((S) + 1) % NS) * SC::IMG); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (mm) mma_pair(std::integral_constant<bool, ZERO>{}, ACC, BLK, tw[(S) & 1]);                 \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-        }
+        GGNN_DENSE_STAMP(rstep, 0)
         // ---- the pre-activation gradients of the candidate and of the update gate ------------------------------------------------
         f32x4 ht[2], ut[2];
 #pragma unroll
@@ -199,13 +116,13 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
             }
             store_tile(o_dpc, D, t, dpc);
             store_tile(o_dpg + D, 2 * D, t, dpu);
-            tile_to_planes(Bc, t, dpc);
-            tile_to_planes(Bu, t, dpu);
+            to_planes(Bc, t, dpc);
+            to_planes(Bu, t, dpu);
         }
         __syncthreads();                                               // (1) dpc, dpu complete, split (first pass: the adjacency too)
-        GGNN_DGB_T(1)
+        GGNN_DENSE_STAMP(rstep, 1)
         f32x4 drh[2];
-        GGNN_DGB_STAGE(0, drh, Bc, true)
+        GGNN_DENSE_STAGE(0, drh, Bc, true)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const f32x4 rt = load_tile(sv + 2 * TS, D, t);
@@ -216,24 +133,24 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
                 drh[t][e] *= rt[e];                                    // the state's share through r*h
             }
             store_tile(o_dpg, 2 * D, t, dpr);
-            tile_to_planes(Br, t, dpr);
+            to_planes(Br, t, dpr);
         }
         __syncthreads();                                               // (2) dpr complete, split
-        GGNN_DGB_T(2)
+        GGNN_DENSE_STAMP(rstep, 2)
         f32x4 dx[2], dh[2];
-        GGNN_DGB_STAGE(1, dx, Br, true)
-        GGNN_DGB_STAGE(2, dx, Bu, false)
-        GGNN_DGB_STAGE(3, dx, Bc, false)
-        GGNN_DGB_STAGE(4, dh, Br, true)
-        GGNN_DGB_STAGE(5, dh, Bu, false)
+        GGNN_DENSE_STAGE(1, dx, Br, true)
+        GGNN_DENSE_STAGE(2, dx, Bu, false)
+        GGNN_DENSE_STAGE(3, dx, Bc, false)
+        GGNN_DENSE_STAGE(4, dh, Br, true)
+        GGNN_DENSE_STAGE(5, dh, Bu, false)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             store_tile(a.dx + (size_t)step * bv * D, D, t, dx[t]);
-            if (mm) tile_to_lds(DXbuf, t, dx[t]);
+            if (mm) to_lds(DXbuf, t, dx[t]);
         }
-        GGNN_DGB_T(3)
+        GGNN_DENSE_STAMP(rstep, 3)
         __syncthreads();                                               // (3) dx complete; the three operand blocks are free
-        GGNN_DGB_T(4)
+        GGNN_DENSE_STAMP(rstep, 4)
         // ---- dM_e = A_e^T dx on the matrix pipe (f32, like the forward's aggregation), split into block BI; then dh += dM_e W_e^T ----
 #define GGNN_DGB_AGG(EE, BI)                                                                               \
         if constexpr ((EE) < E) {                                                                          \
@@ -250,10 +167,10 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
             }                                                                                              \
             store_tile(a.dM + (size_t)step * bv * E * D + (EE) * D, E * D, 0, dm[0]);                      \
             store_tile(a.dM + (size_t)step * bv * E * D + (EE) * D, E * D, 1, dm[1]);                      \
-            tile_to_planes(Pblk + (size_t)(BI) * PBLK, 0, dm[0]);                                          \
-            tile_to_planes(Pblk + (size_t)(BI) * PBLK, 1, dm[1]);                                          \
+            to_planes(Pblk + (size_t)(BI) * PBLK, 0, dm[0]);                                          \
+            to_planes(Pblk + (size_t)(BI) * PBLK, 1, dm[1]);                                          \
         }
-#define GGNN_DGB_XFORM(EE, BI) if constexpr ((EE) < E) { GGNN_DGB_STAGE(6 + (EE), dh, Pblk + (size_t)(BI) * PBLK, false) }
+#define GGNN_DGB_XFORM(EE, BI) if constexpr ((EE) < E) { GGNN_DENSE_STAGE(6 + (EE), dh, Pblk + (size_t)(BI) * PBLK, false) }
 #define GGNN_DGB_GROUP(E0)                                                                                 \
         if constexpr ((E0) < E) {                                                                          \
             if constexpr ((E0) > 0) __syncthreads();                   /* the previous group's blocks have been consumed */ \
@@ -262,52 +179,29 @@ __global__ __launch_bounds__(NW * 64) void ggnn_dense_graph_bwd_kernel(DenseGrap
             GGNN_DGB_XFORM((E0) + 0, 0) GGNN_DGB_XFORM((E0) + 1, 1) GGNN_DGB_XFORM((E0) + 2, 2) GGNN_DGB_XFORM((E0) + 3, 3) \
         }
         GGNN_DGB_GROUP(0)
-        GGNN_DGB_T(5)
+        GGNN_DENSE_STAMP(rstep, 5)
         GGNN_DGB_GROUP(4)
-        GGNN_DGB_T(6)
+        GGNN_DENSE_STAMP(rstep, 6)
 #undef GGNN_DGB_GROUP
 #undef GGNN_DGB_XFORM
 #undef GGNN_DGB_AGG
-#undef GGNN_DGB_STAGE
         // ---- g <- dh: the products, the share through r*h, and g u LAST (see the file header) ----------------------------------------
 #pragma unroll
         for (int t = 0; t < 2; ++t) gt[t] = (dh[t] + drh[t]) + gt[t] * ut[t];
-        GGNN_DGB_T(7)
+        GGNN_DENSE_STAMP(rstep, 7)
         if (!last) __syncthreads();                                    // (4) the operand blocks are free for the next pass
     }
-#undef GGNN_DGB_T
     if (a.d_h0) { store_tile(a.d_h0, D, 0, gt[0]); store_tile(a.d_h0, D, 1, gt[1]); }
 }
 
-static size_t bwd_lds_bytes(int D, int E) {
-    const int bn = (D + 15) / 16 * 16, nc2 = (D / 16) / 2;
-    const size_t pblk = (size_t)3 * nc2 * 4 * 128 + 128;
-    return ((size_t)32 * (bn + 4) + 4 * pblk + (size_t)E * 32 * 33) * sizeof(float);
-}
-
 int dense_bwd_supported(int v, int E, int D) {
-    return dense_split_supported(v, E, D) && bwd_lds_bytes(D, E) <= (size_t)160 * 1024;
+    return dense_split_supported(v, E, D) && dense_dispatch(D, E, [](auto d, auto e) {
+        return DenseBwdLds<decltype(d)::value, decltype(e)::value>::BYTES <= kDenseLdsLimit; });
 }
 
 size_t dense_bwd_packed_bytes(int D, int E) {
     if (E <= 0) return 0;
-    switch (D) {
-        case 100: return (size_t)(6 + E) * SplitCfg<100>::IMG_BYTES;
-        case 64: return (size_t)(6 + E) * SplitCfg<64>::IMG_BYTES;
-        case 32: return (size_t)(6 + E) * SplitCfg<32>::IMG_BYTES;
-        default: return 0;
-    }
-}
-
-template <int D, int E>
-static int launch_bwd(const DenseGraphBwdArgs& a, hipStream_t st) {
-    constexpr int NW = 8;
-    const size_t ldsb = bwd_lds_bytes(D, E);
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (ldsb > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&ggnn_dense_graph_bwd_kernel<D, E, NW>, ldsb, lds_ok)));
-    hipLaunchKernelGGL((ggnn_dense_graph_bwd_kernel<D, E, NW>), dim3(a.b), dim3(NW * 64), ldsb, st, a);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    return dense_for_D(D, [&](auto d) { return (size_t)(6 + E) * SplitCfg<decltype(d)::value>::IMG_BYTES; });
 }
 
 }  // namespace ggnn
@@ -319,12 +213,10 @@ extern "C" size_t ggnn_dense_bwd_packed_bytes(int D, int E) { return dense_bwd_p
 extern "C" int ggnn_dense_bwd_pack_f32(const float* W, const float* Wg, const float* Wc, int E, int D, float* packed, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(W && Wg && Wc && packed && aligned16(packed) && E > 0 && E <= 64, "null or misaligned pointer, or E = %d outside 1..64", E);
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 100: hipLaunchKernelGGL((dense_bwd_pack_kernel<100>), dim3(8, 6 + E), dim3(256), 0, st, W, Wg, Wc, packed); break;
-        case 64: hipLaunchKernelGGL((dense_bwd_pack_kernel<64>), dim3(8, 6 + E), dim3(256), 0, st, W, Wg, Wc, packed); break;
-        case 32: hipLaunchKernelGGL((dense_bwd_pack_kernel<32>), dim3(8, 6 + E), dim3(256), 0, st, W, Wg, Wc, packed); break;
-        default: return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense backward for hidden size %d", D);
-    }
+    if (!dense_bwd_packed_bytes(D, E)) return fail(GGNN_E_UNSUPPORTED, "no graph-resident dense backward for hidden size %d", D);
+    dense_for_D(D, [&](auto d) {
+        hipLaunchKernelGGL((dense_bwd_pack_kernel<decltype(d)::value>), dim3(8, 6 + E), dim3(256), 0, st, W, Wg, Wc, packed);
+        return 0; });
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
@@ -340,13 +232,9 @@ extern "C" int ggnn_dense_propagate_bwd_f32(const float* d_out, const float* A, 
     GGNN_CHECK_ARG(d_out && A && bwd_packed && saved && dpc && dpg && dx && dM, "null pointer");
     GGNN_CHECK_ARG(aligned16(d_out) && aligned16(bwd_packed) && aligned16(saved) && aligned16(dpc) && aligned16(dpg) && aligned16(dx) &&
                    aligned16(dM) && (!d_h0 || aligned16(d_h0)), "pointers must be 16-byte aligned");
-    DenseGraphBwdArgs a{d_out, A, bwd_packed, saved, d_h0, dpc, dpg, dx, dM, b, v, steps, nullptr};
-    { const char* e = getenv("GGNN_DGB_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
+    const DenseGraphBwdArgs a{d_out, A, bwd_packed, saved, d_h0, dpc, dpg, dx, dM, b, v, steps, stamp_ptr_from_env("GGNN_DGB_TPTR")};
     hipStream_t st = (hipStream_t)stream;
-#define GGNN_DGB_CASE(DD, EE) if (D == DD && E == EE) return launch_bwd<DD, EE>(a, st);
-    GGNN_DGB_CASE(100, 4) GGNN_DGB_CASE(100, 2) GGNN_DGB_CASE(100, 6) GGNN_DGB_CASE(100, 8)
-    GGNN_DGB_CASE(64, 4) GGNN_DGB_CASE(64, 8) GGNN_DGB_CASE(64, 2) GGNN_DGB_CASE(64, 6)
-    GGNN_DGB_CASE(32, 4) GGNN_DGB_CASE(32, 8) GGNN_DGB_CASE(32, 2) GGNN_DGB_CASE(32, 6)
-#undef GGNN_DGB_CASE
-    return fail(GGNN_E_UNSUPPORTED, "graph-resident dense backward: unsupported shape");
+    return dense_dispatch(D, E, [&](auto d, auto e) {
+        constexpr int DD = decltype(d)::value, EE = decltype(e)::value;
+        return dense_graph_launch<&ggnn_dense_graph_bwd_kernel<DD, EE, kDenseWaves>>(DenseBwdLds<DD, EE>::BYTES, a, st); });
 }

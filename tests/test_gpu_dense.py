@@ -27,7 +27,8 @@ def test_dense_aggregate(pkg, cuda, b, v, E, D, bias):
 
 
 @pytest.mark.parametrize("b,v,E,D,bias,steps", [(7, 29, 4, 100, True, 4), (3, 32, 4, 100, False, 2), (5, 17, 8, 64, True, 3),
-                                                 (4, 5, 2, 32, True, 4), (2, 16, 6, 100, True, 1), (256, 29, 4, 100, True, 4)])
+                                                 (4, 5, 2, 32, True, 4), (2, 16, 6, 100, True, 1), (256, 29, 4, 100, True, 4),
+                                                 (3, 32, 6, 100, False, 3), (2, 7, 6, 100, True, 2)])
 @pytest.mark.parametrize("fmt", [3, 2])
 def test_graph_resident_dense_forward(pkg, oracle, cuda, b, v, E, D, bias, steps, fmt):
     """ggnn_dense_propagate_f32 -- all timesteps of a graph in one workgroup -- against the fp64 oracle of

@@ -15,9 +15,10 @@ import train_reference as TR
 
 pytestmark = pytest.mark.gpu
 
-# test_graph_resident_dense_forward's shapes, plus one vertex in one graph and the flagship batch
+# test_graph_resident_dense_forward's shapes, plus one vertex in one graph and the flagship batch, plus two with six edge types (the
+# backward's second group of operand blocks half full; D = 64 and D = 32 differ in chunk count)
 SHAPES = [(7, 29, 4, 100, True, 4), (3, 32, 4, 100, False, 2), (5, 17, 8, 64, True, 3), (4, 5, 2, 32, True, 4), (2, 16, 6, 100, True, 1),
-          (256, 29, 4, 100, True, 4), (1, 1, 4, 100, True, 2)]
+          (256, 29, 4, 100, True, 4), (1, 1, 4, 100, True, 2), (3, 9, 6, 64, True, 2), (2, 20, 6, 32, False, 3)]
 ACCURACY = {}            # figures of test_backward_kernel_against_fp64, written to $GGNN_DENSE_TRAIN_ACCURACY_JSON when that is set
 
 
@@ -253,6 +254,10 @@ def test_backward_kernel_against_fp64(pkg, oracle, cuda, b, v, E, D, bias, steps
         3, 32, 4, 100, 2           (0,2)  5.1e-7 / 6.8e-7                  5.1e-7 / 7.6e-7      4.9e-7 / 5.4e-7
         1, 1, 4, 100, 2            0/1    4.0e-7 / 4.5e-7                  3.2e-7 / 3.2e-7      3.2e-7 / 2.6e-7
         1, 1, 4, 100, 2            (0,2)  4.0e-7 / 6.3e-7                  2.6e-7 / 3.2e-7      1.9e-7 / 3.0e-7
+        3, 9, 6, 64, 2             0/1    4.8e-7 / 6.3e-7                  5.4e-7 / 7.1e-7      5.4e-7 / 9.5e-7
+        3, 9, 6, 64, 2             (0,2)  5.1e-7 / 5.7e-7                  6.0e-7 / 1.1e-6      6.2e-7 / 5.6e-7
+        2, 20, 6, 32, 3            0/1    4.2e-7 / 5.4e-7                  4.4e-7 / 5.5e-7      4.0e-7 / 6.3e-7
+        2, 20, 6, 32, 3            (0,2)  4.5e-7 / 5.9e-7                  5.0e-7 / 5.2e-7      5.1e-7 / 5.1e-7
     (2, 16, 6, 100, 1) is refused by the route (_assert_refused) and has no figures."""
     x = _inputs(oracle, b, v, E, D, bias, steps, weighted=weighted)
     if not _supported(pkg, v, E, D):

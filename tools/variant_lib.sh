@@ -10,10 +10,8 @@ objs=$(ls "$P"/build/*.o)
 new=""
 for src in ${srcs//,/ }; do
     base=$(basename "$src" .hip)
-    extra=""
-    case $base in   # the translation units build.py compiles without packed-f32 vector instructions
-        *_split|ggnn_msg_compact|ggnn_panel|ggnn_bwd_gemm|ggnn_gru_wide) extra="-Xclang -target-feature -Xclang -packed-fp32-ops -mllvm -amdgpu-use-amdgpu-trackers=1" ;;
-    esac
+    # the per-source flags of build.py (the translation units it compiles without packed-f32 vector instructions)
+    extra=$(cd "$P" && python3 -c "import sys, build; print(' '.join(build.PER_SOURCE_FLAGS.get(sys.argv[1], [])))" "$base.hip")
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -I "$ROOT/include" $extra "$@" -c "$P/csrc/$base.hip" -o "/tmp/${base}_$tag.o"
     objs=$(echo "$objs" | grep -v "/$base.o")
     new="$new /tmp/${base}_$tag.o"
