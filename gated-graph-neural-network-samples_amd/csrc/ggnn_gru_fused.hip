@@ -42,7 +42,29 @@
 #define GGNN_TDBG(a) ((unsigned long long*)nullptr)
 #endif
 
+// The ablation bits of GGNN_GRU_DBG (1 MFMAs off, 2 | 4 the gates / output epilogues off, 8 image DMA off, 16 fragment splits off,
+// 32 raised priority around the MFMA blocks; tools/gru_ablate.py, tools/exp_ablate_f16.sh) are experiment switches: every test of one
+// inside the stage loop is a scalar compare and a branch, and the mask stays live across the whole pass.  They exist only with
+// -DGGNN_GRU_ABLATE=1 (a variant library, tools/variant_lib.sh); in the product library the tests are the constant false, the
+// kernel has no such parameter and the launch reads no environment variable for it.
+#ifndef GGNN_GRU_ABLATE
+#define GGNN_GRU_ABLATE 0
+#endif
+#if GGNN_GRU_ABLATE
+#define GGNN_ABL(BIT) ((ablate & (BIT)) != 0)
+#define GGNN_ABL_PARAM , int ablate
+#define GGNN_ABL_ARG , gru_ablate_bits()
+static int gru_ablate_bits() { static const int v = [] { const char* e = getenv("GGNN_GRU_DBG"); return e ? atoi(e) : 0; }(); return v; }
+#else
+#define GGNN_ABL(BIT) (false)
+#define GGNN_ABL_PARAM
+#define GGNN_ABL_ARG
+#endif
+
 namespace ggnn {
+
+// ticket source of a fused GRU instantiation (the kernel's TK)
+constexpr int kTkRuntime = -1, kTkStatic = 0, kTkCounter = 1;
 
 // large hidden sizes (multiples of 64 from 128): column-panel kernels, ggnn_panel.hip
 int gru_panel_supported(int D);
@@ -52,7 +74,7 @@ int gru_panel_dispatch(const GruFusedArgs& a, int D, float* packed, hipStream_t 
 // This source is compiled TWICE: as itself (the f32-MFMA instantiations, the dispatch, the C entry points) and, through
 // ggnn_gru_fused_split.hip (GGNN_GRU_TU_SPLIT), for the SPLIT instantiations -- that translation unit is built without
 // packed-f32 vector instructions (build.py: a v_pk_* instruction beside the partner wave's bf16 MFMAs stalls the SIMD).
-int gru_split_launch(int D, int nx, bool save, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st);
+int gru_split_launch(int D, int nx, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st);
 
 #ifndef GGNN_GRU_TU_SPLIT
 int gru_pack_floats(int D, int nx) {
@@ -125,9 +147,7 @@ __device__ __forceinline__ void frag_add(Frag<D>& f, const Frag<D>& t) {
 // for it (only slots beyond the pipelined depth, 4 per row = the largest valence in QM9, are fetched synchronously).
 // SPLIT: the products run on the bf16 matrix pipe in 3-way split form (ggnn_split.hpp) -- same stages, same fragments, same
 // accumulators; the stage images are the split ones and every activation fragment is split in registers before its first stage.
-// SAVEX: the gathered segment is stored too (save_x; training).  The split-form inference dispatch runs <SAVE = true, SAVEX =
-// false>: the instantiation with the r / u / c stores (skipped at run time) but without the save_x path comes out of the register
-// allocator with the least scratch (R = 1 / 2: 8 / 36 B; with it 28 / 40 B; SAVE = false: 164 / 196 B).
+// SAVEX: the gathered segment is stored too (save_x; training).  Inference runs <SAVE = false, SAVEX = false>.
 // FORM: how a pass's stage images come through the LDS ring.
 //   0  one 8-wave workgroup per CU, whole images, 2 slots; the barrier that closes a stage waits for EVERY load the wave has
 //      issued (vmcnt(0): the next image's DMA, but also the stage's gather / fragment fetches).
@@ -142,11 +162,16 @@ __device__ __forceinline__ void frag_add(Frag<D>& f, const Frag<D>& t) {
 //      splits and DMA all switched off -- 18 stage barriers each waiting out one HBM round trip -- 63 us with only the MFMAs
 //      added, 63 us with only the side work added, 88 us with both: the three parts ran one after the other.
 // Same products in the same order per accumulator in every form: bit-identical results.
+// TK: where a pass's ticket comes from -- kTkStatic (b, b + nb, ...), kTkCounter (GruFusedArgs::tickets) or kTkRuntime (tested per
+// pass).  G4AVG: the gather's parameters are the constants T = 4 edge types, mean aggregation (the reference's default and the
+// benchmark's case): no per-row tests of g_use_avg / g_T and no registers for them.  The hot inference launches (hidden size 100) are
+// instantiated with both fixed, everything else runs the generic <kTkRuntime, false> instantiation: same arithmetic either way.
 // FMT (SPLIT kernels): operand format of the split products and of the images (ggnn_split.hpp) -- kSplitF16x2 (two f16 pieces, three
 // products: half the MFMAs, 48 KiB images; valid inside its operand range) or the exact kSplitBf16x3, chosen per launch by
 // GruFusedArgs::fmt; f32 kernels: kSplitBf16x3 stands for "accumulators unscaled".
-template <int D, int NX, int NW, bool SAVE, bool GATHER, bool SPLIT, bool SAVEX = SAVE, int FORM = 0, int FMT = kSplitBf16x3>
-__global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_kernel(GruFusedArgs a, const float* __restrict__ packed) {
+template <int D, int NX, int NW, bool SAVE, bool GATHER, bool SPLIT, bool SAVEX = SAVE, int FORM = 0, int FMT = kSplitBf16x3,
+          int TK = kTkRuntime, bool G4AVG = false>
+__global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_kernel(GruFusedArgs a, const float* __restrict__ packed GGNN_ABL_PARAM) {
     static_assert(SPLIT || FMT == kSplitBf16x3, "the f32-MFMA kernels have no operand format");
     using C = StageCfg<D>;
     using I = ImgCfg<D, SPLIT, FMT>;
@@ -156,6 +181,11 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     constexpr int NSLOT = DEEP ? 3 : 2;
     static_assert(!HALF || SPLIT, "the half-stage forms are split-form kernels");
     static_assert(FORM != 1 || NW == 4, "form 1 is the four-wave kernel");
+    static_assert(!G4AVG || GATHER, "G4AVG fixes the gather's parameters");
+    auto dyn_tk = [&]() -> bool {                                     // tickets from the global counter?
+        if constexpr (TK == kTkRuntime) return a.tickets != nullptr;
+        else return TK == kTkCounter;
+    };
     constexpr int NT = C::NT, NC = C::NC, NR = C::NR;
     constexpr int NSTAGE = 3 * (NX + 1);
     constexpr int SLOT = HALF ? SC::HA : I::IMG;                     // floats per ring slot
@@ -185,7 +215,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     // One-tile tail tickets (tail_w == 1, the usual case) are worked COOPERATIVELY: all waves take the same 16 rows and
     // wave w computes output column tile w of every gate (25 MFMAs per stage instead of 175 on one wave while seven
     // idle); the r*h fragment, which the candidate stage needs whole, is exchanged through LDS.
-    const bool coop_tail = (tail_w == 1) && (NT <= NW) && !HALF;   // (the half-stage forms run thin tail tickets on single waves)
+    const bool coop_tail = !HALF && (tail_w == 1) && (NT <= NW);   // (the half-stage forms run thin tail tickets on single waves)
     auto is_coop = [&](int t) -> bool { return coop_tail && t >= full_tk && t < n_tk; };
     auto tile_of = [&](int t) -> int {                              // this wave's tile of ticket t, or -1
         if (t < full_tk) return t * NW + wave;
@@ -213,9 +243,17 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     // (form 1: the SIMD partner is another workgroup's wave at a phase of its own: every wave issues its side work first)
     const bool late = FORM == 1 || wave >= NW / 2;
     int tk = blockIdx.x, tk_next = blockIdx.x + nb;                 // current / next pass's ticket (workgroup-uniform)
-    if (a.tickets && tid == 0) *tk_slot = nb + atomicAdd(a.tickets, 1);
+    if (dyn_tk() && tid == 0) *tk_slot = nb + atomicAdd(a.tickets, 1);
 
     int cur = 0;
+    // Global address of packed image `image`, REcomputed where it is used (the base passes through an empty asm): the compiler otherwise
+    // keeps every stage's DMA source -- 3 (NX + 1) images x halves x pieces, all loop invariants -- in a scalar register pair of its
+    // own, and with ~100 scalar registers in use those were spilled to vector lanes and read back (v_readlane) in front of every DMA.
+    auto image_src = [&](int image) -> const float* {
+        const float* p = packed;
+        asm volatile("" : "+s"(p));
+        return p + (size_t)image * I::IMG;
+    };
     // SPLIT: the DMA goes out through inline assembly and is waited for explicitly (dma_image_asm, ggnn_split.hpp)
     auto dma = [&](const float* src, float* dst) {
         if constexpr (SPLIT) dma_image_asm<I::IMG_BYTES, NW>(src, dst, wave, lane);
@@ -270,7 +308,9 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     auto g_ptrs = [&](int r, bool on) {               // level 1: slot range + in-degree of row r
         const int b = ldi_b(a.g_row_ptr, (unsigned)r * 4u), e = ldi_b(a.g_row_ptr, (unsigned)r * 4u + 4u);   // r is valid even when !on
         g_beg = on ? b : 0; g_end = on ? e : 0;
-        if (a.g_use_avg) {
+        if constexpr (G4AVG) {
+            g_n = ld4_b(a.g_nin, (unsigned)r * 16u);
+        } else if (a.g_use_avg) {
             if (a.g_T == 4) {
                 g_n = ld4_b(a.g_nin, (unsigned)r * 16u);
             } else {
@@ -320,7 +360,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             frag_add<D>(f, gt);
         }
         if (g_beg >= g_end) frag_zero<D>(f);          // a node without incoming messages (slot 0 was row 0)
-        if (a.g_use_avg) {                                            // :206-209
+        if (G4AVG || a.g_use_avg) {                                   // :206-209
             // x / den for the 25+ values of the row with ONE division: r = RN(1/den), q = RN(x r), then the FMA
             // residual step q + (x - den q) r.  With a correctly rounded r this IS the correctly rounded quotient
             // (Markstein) -- bit-identical to the `/` of the stand-alone kernel, asserted by the tests -- for 3 vector-ALU
@@ -369,7 +409,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     }
     publish();                // (f32: hipcc emits vmcnt(0) before the barrier while an LDS-DMA is in flight)
 
-    if (a.tickets) tk_next = __builtin_amdgcn_readfirstlane(*tk_slot);
+    if (dyn_tk()) tk_next = __builtin_amdgcn_readfirstlane(*tk_slot);
 
     // One pass (= one ticket) of the workgroup.  COOP is a compile-time flag: the ordinary passes and the cooperative
     // tail passes are separate instantiations, run by separate loops below, so the register allocation of the hot loop
@@ -395,7 +435,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
         const int rown = rown_ < a.V ? rown_ : a.V - 1;
         // the ticket after the next one: requested now, published before the last stage's barrier, read after it
         int tk_fetch = 0;
-        if (a.tickets && tid == 0) tk_fetch = atomicAdd(a.tickets, 1);
+        if (dyn_tk() && tid == 0) tk_fetch = atomicAdd(a.tickets, 1);
 
         // what is fetched at the START of stage POS (it lands in the shadow of that stage's MFMAs and is drained
         // by its closing barrier)
@@ -452,7 +492,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                 if (wave < NT && wave * 16 + 4 * kq < D) hv_pre = ld4_b(a.h, ((unsigned)rowc * D + wave * 16 + 4 * kq) * 4u); \
             }                                                                                            \
             GGNN_T(POS, 1)                                                                               \
-            if (active && wave < NT && !(a.dbg & 1)) {                                                   \
+            if (active && wave < NT && !GGNN_ABL(1)) {                                                   \
                 if (C::TAILPACK3 && (POS) == NSTAGE - 1 && wave == NT - 1) {                             \
                     /* the candidate's last tile: x part + r*h part as two sums, like the tail-packed ordinary passes */ \
                     f32x4 t_;                                                                            \
@@ -473,8 +513,8 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
         {                                                                                                \
             constexpr int npos_ = (POS) + 1;                                                             \
             const bool more_ = (npos_ < NSTAGE) || tk_next < n_dma;                                      \
-            const float* csrc_ = packed + (size_t)gru_stage_image<NX>(POS) * I::IMG;                     \
-            const float* nsrc_ = packed + (size_t)gru_stage_image<NX>(npos_ < NSTAGE ? npos_ : 0) * I::IMG; \
+            const float* csrc_ = image_src(gru_stage_image<NX>(POS));                     \
+            const float* nsrc_ = image_src(gru_stage_image<NX>(npos_ < NSTAGE ? npos_ : 0)); \
             constexpr int ntl_ = ((C::TAILPACK && (POS) % 3 == 1) ||                                     \
                                   (C::TAILPACK3 && (POS) % 3 == 2 && (POS) < 3 * NX)) ? NT - 1 : NT;     \
             const int nxt_ = cur + 1 < NSLOT ? cur + 1 : 0, nx2_ = nxt_ + 1 < NSLOT ? nxt_ + 1 : 0;      \
@@ -482,31 +522,31 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             if constexpr (GATHER && (POS) == G_U % NSTAGE) {   /* the fragment this stage multiplies */  \
                 if (active && (!G_NEXT || p > 0)) { g_finish(xf[GBUF]); if constexpr (SAVEX) { if (row < a.V && a.save_x) store_x(xf[GBUF], row); } } \
             }                                                                                            \
-            if constexpr ((POS) % 3 == 0 || (POS) == NSTAGE - 1) { if (active && !(a.dbg & 16)) split_frag<D, FMT>(sf, FRAG); } \
+            if constexpr ((POS) % 3 == 0 || (POS) == NSTAGE - 1) { if (active && !GGNN_ABL(16)) split_frag<D, FMT>(sf, FRAG); } \
             /* ---- sub-stage A: tiles [0, TA) from slot cur */                                          \
             bool dma_a_ = false;                                                                         \
             if constexpr (DEEP) {                                                                        \
                 if (late) {                                                                              \
                     prefetch(std::integral_constant<int, (POS)>{}, 1);                                   \
-                    if (more_ && !(a.dbg & 8)) { dma_ha(nsrc_, ring + nx2_ * SLOT); dma_a_ = true; }     \
+                    if (more_ && !GGNN_ABL(8)) { dma_ha(nsrc_, ring + nx2_ * SLOT); dma_a_ = true; }     \
                     prefetch(std::integral_constant<int, (POS)>{}, 2);                                   \
                 }                                                                                        \
             } else {                                                                                     \
-                if (!(a.dbg & 8)) dma_hb(csrc_ + SC::HA, ring + nxt_ * SLOT);                            \
+                if (!GGNN_ABL(8)) dma_hb(csrc_ + SC::HA, ring + nxt_ * SLOT);                            \
                 prefetch(std::integral_constant<int, (POS)>{});                                          \
             }                                                                                            \
             GGNN_T(POS, 1)                                                                               \
             __builtin_amdgcn_sched_barrier(0);                                                           \
-            if (a.dbg & 32) __builtin_amdgcn_s_setprio(3);                                               \
-            if (active && !(a.dbg & 1))                                                                  \
+            if GGNN_ABL(32) __builtin_amdgcn_s_setprio(3);                                               \
+            if (active && !GGNN_ABL(1))                                                                  \
                 stage_mma_split_at<D, (ntl_ < SC::TA ? ntl_ : SC::TA), ((POS) < 3), 0, false, FMT>(ACC, sf, FRAG, ring + cur * SLOT, ring + cur * SLOT, li, kq); \
-            if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);                                               \
+            if GGNN_ABL(32) __builtin_amdgcn_s_setprio(0);                                               \
             __builtin_amdgcn_sched_barrier(0);                                                           \
             GGNN_T(POS, 2)                                                                               \
             if constexpr (DEEP) {                                                                        \
                 if (!late) {                                                                             \
                     prefetch(std::integral_constant<int, (POS)>{}, 1);                                   \
-                    if (more_ && !(a.dbg & 8)) { dma_ha(nsrc_, ring + nx2_ * SLOT); dma_a_ = true; }     \
+                    if (more_ && !GGNN_ABL(8)) { dma_ha(nsrc_, ring + nx2_ * SLOT); dma_a_ = true; }     \
                     prefetch(std::integral_constant<int, (POS)>{}, 2);                                   \
                 }                                                                                        \
                 publish_deep(dma_a_ ? own_a : 0);                                                        \
@@ -518,20 +558,20 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                 const int nb1_ = cur + 1 < NSLOT ? cur + 1 : 0, nb2_ = nb1_ + 1 < NSLOT ? nb1_ + 1 : 0;  \
                 bool dma_b_ = false;                                                                     \
                 if constexpr (DEEP) {                                                                    \
-                    if (late && more_ && !(a.dbg & 8)) { dma_hb(nsrc_ + SC::HA, ring + nb2_ * SLOT); dma_b_ = true; } \
+                    if (late && more_ && !GGNN_ABL(8)) { dma_hb(nsrc_ + SC::HA, ring + nb2_ * SLOT); dma_b_ = true; } \
                 } else {                                                                                 \
-                    if (more_ && !(a.dbg & 8)) dma_ha(nsrc_, ring + nb1_ * SLOT);                        \
+                    if (more_ && !GGNN_ABL(8)) dma_ha(nsrc_, ring + nb1_ * SLOT);                        \
                 }                                                                                        \
                 __builtin_amdgcn_sched_barrier(0);                                                       \
                 GGNN_T2(POS, 0)                                                                          \
-                if (a.dbg & 32) __builtin_amdgcn_s_setprio(3);                                           \
-                if (active && !(a.dbg & 1))                                                              \
+                if GGNN_ABL(32) __builtin_amdgcn_s_setprio(3);                                           \
+                if (active && !GGNN_ABL(1))                                                              \
                     stage_mma_split_at<D, ntl_, ((POS) < 3), SC::TA, false, FMT>(ACC, sf, FRAG, ring + cur * SLOT, ring + cur * SLOT, li, kq); \
-                if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);                                           \
+                if GGNN_ABL(32) __builtin_amdgcn_s_setprio(0);                                           \
                 __builtin_amdgcn_sched_barrier(0);                                                       \
                 GGNN_T2(POS, 1)                                                                          \
                 if constexpr (DEEP) {                                                                    \
-                    if (!late && more_ && !(a.dbg & 8)) { dma_hb(nsrc_ + SC::HA, ring + nb2_ * SLOT); dma_b_ = true; } \
+                    if (!late && more_ && !GGNN_ABL(8)) { dma_hb(nsrc_ + SC::HA, ring + nb2_ * SLOT); dma_b_ = true; } \
                     GGNN_T2(POS, 2)                                                                      \
                     publish_deep(dma_b_ ? own_b : 0);                                                    \
                 } else publish();                                                                        \
@@ -545,7 +585,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
         {                                                                                                \
             constexpr int npos_ = (POS) + 1;                                                             \
             const bool more_ = (npos_ < NSTAGE) || tk_next < n_dma;                                      \
-            const float* nsrc_ = packed + (size_t)gru_stage_image<NX>(npos_ < NSTAGE ? npos_ : 0) * I::IMG; \
+            const float* nsrc_ = image_src(gru_stage_image<NX>(npos_ < NSTAGE ? npos_ : 0)); \
             float* ndst_ = ring + (cur ^ 1) * I::IMG;                                                    \
             GGNN_T(POS, 0)                                                                               \
             if constexpr (GATHER && (POS) == G_U % NSTAGE) {   /* the fragment this stage multiplies */  \
@@ -558,7 +598,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                via the stage_mma hook measured slower.) */                                                \
             if (late) {                                                                                  \
                 prefetch(std::integral_constant<int, (POS)>{});                                          \
-                if (more_ && !(a.dbg & 8)) dma(nsrc_, ndst_);                             \
+                if (more_ && !GGNN_ABL(8)) dma(nsrc_, ndst_);                             \
             }                                                                                            \
             GGNN_T(POS, 1)                                                                               \
             __builtin_amdgcn_sched_barrier(0);   /* keep the side work on its side of the MFMA block */  \
@@ -568,9 +608,9 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                                   (C::TAILPACK3 && (POS) % 3 == 2 && (POS) < 3 * NX)) ? NT - 1 : NT;     \
             /* stages 0..2 open the three accumulator sets: they start from the constant 0 */            \
             /* SPLIT: a fragment is split into its bf16 planes before the first of its stages */         \
-            if constexpr (SPLIT && ((POS) % 3 == 0 || (POS) == NSTAGE - 1)) { if (active && !(a.dbg & 16)) split_frag<D, FMT>(sf, FRAG); } \
-            if (a.dbg & 32) __builtin_amdgcn_s_setprio(3);                                               \
-            if (active && !(a.dbg & 1)) {                                                                \
+            if constexpr (SPLIT && ((POS) % 3 == 0 || (POS) == NSTAGE - 1)) { if (active && !GGNN_ABL(16)) split_frag<D, FMT>(sf, FRAG); } \
+            if GGNN_ABL(32) __builtin_amdgcn_s_setprio(3);                                               \
+            if (active && !GGNN_ABL(1)) {                                                                \
                 const float* img_ = ring + cur * I::IMG;                                                 \
                 if constexpr (!coop) {                                                                   \
                     if constexpr (SPLIT) stage_mma_split<D, ntl_, ((POS) < 3), false, FMT>(ACC, sf, FRAG, img_, li, kq); \
@@ -585,11 +625,11 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                     else stage_mma_one<D, ((POS) < 3)>(ACC[0], FRAG, img_, li, kq, wave);                \
                 }                                                                                        \
             }                                                                                            \
-            if (a.dbg & 32) __builtin_amdgcn_s_setprio(0);                                               \
+            if GGNN_ABL(32) __builtin_amdgcn_s_setprio(0);                                               \
             __builtin_amdgcn_sched_barrier(0);                                                           \
             if (!late) {                                                                                 \
                 prefetch(std::integral_constant<int, (POS)>{});                                          \
-                if (more_ && !(a.dbg & 8)) dma(nsrc_, ndst_);                             \
+                if (more_ && !GGNN_ABL(8)) dma(nsrc_, ndst_);                             \
             }                                                                                            \
             GGNN_T(POS, 2)                                                                               \
             publish();                                                                                   \
@@ -625,7 +665,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             // cooperative tail pass: this wave holds column tile `wave` of r and u (accumulators [0]).  Its r*h tile goes
             // to LDS, every wave then reads the whole r*h fragment back; u and the h columns stay in acc_u[0] / acc_r[0].
             const int col = wave * 16 + 4 * kq;
-            if (wave < NT && col < D && !(a.dbg & 2)) {
+            if (wave < NT && col < D && !GGNN_ABL(2)) {
                 const f32x4 r = sigmoid4_acc<FMT>(acc_r[0], ld4(bias_s + col));
                 const f32x4 u = sigmoid4_acc<FMT>(acc_u[0], ld4(bias_s + D + col));
                 f32x4 hv;
@@ -645,7 +685,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             for (int c = 0; c < NC; ++c) rh.v[c] = *reinterpret_cast<const f32x4*>(rh_x + li * RHP + 16 * c + 4 * kq);
 #pragma unroll
             for (int q = 0; q < NR; ++q) rh.r[q] = rh_x[li * RHP + 16 * NC + 4 * q + kq];
-        } else if (active && !(a.dbg & 2)) {                   // (constexpr-else of the cooperative branch)
+        } else if (active && !GGNN_ABL(2)) {                   // (constexpr-else of the cooperative branch)
             stage_tail_reduce<D>(acc_r);                       // VALU-tail columns: add the four kq partials
             stage_tail_reduce<D>(acc_u);
             if constexpr (C::TAILPACK) {
@@ -666,6 +706,9 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                     const f32x4 r = sigmoid4_acc<FMT>(acc_r[nt], ld4(bias_s + col));
                     const f32x4 u = sigmoid4_acc<FMT>(acc_u[nt], ld4(bias_s + D + col));
                     acc_r[nt] = r; acc_u[nt] = u;
+                    // u is next used by the blend, a whole stage later: without a use HERE (the training instantiation has its store)
+                    // the compiler sinks the sigmoid down to the blend and the inference kernel runs out of registers
+                    if constexpr (!SAVE && SPLIT && GATHER) { touch(u.x); touch(u.y); touch(u.z); touch(u.w); }
                     if constexpr (SAVE) {
                         if (row < a.V && a.save_r) {
                             st4_b(a.save_r, ((unsigned)row * D + col) * 4u, r);
@@ -687,20 +730,20 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
         }
 
         // ---- candidate: the r*h rows of Wc ----------------------------------------------------------------
-        if (a.tickets && tid == 0) tk_slot[(p + 1) & 1] = nb + tk_fetch;
+        if (dyn_tk() && tid == 0) tk_slot[(p + 1) & 1] = nb + tk_fetch;
         GGNN_STAGE(3 * NX + 2, acc_c, rh)
 #undef GGNN_STAGE
 #undef GGNN_HALF_STAGE
 #undef GGNN_COOP_STAGE
         tk = tk_next;
-        tk_next = a.tickets ? __builtin_amdgcn_readfirstlane(tk_slot[(p + 1) & 1]) : tk_next + nb;
+        tk_next = dyn_tk() ? __builtin_amdgcn_readfirstlane(tk_slot[(p + 1) & 1]) : tk_next + nb;
 
         // ---- c = act(.), h' = u*h + (1-u)*c ----------------------------------------------------------------
         // remainder tile: lane (li,kq) needs h cols 16NC + 4kq + e = remainder frag q = kq of lane (li, e);
         // the cross-lane reads stay outside lane-divergent control flow
         if constexpr (coop) {
             const int col = wave * 16 + 4 * kq;
-            if (wave < NT && col < D && row < a.V && !(a.dbg & 4)) {
+            if (wave < NT && col < D && row < a.V && !GGNN_ABL(4)) {
                 f32x4 c;
                 if (a.act == GGNN_ACT_TANH) {
                     c = tanh4_acc<FMT>(acc_c[0], ld4(bias_s + 2 * D + col));
@@ -733,7 +776,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                 if (kq == q) hrem = f32x4{h0, h1, h2, h3};
             }
         }
-        if (active && row < a.V && !(a.dbg & 4)) {
+        if (active && row < a.V && !GGNN_ABL(4)) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int col = nt * 16 + 4 * kq;
@@ -765,13 +808,15 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     }
 }
 
-template <int D, int NX, int NW, bool SAVE, bool GATHER, bool SPLIT, bool SAVEX = SAVE, int FORM = 0, int FMT = kSplitBf16x3>
+template <int D, int NX, int NW, bool SAVE, bool GATHER, bool SPLIT, bool SAVEX = SAVE, int FORM = 0, int FMT = kSplitBf16x3,
+          int TK = kTkRuntime, bool G4AVG = false>
 static int launch_gru_fused_m(const GruFusedArgs& a_in, float* packed, hipStream_t st) {
     using C = StageCfg<D>;
     using I = ImgCfg<D, SPLIT, FMT>;
     GruFusedArgs a = a_in;
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("GGNN_GRU_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
+#if GGNN_GRU_STAMPS
     { const char* e = getenv("GGNN_GRU_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
+#endif
     if (a.Wg) {   // raw weights given: build the stage images first (skipped when the caller pre-packed them)
         hipLaunchKernelGGL((gru_pack_weights_kernel<D, SPLIT, FMT>), dim3(8, 3 * (NX + 1)), dim3(256), 0, st, a.Wg, a.Wc, NX, packed);
         GGNN_CHECK_HIP(hipGetLastError());
@@ -796,15 +841,15 @@ static int launch_gru_fused_m(const GruFusedArgs& a_in, float* packed, hipStream
     static const int coop_small = [] { const char* e = getenv("GGNN_GRU_COOP_SMALL"); return e ? atoi(e) : 1; }();
     if (FORM == 0 && coop_small && wt_total > nb && wt_total <= 2 * nb && StageCfg<D>::NT <= NW) nb = wt_total;
     static std::atomic<unsigned long long> lds_ok{0};        // (one per template instantiation)
-    if (lds > 64 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT>, lds, lds_ok));
-    hipLaunchKernelGGL((ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT>), dim3(nb), dim3(NW * 64), lds, st, a, (const float*)packed);
+    if (lds > 64 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT, TK, G4AVG>, lds, lds_ok));
+    hipLaunchKernelGGL((ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT, TK, G4AVG>), dim3(nb), dim3(NW * 64), lds, st, a, (const float*)packed GGNN_ABL_ARG);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
 
 #ifdef GGNN_GRU_TU_SPLIT
-// SAVE is a run-time matter in the kernel's epilogues (uniform branches on the save pointers): the training instantiation
-// serves inference too (it is also the one that comes out of the register allocator with less scratch).
+// Gather-fused launches: SAVE / SAVEX follow the call -- with save buffers the training instantiation, without them the inference
+// instantiation.  (The plain launches, off the timed path, keep the one instantiation whose stores are skipped at run time.)
 // GGNN_GRU_FORM: ring form of the gather-fused launches (the kernel's FORM): 0 whole images / 8 waves (the form before round 4),
 // 1 two 4-wave workgroups per CU on half-image rings, 2 8 waves on a 3-slot half-image ring with partial waits
 // Default (-1): form 1, except the single-input launch in the exact bf16x3 format.  Round 5, two-piece f16 format
@@ -821,38 +866,59 @@ static int gru_form(int nx, int fmt) {
     return v >= 0 ? v : ((nx >= 2 || fmt == kSplitF16x2) ? 1 : 0);
 }
 
+// gather-fused launch of one (NX, NW, FORM): training or inference instantiation by the save buffers
+template <int D, int NX, int NW, int FORM, int FMT>
+static int split_launch_gather(bool save, const GruFusedArgs& a, float* packed, hipStream_t st) {
+    return save ? launch_gru_fused_m<D, NX, NW, true, true, true, true, FORM, FMT>(a, packed, st)
+                : launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT>(a, packed, st);
+}
+// the hot inference launches: ticket source and gather parameters fixed at compile time (the kernel's TK / G4AVG)
+template <int D, int NX, int NW, int FORM, int FMT>
+static int split_launch_hot(const GruFusedArgs& a, float* packed, hipStream_t st) {
+    return a.tickets ? launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT, kTkCounter, true>(a, packed, st)
+                     : launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT, kTkStatic, true>(a, packed, st);
+}
+
 template <int D, int FMT>
-static int split_launch_d(int nx, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
+static int split_launch_d(int nx, bool save, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
     if constexpr (SplitCfg<D>::OK) {
+        const int f = gru_form(nx, FMT);
         // form 6: the wide kernel (one wave per SIMD, several tiles per wave; ggnn_gru_wide.hip)
         // (60 + NTW: the same with NTW tiles per wave where the instantiation exists -- experiments)
-        if (const int f = gru_form(nx, FMT); gather && (f == 6 || (f >= 60 && f < 70)) && gru_wide_supported(D, nx, a))
+        if (gather && (f == 6 || (f >= 60 && f < 70)) && gru_wide_supported(D, nx, a))
             return gru_wide_launch(D, nx, f >= 60 ? f - 60 : 0, a, packed, st);
-        if (gather && gru_form(nx, FMT) == 2) {
-            switch (nx) {
-                case 1: return launch_gru_fused_m<D, 1, 8, true, true, true, true, 2, FMT>(a, packed, st);
-                case 2: return a.save_x ? launch_gru_fused_m<D, 2, 8, true, true, true, true, 2, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 2, 8, true, true, true, false, 2, FMT>(a, packed, st);
-                case 3: return a.save_x ? launch_gru_fused_m<D, 3, 8, true, true, true, true, 2, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 3, 8, true, true, true, false, 2, FMT>(a, packed, st);
+        if constexpr (D == 100) {
+            // inference at the reference's hidden size, T = 4, mean aggregation, in the forms the default policy picks
+            if (gather && !save && a.g_use_avg && a.g_T == 4) {
+                if (f == 1) {
+                    switch (nx) {
+                        case 1: return split_launch_hot<D, 1, 4, 1, FMT>(a, packed, st);
+                        case 2: return split_launch_hot<D, 2, 4, 1, FMT>(a, packed, st);
+                        case 3: return split_launch_hot<D, 3, 4, 1, FMT>(a, packed, st);
+                    }
+                }
+                if constexpr (FMT == kSplitBf16x3) { if (f == 0 && nx == 1) return split_launch_hot<D, 1, 8, 0, FMT>(a, packed, st); }
             }
         }
-        if (gather && gru_form(nx, FMT) == 1) {
+        if (gather && f == 2) {
             switch (nx) {
-                case 1: return launch_gru_fused_m<D, 1, 4, true, true, true, true, 1, FMT>(a, packed, st);
-                case 2: return a.save_x ? launch_gru_fused_m<D, 2, 4, true, true, true, true, 1, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 2, 4, true, true, true, false, 1, FMT>(a, packed, st);
-                case 3: return a.save_x ? launch_gru_fused_m<D, 3, 4, true, true, true, true, 1, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 3, 4, true, true, true, false, 1, FMT>(a, packed, st);
+                case 1: return split_launch_gather<D, 1, 8, 2, FMT>(save, a, packed, st);
+                case 2: return split_launch_gather<D, 2, 8, 2, FMT>(save, a, packed, st);
+                case 3: return split_launch_gather<D, 3, 8, 2, FMT>(save, a, packed, st);
+            }
+        }
+        if (gather && f == 1) {
+            switch (nx) {
+                case 1: return split_launch_gather<D, 1, 4, 1, FMT>(save, a, packed, st);
+                case 2: return split_launch_gather<D, 2, 4, 1, FMT>(save, a, packed, st);
+                case 3: return split_launch_gather<D, 3, 4, 1, FMT>(save, a, packed, st);
             }
         }
         if (gather) {
             switch (nx) {
-                case 1: return launch_gru_fused_m<D, 1, 8, true, true, true, true, 0, FMT>(a, packed, st);        // (R = 0: no scratch either way)
-                case 2: return a.save_x ? launch_gru_fused_m<D, 2, 8, true, true, true, true, 0, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 2, 8, true, true, true, false, 0, FMT>(a, packed, st);
-                case 3: return a.save_x ? launch_gru_fused_m<D, 3, 8, true, true, true, true, 0, FMT>(a, packed, st)
-                                        : launch_gru_fused_m<D, 3, 8, true, true, true, false, 0, FMT>(a, packed, st);
+                case 1: return split_launch_gather<D, 1, 8, 0, FMT>(save, a, packed, st);
+                case 2: return split_launch_gather<D, 2, 8, 0, FMT>(save, a, packed, st);
+                case 3: return split_launch_gather<D, 3, 8, 0, FMT>(save, a, packed, st);
             }
         } else {
             switch (nx) {
@@ -864,8 +930,8 @@ static int split_launch_d(int nx, bool gather, const GruFusedArgs& a, float* pac
     }
     return fail(GGNN_E_INVALID, "nx %d outside 1..3", nx);
 }
-int gru_split_launch(int D, int nx, bool save, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
-    (void)save;
+int gru_split_launch(int D, int nx, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
+    const bool save = a.save_r != nullptr;      // (save_r / save_u / save_c come together: dispatch_nx)
 #ifdef GGNN_PROBE_NX   // register-allocation probe (tools/kernel_regs.sh .../ggnn_gru_fused_split.hip . -DGGNN_PROBE_NX=2): one instantiation
 #ifndef GGNN_PROBE_SAVE
 #define GGNN_PROBE_SAVE true
@@ -876,13 +942,26 @@ int gru_split_launch(int D, int nx, bool save, bool gather, const GruFusedArgs& 
 #ifndef GGNN_PROBE_FMT
 #define GGNN_PROBE_FMT kSplitF16x2
 #endif
-    return launch_gru_fused_m<100, GGNN_PROBE_NX, 8, GGNN_PROBE_SAVE, true, true, GGNN_PROBE_SAVEX, 0, GGNN_PROBE_FMT>(a, packed, st);
+#ifndef GGNN_PROBE_FORM     // (form 1 is the four-wave kernel: -DGGNN_PROBE_FORM=1 -DGGNN_PROBE_NW=4)
+#define GGNN_PROBE_FORM 0
+#endif
+#ifndef GGNN_PROBE_NW
+#define GGNN_PROBE_NW 8
+#endif
+#ifndef GGNN_PROBE_TK
+#define GGNN_PROBE_TK kTkRuntime
+#endif
+#ifndef GGNN_PROBE_G4AVG
+#define GGNN_PROBE_G4AVG false
+#endif
+    return launch_gru_fused_m<100, GGNN_PROBE_NX, GGNN_PROBE_NW, GGNN_PROBE_SAVE, true, true, GGNN_PROBE_SAVEX, GGNN_PROBE_FORM, GGNN_PROBE_FMT,
+                              GGNN_PROBE_TK, GGNN_PROBE_G4AVG>(a, packed, st);
 #else
     const bool f2 = gru_launch_fmt(a.fmt) == kSplitF16x2;            // (per launch: GruFusedArgs::fmt)
     switch (D) {
-        case 100: return f2 ? split_launch_d<100, kSplitF16x2>(nx, gather, a, packed, st) : split_launch_d<100, kSplitBf16x3>(nx, gather, a, packed, st);
-        case 64: return f2 ? split_launch_d<64, kSplitF16x2>(nx, gather, a, packed, st) : split_launch_d<64, kSplitBf16x3>(nx, gather, a, packed, st);
-        case 32: return f2 ? split_launch_d<32, kSplitF16x2>(nx, gather, a, packed, st) : split_launch_d<32, kSplitBf16x3>(nx, gather, a, packed, st);
+        case 100: return f2 ? split_launch_d<100, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<100, kSplitBf16x3>(nx, save, gather, a, packed, st);
+        case 64: return f2 ? split_launch_d<64, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<64, kSplitBf16x3>(nx, save, gather, a, packed, st);
+        case 32: return f2 ? split_launch_d<32, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<32, kSplitBf16x3>(nx, save, gather, a, packed, st);
         default: return fail(GGNN_E_UNSUPPORTED, "no split-form fused GRU for hidden size %d", D);
     }
 #endif
@@ -890,7 +969,7 @@ int gru_split_launch(int D, int nx, bool save, bool gather, const GruFusedArgs& 
 #else
 template <int D, int NX, int NW, bool SAVE, bool GATHER>
 static int launch_gru_fused(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    if (SplitCfg<D>::OK && split_matrix_path()) return gru_split_launch(D, NX, SAVE, GATHER, a, packed, st);
+    if (SplitCfg<D>::OK && split_matrix_path()) return gru_split_launch(D, NX, GATHER, a, packed, st);
     return launch_gru_fused_m<D, NX, NW, SAVE, GATHER, false>(a, packed, st);
 }
 

@@ -15,8 +15,19 @@
 
 namespace ggnn {
 
+// The clock stamps behind GGNN_K1C_TPTR (tools/k1c_timeline.py) are eight tested branches per wave, and a wave works two or three
+// tiles: compiled in only with -DGGNN_K1C_STAMPS=1 (a variant library, tools/variant_lib.sh).
+#ifndef GGNN_K1C_STAMPS
+#define GGNN_K1C_STAMPS 0
+#endif
+
 constexpr int kMaxTypesC = 64;
-struct TypeRows { int row_off[kMaxTypesC + 1]; int tile_off[kMaxTypesC + 1]; int T; int num_nodes; unsigned long long* tdbg; };
+struct TypeRows {
+    int row_off[kMaxTypesC + 1]; int tile_off[kMaxTypesC + 1]; int T; int num_nodes;
+#if GGNN_K1C_STAMPS
+    unsigned long long* tdbg;
+#endif
+};
 
 static inline size_t align256c(size_t x) { return (x + 255) / 256 * 256; }
 
@@ -90,7 +101,11 @@ __global__ __launch_bounds__(NW * 64, 4) /* 4 waves per SIMD = 2 workgroups per 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
 
+#if GGNN_K1C_STAMPS
 #define K1C_T(K) if (tr.tdbg && lane == 0) tr.tdbg[((size_t)blockIdx.x * NW + wave) * 8 + (K)] = (K) == 0 || (K) == 7 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+#else
+#define K1C_T(K)
+#endif
     K1C_T(0)
     K1C_T(6)                  // (shader-clock twin of the start stamp; a wave has at most 3 tiles in these runs)
     int t = 0;
@@ -114,7 +129,9 @@ __global__ __launch_bounds__(NW * 64, 4) /* 4 waves per SIMD = 2 workgroups per 
     if constexpr (SPLIT) dma_wait();
     __syncthreads();                                        // the image has landed (vmcnt(0) + barrier)
     K1C_T(2)
+#if GGNN_K1C_STAMPS
     int tcount = 0;
+#endif
 
     while (idx < n_wt) {
         const int idx_n = idx + stride;
@@ -143,8 +160,10 @@ __global__ __launch_bounds__(NW * 64, 4) /* 4 waves per SIMD = 2 workgroups per 
         }
         a = an;
         idx = idx_n;
+#if GGNN_K1C_STAMPS
         if (tcount < 3) { K1C_T(3 + tcount) }
         ++tcount;
+#endif
     }
     K1C_T(7)
 }
@@ -184,7 +203,9 @@ static int launch_compact_m(const float* h, const float* W, const int* pair_node
         tr.tile_off[t + 1] = tr.tile_off[t] + (int)(((tr.row_off[t + 1] - tr.row_off[t] + 15) / 16 + R * NW - 1) / (R * NW));
     static std::atomic<unsigned long long> lds_ok{0};
     if (C::IMG_BYTES > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&msg_transform_compact_kernel<D, NW, SPLIT, FMT>, C::IMG_BYTES, lds_ok));
+#if GGNN_K1C_STAMPS
     { const char* e = getenv("GGNN_K1C_TPTR"); tr.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
+#endif
     hipLaunchKernelGGL((msg_transform_compact_kernel<D, NW, SPLIT, FMT>), dim3(tr.tile_off[tr.T]), dim3(NW * 64), C::IMG_BYTES, st, h, pair_node,
                        tr, (const float*)packed, Hc);
     GGNN_CHECK_HIP(hipGetLastError());

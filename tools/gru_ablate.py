@@ -1,5 +1,9 @@
-"""Times ops.gru alone (V=100k, D=100, nx=1) -- used with GGNN_GRU_DBG ablation bits."""
+"""Times ops.gru alone (V=100k, D=100, nx=1) -- used with GGNN_GRU_DBG ablation bits, which only a variant library has:
+    bash tools/variant_lib.sh abl ggnn_gru_fused.hip,ggnn_gru_fused_split.hip -DGGNN_GRU_ABLATE=1
+    GGNN_LIB_VARIANT=abl GGNN_GRU_DBG=1 python tools/gru_ablate.py"""
 import importlib, os, sys, torch, numpy as np
+if not os.environ.get("GGNN_LIB_VARIANT"):
+    sys.exit("tools/gru_ablate.py needs a variant library (see the docstring): set GGNN_LIB_VARIANT=abl")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
 V, D = int(os.environ.get("V", 99990)), 100

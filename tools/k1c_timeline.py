@@ -1,5 +1,9 @@
-"""Per-wave timeline of the compacted message transform (debug stamps behind GGNN_K1C_TPTR)."""
+"""Per-wave timeline of the compacted message transform (debug stamps behind GGNN_K1C_TPTR; compiled in only with -DGGNN_K1C_STAMPS=1):
+    bash tools/variant_lib.sh k1t ggnn_msg_compact.hip -DGGNN_K1C_STAMPS=1
+    GGNN_LIB_VARIANT=k1t python tools/k1c_timeline.py"""
 import importlib, os, sys, torch, numpy as np
+if not os.environ.get("GGNN_LIB_VARIANT"):
+    sys.exit("tools/k1c_timeline.py needs a variant library (see the docstring): set GGNN_LIB_VARIANT=k1t")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
 dev = "cuda:0"

@@ -3,6 +3,10 @@
 #   tools/variant_lib.sh <tag> <source.hip[,source2.hip,...]> [-DFLAG=...]      then run with GGNN_LIB_VARIANT=<tag>
 # e.g. the fused GRU with its s_memtime stamps for tools/gru_timeline.py:
 #   tools/variant_lib.sh tl ggnn_gru_fused.hip,ggnn_gru_fused_split.hip -DGGNN_GRU_STAMPS=1
+# the fused GRU with the GGNN_GRU_DBG ablation bits (tools/gru_ablate.py, tools/exp_ablate_f16.sh; the product library has none):
+#   tools/variant_lib.sh abl ggnn_gru_fused.hip,ggnn_gru_fused_split.hip -DGGNN_GRU_ABLATE=1
+# the compacted message transform with the stamps behind GGNN_K1C_TPTR (tools/k1c_timeline.py):
+#   tools/variant_lib.sh k1t ggnn_msg_compact.hip -DGGNN_K1C_STAMPS=1
 set -e
 tag=$1; srcs=$2; shift; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd); P=$ROOT/gated-graph-neural-network-samples_amd
