@@ -13,7 +13,11 @@
 // (the training path's dW = S^T dP).
 //
 // The backward pass reuses the kernel: dx = A_hat^T (dP W^T) = (A_hat^T dP) W^T, i.e. the same launch on the transposed CSR with
-// the image of W^T (ggnn_gcn_pack_weights_f32(transpose = 1)).
+// the image of W^T (ggnn_gcn_pack_weights_f32(transpose = 1)).  Its BWD instantiation (ggnn_gcn_layer_bwd_f32) goes one step
+// further and writes the dP of the layer BELOW: the epilogue applies that layer's dropout mask and the ReLU gate of its forward
+// output gate_out = dropout(relu(P)), read at the lane's own row and column quad -- the two element-wise launches
+// (ggnn_dropout_f32, ggnn_act_bwd_f32) and their [V, D] round trips between two layer launches are gone.  The gather, split, product
+// and tile walk are the forward's; BWD is a template parameter, so the forward instantiations keep their code and registers.
 //
 // Memory per layer at V = 1e5, D = 100, ~3.1 nonzeros per row: x is read ~once through L2 (each row is gathered by ~3 neighbours
 // of nearby rows), out written once, the CSR read once -- about 83 MB, against ~245 MB for the segment sum + GEMM + epilogue
@@ -31,6 +35,23 @@ using GcnImg = SplitCfg<D, kSplitBf16x3>;
 
 template <int D>
 __global__ void gcn_pack_kernel(const float* __restrict__ W, int transpose, float* __restrict__ img) {
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    if (transpose) pack_split_image<D, kSplitBf16x3>(StageValueT<D>{W, 0, 0, D}, img, first, stride);
+    else pack_split_image<D, kSplitBf16x3>(StageValue<D>{W, 0, 0, D, -1, nullptr, 0, 0, -1}, img, first, stride);
+}
+
+// Every weight image of a training step in ONE launch (2L launches of gcn_pack_kernel before): blockIdx.y = slot j of `images`,
+// slot j < L the image of W_j, slot L + (l - 1) the image of W_l^T for l >= 1 (layer 0 forms no dx).  pack_split_image writes word i
+// as a function of (i, W) alone: the images are gcn_pack_kernel's bit for bit whatever the grid.
+constexpr int kGcnTrainMaxLayers = 64;
+struct GcnPackList { const float* W[kGcnTrainMaxLayers]; };
+
+template <int D>
+__global__ __launch_bounds__(256) void gcn_train_pack_kernel(GcnPackList w, int L, float* __restrict__ images, unsigned slot_floats) {
+    const int j = blockIdx.y;
+    const bool transpose = j >= L;
+    const float* W = w.W[transpose ? j - L + 1 : j];
+    float* img = images + (size_t)j * slot_floats;
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     if (transpose) pack_split_image<D, kSplitBf16x3>(StageValueT<D>{W, 0, 0, D}, img, first, stride);
     else pack_split_image<D, kSplitBf16x3>(StageValue<D>{W, 0, 0, D, -1, nullptr, 0, 0, -1}, img, first, stride);
@@ -72,10 +93,20 @@ __device__ __forceinline__ f32x4 gcn_epilogue(f32x4 v, int row, int col, const G
     return v;
 }
 
-template <int D>
+// d v / d P of out = dropout(relu(P)) given out: ggnn_act_bwd_f32's ReLU select, term for term
+__device__ __forceinline__ f32x4 gcn_relu_gate(f32x4 v, f32x4 gate) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = gate[e] > 0.f ? v[e] : 0.f;
+    return v;
+}
+
+// BWD: x = dP of this layer, (row_ptr, col, val) = the transposed CSR, packed = the image of W^T, ep = the dropout of the layer
+// below (no bias, no ReLU), gate_out [V, D] = that layer's forward output; out = its dP.  s_out is not written.
+template <int D, bool BWD = false>
 __global__ __launch_bounds__(kGcnNW * 64, 4) /* 4 waves per SIMD = 2 workgroups per CU, <= 128 VGPRs */ void gcn_layer_kernel(
         const float* __restrict__ x, const int* __restrict__ row_ptr, const int* __restrict__ col, const float* __restrict__ val,
-        int nnz, const float* __restrict__ packed, GcnEpilogue ep, float* __restrict__ out, float* __restrict__ s_out, int V) {
+        int nnz, const float* __restrict__ packed, GcnEpilogue ep, float* __restrict__ out, float* __restrict__ s_out, int V,
+        const float* __restrict__ gate_out) {
     using S = StageCfg<D>;
     using I = GcnImg<D>;
     constexpr int NT = S::NT;
@@ -123,7 +154,7 @@ __global__ __launch_bounds__(kGcnNW * 64, 4) /* 4 waves per SIMD = 2 workgroups 
             load_frag<D>(t0, x, ok0 ? j0 : 0, kq);
             frag_fma<D>(a, ok0 ? val[k] : 0.f, t0);
         }
-        if (s_out && r < V) {
+        if (!BWD && s_out && r < V) {
             const unsigned ob = ((unsigned)r * (unsigned)D + 4u * (unsigned)kq) * 4u;
 #pragma unroll
             for (int c = 0; c < S::NC; ++c) st4_b(s_out, ob + 64u * c, a.v[c]);
@@ -138,7 +169,12 @@ __global__ __launch_bounds__(kGcnNW * 64, 4) /* 4 waves per SIMD = 2 workgroups 
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int c0 = nt * 16 + 4 * kq;
-                if (c0 < D) st4_b(out, ((unsigned)r * (unsigned)D + c0) * 4u, gcn_epilogue(acc[nt], r, c0, ep));
+                if (c0 < D) {
+                    const unsigned ob = ((unsigned)r * (unsigned)D + c0) * 4u;
+                    f32x4 v = gcn_epilogue(acc[nt], r, c0, ep);
+                    if constexpr (BWD) v = gcn_relu_gate(v, ld4_b(gate_out, ob));
+                    st4_b(out, ob, v);
+                }
             }
         }
     }
@@ -166,15 +202,25 @@ int gcn_pack(const float* W, int transpose, float* img, hipStream_t st) {
 }
 
 template <int D>
+int gcn_train_pack(const float* const* W, int L, float* images, hipStream_t st) {
+    GcnPackList w{};
+    for (int l = 0; l < L; ++l) w.W[l] = W[l];
+    const unsigned slot_floats = (unsigned)(align256g(GcnImg<D>::IMG_BYTES) / sizeof(float));
+    hipLaunchKernelGGL((gcn_train_pack_kernel<D>), dim3(16, (unsigned)(2 * L - 1)), dim3(256), 0, st, w, L, images, slot_floats);
+    GGNN_CHECK_HIP(hipGetLastError());
+    return GGNN_OK;
+}
+
+template <int D, bool BWD = false>
 int gcn_launch(const float* x, const int* row_ptr, const int* col, const float* val, int nnz, const float* img,
-               const GcnEpilogue& ep, float* out, float* s_out, int V, hipStream_t st) {
+               const GcnEpilogue& ep, float* out, float* s_out, int V, hipStream_t st, const float* gate_out = nullptr) {
     constexpr int BYTES = GcnImg<D>::IMG_BYTES;
     static std::atomic<unsigned long long> lds_ok{0};
-    if (BYTES > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gcn_layer_kernel<D>, BYTES, lds_ok));
+    if (BYTES > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gcn_layer_kernel<D, BWD>, BYTES, lds_ok));
     const long long n_tiles = (V + 15) / 16;
     const long long blocks = std::min<long long>((n_tiles + kGcnNW - 1) / kGcnNW, 2LL * num_cus());
-    hipLaunchKernelGGL((gcn_layer_kernel<D>), dim3((unsigned)blocks), dim3(kGcnNW * 64), BYTES, st, x, row_ptr, col, val, nnz, img,
-                       ep, out, s_out, V);
+    hipLaunchKernelGGL((gcn_layer_kernel<D, BWD>), dim3((unsigned)blocks), dim3(kGcnNW * 64), BYTES, st, x, row_ptr, col, val, nnz, img,
+                       ep, out, s_out, V, gate_out);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
@@ -185,6 +231,16 @@ int gcn_dispatch(const float* x, const int* row_ptr, const int* col, const float
         case 100: return gcn_launch<100>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
         case 64: return gcn_launch<64>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
         default: return gcn_launch<32>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
+    }
+}
+
+// the layer backward: out = relu_gate(dropout(A_hat^T (dP W^T)), gate_out)
+int gcn_dispatch_bwd(const float* dP, const int* row_ptr_t, const int* col_t, const float* val_t, int nnz, const float* img_T,
+                     const GcnEpilogue& ep, const float* gate_out, float* out, int V, int D, hipStream_t st) {
+    switch (D) {
+        case 100: return gcn_launch<100, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
+        case 64: return gcn_launch<64, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
+        default: return gcn_launch<32, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
     }
 }
 
@@ -232,6 +288,34 @@ extern "C" int ggnn_gcn_layer_f32(const float* x, const int32_t* row_ptr, const 
     if ((unsigned long long)V * D >= (1ULL << 30)) return fail(GGNN_E_UNSUPPORTED, "V*D must be < 2^30 (32-bit byte offsets)");
     const GcnEpilogue ep{bias, relu ? 1 : 0, row_key, row_key_base, (uint32_t)seed, (uint32_t)(seed >> 32), keep_prob};
     return gcn_dispatch(x, row_ptr, col, val, (int)nnz, img, ep, out, s_out, V, D, (hipStream_t)stream);
+}
+
+extern "C" int ggnn_gcn_layer_bwd_f32(const float* dP, const int32_t* row_ptr_t, const int32_t* col_t, const float* val_t, int64_t nnz,
+                                      const float* img_T, const float* gate_out, const int64_t* row_key, int64_t row_key_base,
+                                      uint64_t seed, float keep_prob, float* out, int V, int D, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(V >= 0 && nnz >= 0 && nnz < (1LL << 31), "bad sizes V=%d nnz=%lld", V, (long long)nnz);
+    if (!ggnn_gcn_fused_supported(D)) return fail(GGNN_E_UNSUPPORTED, "fused GCN layer supports hidden sizes 32, 64, 100 (got %d)", D);
+    GGNN_CHECK_ARG(gcn_epilogue_args(nullptr, keep_prob), "keep_prob %g outside (0, 1]", (double)keep_prob);
+    if (V == 0) return GGNN_OK;
+    GGNN_CHECK_ARG(dP && row_ptr_t && img_T && out && gate_out && (nnz == 0 || (col_t && val_t)), "null pointer");
+    GGNN_CHECK_ARG(aligned16(dP) && aligned16(img_T) && aligned16(out) && aligned16(gate_out), "pointers must be 16-byte aligned");
+    GGNN_CHECK_ARG(dP != out && gate_out != out, "out must not alias dP or gate_out");
+    if ((unsigned long long)V * D >= (1ULL << 30)) return fail(GGNN_E_UNSUPPORTED, "V*D must be < 2^30 (32-bit byte offsets)");
+    const GcnEpilogue ep{nullptr, 0, row_key, row_key_base, (uint32_t)seed, (uint32_t)(seed >> 32), keep_prob};
+    return gcn_dispatch_bwd(dP, row_ptr_t, col_t, val_t, (int)nnz, img_T, ep, gate_out, out, V, D, (hipStream_t)stream);
+}
+
+extern "C" int ggnn_gcn_train_pack_f32(const float* const* W, int num_layers, int D, float* images, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(num_layers > 0 && num_layers <= kGcnTrainMaxLayers, "layers=%d outside [1, %d]", num_layers, kGcnTrainMaxLayers);
+    if (!ggnn_gcn_fused_supported(D)) return fail(GGNN_E_UNSUPPORTED, "fused GCN layer supports hidden sizes 32, 64, 100 (got %d)", D);
+    GGNN_CHECK_ARG(W && images && aligned16(images), "null or misaligned pointer");
+    for (int l = 0; l < num_layers; ++l) GGNN_CHECK_ARG(W[l] != nullptr, "null weight pointer of layer %d", l);
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 100: return gcn_train_pack<100>(W, num_layers, images, st);
+        case 64: return gcn_train_pack<64>(W, num_layers, images, st);
+        default: return gcn_train_pack<32>(W, num_layers, images, st);
+    }
 }
 
 extern "C" int ggnn_gcn_epilogue_f32(const float* P, const float* bias, int relu, const int64_t* row_key, int64_t row_key_base,

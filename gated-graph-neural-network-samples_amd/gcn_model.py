@@ -4,7 +4,8 @@
 
 running as one fused aggregate-transform HIP launch (csrc/ggnn_gcn.hip) at hidden sizes 32 / 64 / 100, and as the composition
 weighted segment sum -> GEMM -> epilogue at the others.  Inference runs all layers behind one native call
-(ggnn_gcn_propagate_f32); training runs GCNLayerFn per layer (hand-written backward, no autograd on the kernels).
+(ggnn_gcn_propagate_f32); training runs GCNLayerFn per layer (hand-written backward, no autograd on the kernels), or with
+params['native_training'] = True the whole step as two native calls (train_native.native_gcn_train_step, csrc/ggnn_gcn_train.hip).
 The readout and loss are the fused kernels of the sparse GGNN (chem_tensorflow_gcn.py:84-93 is the same formula).
 """
 from __future__ import annotations
@@ -105,7 +106,8 @@ class SparseGCNChemModel(ChemModel):
                        'graph_state_dropout_keep_prob': 1.0,
                        })
         # (params['pack_on_device'], default False, is read with .get like the sparse model's: a key in this dict would break
-        # restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340)
+        # restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340.  So is
+        # params['native_training'], default False: the optimisation step on train_native.native_gcn_train_step)
         return params
 
     DERIVED_PLACEHOLDERS = dict(ChemModel.DERIVED_PLACEHOLDERS, adjacency_list=('gcn_graph',), adjacency_weights=('gcn_graph',))
@@ -270,6 +272,9 @@ class SparseGCNChemModel(ChemModel):
     def threaded_batches_default(self) -> bool:
         if self.params.get('pack_on_device'):
             return self.DEVICE_PACK_THREADED
+        from . import train_native
+        if train_native.gcn_model_eligible(self):
+            return False                          # the native step leaves the host slack: inline packing, as for the native GGNN step
         return super().threaded_batches_default()
 
     def device_batches(self, data: Any, order: np.ndarray, keep_prob: float):

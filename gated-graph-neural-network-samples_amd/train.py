@@ -220,6 +220,9 @@ def train_step(model, batch_data) -> torch.Tensor:
     if train_native.dense_eligible(model, batch_data):
         # the dense model with graph_resident_training == 'native': the same on the graph-resident kernels (csrc/ggnn_dense_train.hip)
         return train_native.native_dense_train_step(model, batch_data)
+    if train_native.gcn_eligible(model, batch_data):
+        # the sparse GCN with native_training: the same on the fused layer kernels (csrc/ggnn_gcn_train.hip)
+        return train_native.native_gcn_train_step(model, batch_data)
     variables =list(model.trainable_variables.values())
     for v in variables:
         v.requires_grad_(True)

@@ -12,7 +12,9 @@ handful of launches for the weight images and masks, and the optimizer's two lau
 
 The dense model (chem_tensorflow_dense.py:93-117) has the same step on csrc/ggnn_dense_train.hip (ggnn_dense_train_forward_f32 /
 ggnn_dense_train_backward_f32) when its config asks for it with graph_resident_training = 'native': dense_eligible /
-native_dense_train_step at the end of this file.
+native_dense_train_step below.  The sparse GCN (chem_tensorflow_gcn.py:62-82) has it on csrc/ggnn_gcn_train.hip
+(ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32) under native_training = True: gcn_eligible / native_gcn_train_step at
+the end of this file.
 """
 from __future__ import annotations
 
@@ -415,6 +417,149 @@ def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
             d_final.data_ptr(), A.data_ptr(), ops._ptr(nin), bwd_packed.data_ptr(), b, v, E, D, steps, gv(W),
             gv(model.weights['edge_biases']) if has_bias else None, gv(cell.gates_kernel), gv(cell.gates_bias),
             gv(cell.candidate_kernel), gv(cell.candidate_bias), ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
+
+        # ---- per-variable clip -> Adam --------------------------------------------------------------------------------------
+        opt.mark_all_active()
+        opt.clip_and_apply(p['clamp_gradient_norm'])
+    return loss.detach()
+
+
+# ---- the sparse GCN (chem_tensorflow_gcn.py:62-82) on ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32 ------------------------
+def gcn_model_eligible(model) -> bool:
+    """The part of `gcn_eligible` that depends on the model only: a GCN model that asks for the native step
+    (params['native_training'], read with .get: not a key of default_params, whose keys a reference checkpoint must match) on a GPU,
+    a hidden size with the fused layer kernels, the fused optimizer over exactly the trainable variables, nothing frozen, one-layer
+    readout MLPs, no active data-parallel context."""
+    p = getattr(model, "params", None)
+    if p is None or not p.get('native_training') or not hasattr(model, "_graph") or 'gcn_use_bias' not in p:
+        return False
+    if not torch.cuda.is_available() or torch.device(model.device).type != 'cuda' or not backward.USE_NATIVE_STEP or not p['use_graph']:
+        return False
+    L = int(p['num_timesteps'])
+    if not _lib.load().ggnn_gcn_train_supported(int(p['hidden_size'])) or L < 1 or L > 64:
+        return False
+    dist = getattr(model, "dist", None)
+    if dist is not None and dist.active:
+        return False
+    opt = model.optimizer
+    variables = list(model.trainable_variables.values())
+    if not (opt.fused and len(opt.vars) == len(variables) and all(a is b for a, b in zip(opt.vars, variables))):
+        return False
+    have = {v.data_ptr() for v in variables}
+    if any(v.data_ptr() not in have for v in model.named_variables().values()):        # (--freeze-graph-model)
+        return False
+    for task_id in p['task_ids']:
+        for kind in ('regression_gate_task%i', 'regression_transform_task%i'):
+            if len(model.weights[kind % task_id].params["weights"]) != 1:
+                return False
+    return True
+
+
+def gcn_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """True when this step of a GCN model can run on the native sequences: gcn_model_eligible, no per-launch timing, a batch with
+    nodes and graphs whose nodes are sorted by graph (the fused readout's condition), and A_hat as a GCNGraph or as the adjacency
+    feeds one is built from."""
+    if ops._timing is not None or not gcn_model_eligible(model):
+        return False
+    h0 = batch_data.get('initial_node_representation')
+    if h0 is None or not h0.is_cuda or h0.dtype != torch.float32 or h0.dim() != 2 or h0.shape[0] == 0 \
+            or h0.shape[1] != model.params['hidden_size']:
+        return False
+    if batch_data.get('graph_nodes_sorted') is not True or int(batch_data.get('num_graphs') or 0) == 0:
+        return False
+    keep = float(batch_data.get('graph_state_keep_prob', 1.0))
+    if not 0.0 < keep <= 1.0:
+        return False
+    if batch_data.get('gcn_graph') is None and (batch_data.get('adjacency_list') is None or batch_data.get('adjacency_weights') is None):
+        return False
+    return True
+
+
+def native_gcn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    """native_train_step for the sparse GCN: two C calls for the layers and every graph-model gradient, the readout + loss per task
+    between them, clip + Adam.  No torch.autograd; the dropout masks are the autograd route's (the same seeds and row keys)."""
+    lib = _lib.load()
+    p = model.params
+    opt = model.optimizer
+    model.feed(batch_data)
+    ph = model.placeholders
+    h0 = ph['initial_node_representation'].contiguous()
+    V, D = h0.shape
+    graph = model._graph()
+    if graph.num_nodes != V:
+        raise ValueError("initial_node_representation has %d rows, the graph %d nodes" % (V, graph.num_nodes))
+    Ws = model.weights['edge_weights']
+    bs = model.weights['edge_biases'] if p['gcn_use_bias'] else None
+    L = len(Ws)
+    keep = float(ph.get('graph_state_keep_prob', 1.0))
+    uid = model._node_uid() if keep < 1.0 else None
+    seeds = (ctypes.c_uint64 * L)(*[(model.dropout_seed('gcn_state', l) & 0xFFFFFFFFFFFFFFFF) if keep < 1.0 and l < L - 1 else 0
+                                    for l in range(L)])
+    st = torch.cuda.current_stream()
+    side = backward.side_stream(h0.device)
+    dev = h0.device
+
+    with torch.no_grad():
+        # ---- forward: every weight image in one launch, then the L saving layer launches ---------------------------------------
+        if getattr(model, "_native_ws", None) is None:
+            model._native_ws = _DenseWorkspace()
+        ws = model._native_ws.get(lib.ggnn_gcn_train_workspace_bytes(V, D, L), dev)
+        final_off = ctypes.c_int64(0)
+        w_arr, b_arr = _ptrs(Ws), (None if bs is None else _ptrs(bs))
+        ops._launch("gcn_train_forward[L=%d]" % L, lambda: lib.ggnn_gcn_train_forward_f32(
+            h0.data_ptr(), V, D, L, graph.row_ptr.data_ptr(), ops._ptr(graph.col), ops._ptr(graph.val), graph.nnz, w_arr, b_arr,
+            ops._ptr(uid), seeds, keep, ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
+        off = int(final_off.value)
+        final = ws[off:off + V * D * 4].view(torch.float32).view(V, D)
+        model.ops['final_node_representations'] = final
+
+        # ---- gated regression + masked loss per task (chem_tensorflow_gcn.py:84-93, chem_tensorflow.py:158-170) -----------------
+        G = int(ph['num_graphs'])
+        gnl, gptr = ph['graph_nodes_list'], ph.get('graph_ptr')
+        saved, losses = [], []
+        for internal_id, task_id in enumerate(p['task_ids']):
+            gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
+            gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
+            target = ph['target_values'][internal_id, :].contiguous()
+            mask = ph['target_mask'][internal_id, :].contiguous()
+            out, ngate, nval, stats = ops.readout_loss_fwd(final, h0, gnl, gptr, None, G, gW, gate.params["biases"][0].reshape(-1), tW,
+                                                           tr.params["biases"][0].reshape(-1), target, mask)
+            saved.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
+            num, ab, ms = stats[0], stats[1], stats[2]
+            den = ms + SMALL_NUMBER
+            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
+            model.ops['accuracy_task%i' % task_id] = ab / den
+            model.ops['loss_numerator_task%i' % task_id] = num
+            model.ops['abs_error_sum_task%i' % task_id] = ab
+            model.ops['loss_denominator_task%i' % task_id] = ms
+            losses.append(num / den * ratio)
+            model.output = out
+        model.ops['losses'] = losses
+        loss = torch.stack(losses).sum()
+        model.ops['loss'] = loss
+        dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
+
+        # ---- backward -----------------------------------------------------------------------------------------------------
+        opt._flat["g"].zero_()
+        gviews = opt.sink_targets()
+        d_final = None
+        for internal_id, task_id in enumerate(p['task_ids']):
+            gate, tr, gW, tW, ngate, nval, out, target, mask = saved[internal_id]
+            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
+            d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=dev)]).contiguous()
+            dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
+                   gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
+            d_final = ops.readout_loss_bwd(final, h0, gnl, None, G, gW, tW, ngate, nval, out, target, mask, None, d_stats,
+                                           d_last_h=d_final, grad_out=dst)[0]
+            out_keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
+            if out_keep < 1.0:                                                          # utils.py:68: the masks of the forward
+                ops.dropout(dst[0], out_keep, gate.dropout_seed(0), out=dst[0])
+                ops.dropout(dst[2], out_keep, tr.dropout_seed(0), out=dst[2])
+        gW_arr = _ptrs([gviews[w.data_ptr()] for w in Ws])
+        gb_arr = None if bs is None else _ptrs([gviews[b.data_ptr()] for b in bs])
+        ops._launch("gcn_train_backward[L=%d]" % L, lambda: lib.ggnn_gcn_train_backward_f32(
+            d_final.data_ptr(), V, D, L, graph.row_ptr_t.data_ptr(), ops._ptr(graph.col_t), ops._ptr(graph.val_t), graph.nnz,
+            ops._ptr(uid), seeds, keep, gW_arr, gb_arr, ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
 
         # ---- per-variable clip -> Adam --------------------------------------------------------------------------------------
         opt.mark_all_active()

@@ -726,6 +726,40 @@ int ggnn_gcn_propagate_f32(const float* h0, int V, int D, int num_layers, const 
                            int64_t nnz, const float* const* W, const float* const* bias, float* out, void* ws, size_t ws_bytes,
                            ggnn_stream_t stream);
 
+/* ---- sparse GCN: the optimisation step as native launch sequences (ggnn_gcn.hip, ggnn_gcn_train.hip) -----------------------------
+ * ggnn_gcn_layer_bwd_f32: the backward of one layer with the gate of the layer BELOW in its epilogue, one launch:
+ *     out = [gate_out > 0] * dropout(A_hat^T (dP W^T))      = the dP of the layer below
+ *   on the transposed CSR with the image of W^T; gate_out [V,D] is the lower layer's forward output dropout(relu(P)), the dropout is
+ *   that layer's (ggnn_dropout_f32's expression and mask for (seed, row key, column); keep_prob 1: none), the select is
+ *   ggnn_act_bwd_f32's: bit-identical to ggnn_gcn_layer_f32 + ggnn_dropout_f32 + ggnn_act_bwd_f32.  out must not alias dP or gate_out.
+ * ggnn_gcn_train_pack_f32: every weight image of a step in one launch.  W: HOST array of num_layers (<= 64) device pointers;
+ *   images: 2 num_layers - 1 slots of ggnn_gcn_image_bytes(D) rounded up to 256 bytes: slot l = the image of W_l, slot
+ *   num_layers + l - 1 = the image of W_l^T for l >= 1 -- ggnn_gcn_pack_weights_f32's images bit for bit.
+ * ggnn_gcn_train_supported: 1 for the hidden sizes with the native step (32, 64, 100).
+ * ggnn_gcn_train_forward_f32: the pack launch and num_layers saving layer launches (ReLU and dropout with seeds[l] -- HOST array --
+ *   on all but the last layer; row_key [V] int64 or NULL: the row index) into ws (ggnn_gcn_train_workspace_bytes: the images,
+ *   S_l, the layer outputs, one dP buffer per layer and the product workspace); *final_off = byte offset in ws of the final states.
+ * ggnn_gcn_train_backward_f32: d_final [V,D] = dL/d final states; per layer g_W[l] [D,D] += S_l^T dP_l and, with g_b != NULL,
+ *   g_b[l] [D] += colsum(dP_l) on side_stream (ggnn_xty_acc_f32; ggnn_colsum_f32, whose sums are the autograd route's bit for
+ *   bit, rather than the product's ones row), and dP_{l-1} by ggnn_gcn_layer_bwd_f32 on stream for l >= 1;
+ *   g_W / g_b: HOST arrays of device pointers, ADDED to.  On return stream waits for side_stream's last product (side_stream NULL:
+ *   everything on stream).  ws as the forward call left it, same (row_key, seeds, keep_prob).
+ * V == 0 is a no-op; V*D >= 2^30 and other hidden sizes return GGNN_E_UNSUPPORTED. */
+int ggnn_gcn_layer_bwd_f32(const float* dP, const int32_t* row_ptr_t, const int32_t* col_t, const float* val_t, int64_t nnz,
+                           const float* img_T, const float* gate_out, const int64_t* row_key, int64_t row_key_base, uint64_t seed,
+                           float keep_prob, float* out, int V, int D, ggnn_stream_t stream);
+int ggnn_gcn_train_pack_f32(const float* const* W, int num_layers, int D, float* images, ggnn_stream_t stream);
+int ggnn_gcn_train_supported(int D);
+size_t ggnn_gcn_train_workspace_bytes(int V, int D, int num_layers);
+int ggnn_gcn_train_forward_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col,
+                               const float* val, int64_t nnz, const float* const* W, const float* const* bias, const int64_t* row_key,
+                               const uint64_t* seeds, float keep_prob, void* ws, size_t ws_bytes, int64_t* final_off,
+                               ggnn_stream_t stream);
+int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t, const int32_t* col_t,
+                                const float* val_t, int64_t nnz, const int64_t* row_key, const uint64_t* seeds, float keep_prob,
+                                float* const* g_W, float* const* g_b, void* ws, size_t ws_bytes, ggnn_stream_t stream,
+                                ggnn_stream_t side_stream);
+
 /* ---- measurement aid (bench.py's roofline leg; not on the product path) --------------------------------------------------------
  * The dense bf16 MFMA rate the chip SUSTAINS: `launches` back-to-back launches (~16 ms each) of v_mfma_f32_16x16x32_bf16 on
  * register operands, 8 waves per CU; mode 0 all-zero operands, 1 random operands, 2 the operand pattern and planes of the 3-way

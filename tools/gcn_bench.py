@@ -15,6 +15,13 @@ packed on the host (pack_batch + gcn_csr_host + upload) and on the device (pack_
   ms_per_step         epoch time / steps;  step_ms: one training step on a resident batch
   assemble            one ggnn_gcn_assemble_batch launch: algorithmic HBM bytes, device-event time, fraction of the 8 TB/s roof
 --leg pack: only device packing of `--iters` batches (for a kernel trace).
+--leg step: one training step at the benchmark batch through torch.autograd (GCNLayerFn) and on the native sequences
+(params['native_training'], csrc/ggnn_gcn_train.hip), two models in one process on the same resident batch, `--rounds` interleaved
+rounds of `--step-iters` steps each:
+  step_ms        per arm: median and min .. max over the rounds of the device-event time per step
+  enqueue_ms     per arm: median host time per step to enqueue it (no synchronisation inside the timed loop)
+  native_faster  True only if the native arm's whole range lies below the autograd arm's
+--out FILE also writes the JSON there.
 """
 import argparse
 import json
@@ -116,15 +123,69 @@ def pack_leg(a):
     print(json.dumps({"metric": "GCN device packing", "batches": n}))
 
 
+def _step_round(model, feed, iters):
+    """(device ms per step, host enqueue ms per step) of `iters` back-to-back training steps."""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    s.record()
+    for _ in range(iters):
+        model.train_batch(feed)
+    e.record()
+    host = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters, host * 1e3 / iters
+
+
+def step_leg(a):
+    ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
+    cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
+    arms = {}
+    for name, extra in (("autograd", {}), ("native", {"native_training": True})):
+        model = ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms,
+                                             "--config": dict(cfg, **extra)})
+        np.random.seed(0)
+        feed = dict(next(iter(model.make_minibatch_iterator(model.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
+        assert ggnn_amd.train_native.gcn_eligible(model, feed) == (name == "native"), name
+        arms[name] = (model, feed)
+    V, D = arms["native"][1]["initial_node_representation"].shape
+    for model, feed in arms.values():                       # warm-up: workspaces, caching allocator, LDS attributes
+        _step_round(model, feed, 5)
+    dev = {n: [] for n in arms}
+    host = {n: [] for n in arms}
+    for _ in range(a.rounds):                               # interleaved: both arms see the same clocks and the same neighbours
+        for name, (model, feed) in arms.items():
+            d, h = _step_round(model, feed, a.step_iters)
+            dev[name].append(d); host[name].append(h)
+    out = {"metric": "sparse GCN training step, synthetic QM9", "V": int(V), "nnz": arms["native"][1]["gcn_graph"].nnz, "D": int(D),
+           "layers": 4, "rounds": a.rounds, "steps_per_round": a.step_iters}
+    for name in arms:
+        out[name] = {"step_ms_median": round(float(np.median(dev[name])), 4), "step_ms_min": round(min(dev[name]), 4),
+                     "step_ms_max": round(max(dev[name]), 4), "enqueue_ms_median": round(float(np.median(host[name])), 4),
+                     "step_ms_rounds": [round(x, 4) for x in dev[name]]}
+    out["native_faster"] = bool(out["native"]["step_ms_max"] < out["autograd"]["step_ms_min"])
+    out["speedup_median"] = round(out["autograd"]["step_ms_median"] / out["native"]["step_ms_median"], 3)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=5600)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--hidden", type=int, default=100)
-    ap.add_argument("--leg", choices=("layer", "epoch", "pack"), default="layer")
+    ap.add_argument("--leg", choices=("layer", "epoch", "pack", "step"), default="layer")
     ap.add_argument("--epoch-graphs", type=int, default=33600)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--step-iters", type=int, default=50)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "gcn_bench needs a GPU"
+    if a.leg == "step":
+        return step_leg(a)
     if a.leg != "layer":
         return (epoch_leg if a.leg == "epoch" else pack_leg)(a)
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
