@@ -50,6 +50,12 @@ SYMBOLS = {
     "ggnn_readout_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ggnn_readout_loss_fwd_f32": (c_int, [c_void_p] * 15 + [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "ggnn_readout_loss_bwd_f32": (c_int, [c_void_p] * 14 + [c_int] + [c_void_p] * 4 + [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "ggnn_readout_multi_supported": (c_int, [c_int, c_int]),
+    "ggnn_readout_multi_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ggnn_readout_multi_fwd_f32": (c_int, [c_void_p] * 5 + [POINTER(c_void_p)] * 4 + [c_void_p] * 5 +
+                                   [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    "ggnn_readout_multi_bwd_f32": (c_int, [c_void_p] * 4 + [POINTER(c_void_p)] * 2 + [c_void_p] * 7 + [c_int] + [POINTER(c_void_p)] * 4 +
+                                   [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
     "ggnn_gru_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ggnn_gru_f32": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -123,3 +123,52 @@ class _ReadoutLoss(torch.autograd.Function):
 def readout_loss(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, gate_W, gate_b, transform_W, transform_b, target, mask):
     return _ReadoutLoss.apply(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, gate_W, gate_b, transform_W, transform_b,
                               target, mask)
+
+
+class _ReadoutLossMulti(torch.autograd.Function):
+    """_ReadoutLoss for all K tasks as ONE differentiable unit on ggnn_readout_multi_{fwd,bwd}_f32: the node states are read once
+    by the forward and once by the backward whatever K is.  Returns (out [K,G], sum 0.5 diff^2 [K], sum |diff| [K], sum mask [K])."""
+
+    @staticmethod
+    def forward(ctx, last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, targets, masks, K, *weights):
+        last_h = last_h.contiguous()
+        gWs = [w.reshape(-1).contiguous() for w in weights[0:K]]
+        gbs = [b.reshape(-1) for b in weights[K:2 * K]]
+        tWs = [w.reshape(-1).contiguous() for w in weights[2 * K:3 * K]]
+        tbs = [b.reshape(-1) for b in weights[3 * K:4 * K]]
+        out, node_gv, stats = ops.readout_multi_fwd(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, gWs, gbs, tWs, tbs,
+                                                    targets, masks)
+        ctx.save_for_backward(last_h, h0, graph_nodes_list, node_mask, node_gv, out, targets, masks, *gWs, *tWs)
+        ctx.num_graphs, ctx.K = int(num_graphs), K
+        ctx.shapes = [w.shape for w in weights]
+        num, ab, ms = stats[:, 0], stats[:, 1], stats[:, 2]
+        ctx.mark_non_differentiable(ms)
+        return out, num, ab, ms
+
+    @staticmethod
+    def backward(ctx, d_out, d_num, d_abs, d_ms):
+        K = ctx.K
+        last_h, h0, gnl, node_mask, node_gv, out, targets, masks = ctx.saved_tensors[:8]
+        gWs, tWs = ctx.saved_tensors[8:8 + K], ctx.saved_tensors[8 + K:8 + 2 * K]
+        d_stats = None
+        if d_num is not None or d_abs is not None:
+            zero = torch.zeros(K, dtype=torch.float32, device=last_h.device)
+            d_stats = torch.stack([zero if d_num is None else d_num.reshape(K), zero if d_abs is None else d_abs.reshape(K)], dim=1).contiguous()
+        d_h, dgW, dgb, dtW, dtb = ops.readout_multi_bwd(last_h, h0, gnl, node_mask, ctx.num_graphs, gWs, tWs, node_gv, out, targets, masks,
+                                                        None if d_out is None else d_out.contiguous(), d_stats)
+        grads = [dgW[k] for k in range(K)] + [dgb[k] for k in range(K)] + [dtW[k] for k in range(K)] + [dtb[k] for k in range(K)]
+        return (d_h, None, None, None, None, None, None, None, None) + tuple(g.reshape(s) for g, s in zip(grads, ctx.shapes))
+
+
+def readout_loss_multi(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, gate_Ws, gate_bs, transform_Ws, transform_bs,
+                       targets, masks):
+    """gated_regression + masked loss sums of every task: -> (out [K,G], num [K], ab [K], ms [K]), differentiable in last_h and every
+    weight and bias.  targets, masks [K,G].  One pass over the node states where ops.readout_multi_supported(D, K); any other
+    (D, K) -- K > 16, a width that is no multiple of 4 -- computes the same results by the per-task loop over readout_loss."""
+    K = len(gate_Ws)
+    if ops.readout_multi_supported(last_h.shape[-1], K):
+        return _ReadoutLossMulti.apply(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, targets.contiguous(),
+                                       masks.contiguous(), K, *gate_Ws, *gate_bs, *transform_Ws, *transform_bs)
+    per_task = [readout_loss(last_h, h0, graph_nodes_list, graph_ptr, node_mask, num_graphs, gate_Ws[k], gate_bs[k], transform_Ws[k],
+                             transform_bs[k], targets[k].contiguous(), masks[k].contiguous()) for k in range(K)]
+    return tuple(torch.stack([r[i] for r in per_task]) for i in range(4))

@@ -195,6 +195,8 @@ class ChemModel(object):
         self.ops['final_node_representations'] = final
         self.ops['losses'] = []
         fused_readout = getattr(self, 'gated_regression_with_loss', None)
+        if self._forward_tasks_multi(final):
+            return self.ops['loss']
         for (internal_id, task_id) in enumerate(self.params['task_ids']):
             gate_mlp = self.weights['regression_gate_task%i' % task_id]
             transform_mlp = self.weights['regression_transform_task%i' % task_id]
@@ -221,6 +223,45 @@ class ChemModel(object):
             self.ops['loss_denominator_task%i' % task_id] = mask_sum
         self.ops['loss'] = torch.stack(self.ops['losses']).sum()                              # :170
         return self.ops['loss']
+
+    def task_ratio_factors(self, device) -> torch.Tensor:
+        """[K] float32: 1 / task_sample_ratios[task_id] per entry of task_ids (chem_tensorflow.py:168: looked up with the int id,
+        1 where absent), cached on the device."""
+        vals = tuple(1.0 / (self.params['task_sample_ratios'].get(t) or 1.0) for t in self.params['task_ids'])
+        cached = getattr(self, '_task_ratio_factors', None)
+        if cached is None or cached[0] != (vals, str(device)):
+            self._task_ratio_factors = cached = ((vals, str(device)), torch.tensor(vals, dtype=torch.float32, device=device))
+        return cached[1]
+
+    def publish_task_stats(self, out: torch.Tensor, num: torch.Tensor, ab: torch.Tensor, ms: torch.Tensor) -> torch.Tensor:
+        """The per-task entries of self.ops (:161-170) from the multi-task readout's out [K,G] and masked sums [K] each, by a
+        constant number of torch ops: the entries are views of the K-vectors.  Returns the loss."""
+        task_ids = self.params['task_ids']
+        den = ms + SMALL_NUMBER                                                               # :163
+        accuracy = ab / den                                                                   # :165
+        task_losses = num / den * self.task_ratio_factors(num.device)                         # :166, :168
+        for name, vec in (('accuracy_task%i', accuracy), ('loss_numerator_task%i', num), ('abs_error_sum_task%i', ab),
+                          ('loss_denominator_task%i', ms)):
+            for entry, task_id in zip(vec.unbind(0), task_ids):
+                self.ops[name % task_id] = entry
+        self.ops['losses'] = list(task_losses.unbind(0))
+        self.ops['loss'] = task_losses.sum()                                                  # :170
+        self.output = out[len(task_ids) - 1]                                                  # (the per-task loop leaves the last task's)
+        return self.ops['loss']
+
+    def _forward_tasks_multi(self, final) -> bool:
+        """params['multitask_readout'] (default False; read with .get: not a key of default_params, whose keys a reference checkpoint
+        must match): the gated regression and masked loss of EVERY task in one fused pass (autograd.readout_loss_multi) instead of
+        one per entry of task_ids.  False -- and the per-task loop runs -- for one task, and wherever the model's
+        gated_regression_with_loss_multi says the multi-task kernels do not apply (it returns None)."""
+        multi = getattr(self, 'gated_regression_with_loss_multi', None)
+        if not self.params.get('multitask_readout') or multi is None or len(self.params['task_ids']) < 2:
+            return False
+        fused = multi(final)
+        if fused is None:
+            return False
+        self.publish_task_stats(*fused)
+        return True
 
     def feed(self, batch_data: Dict[str, Any]) -> None:
         """The reference's feed_dict: every placeholder the batch carries is replaced.  Values DERIVED from a fed

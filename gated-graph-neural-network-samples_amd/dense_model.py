@@ -278,6 +278,26 @@ class DenseGGNNChemModel(ChemModel):
         self.output = out
         return out, num, ab, ms
 
+    def gated_regression_with_loss_multi(self, last_h):
+        """gated_regression_with_loss for every entry of task_ids in one pass over the [b*v, h] states (autograd.readout_loss_multi;
+        params['multitask_readout']): -> (out [K,b], num [K], ab [K], ms [K]), or None when the multi-task kernels do not apply."""
+        from .autograd import readout_loss_multi
+        ph = self.placeholders
+        task_ids = self.params['task_ids']
+        K, h_dim = len(task_ids), self.params['hidden_size']
+        gates = [self.weights['regression_gate_task%i' % t] for t in task_ids]
+        transforms = [self.weights['regression_transform_task%i' % t] for t in task_ids]
+        if not last_h.is_cuda or K < 2 or not ops.readout_multi_supported(h_dim, K) \
+                or any(len(m.params["weights"]) != 1 for m in gates + transforms):
+            return None
+        b, v = last_h.shape[0], int(ph['num_vertices'])
+        gnl, gptr = self._readout_rows(b, v, last_h.device)
+        return readout_loss_multi(last_h.reshape(-1, h_dim), ph['initial_node_representation'].reshape(-1, h_dim).contiguous(),
+                                  gnl, gptr, ph['node_mask'].reshape(-1).contiguous(), b,
+                                  [m.dropped_weight(0) for m in gates], [m.params["biases"][0] for m in gates],
+                                  [m.dropped_weight(0) for m in transforms], [m.params["biases"][0] for m in transforms],
+                                  ph['target_values'], ph['target_mask'])
+
     def gated_regression(self, last_h, regression_gate, regression_transform):
         """chem_tensorflow_dense.py:119-129."""
         ph = self.placeholders

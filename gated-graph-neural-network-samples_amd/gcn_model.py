@@ -190,6 +190,7 @@ class SparseGCNChemModel(ChemModel):
 
     # chem_tensorflow_gcn.py:84-93 is the sparse GGNN's readout formula: the same fused readout / loss kernels
     gated_regression_with_loss = SparseGGNNChemModel.gated_regression_with_loss
+    gated_regression_with_loss_multi = SparseGGNNChemModel.gated_regression_with_loss_multi
     gated_regression = SparseGGNNChemModel.gated_regression
     _graph_nodes_sorted = SparseGGNNChemModel._graph_nodes_sorted
     _pad_blocks = staticmethod(SparseGGNNChemModel._pad_blocks)

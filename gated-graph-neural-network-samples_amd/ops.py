@@ -1354,6 +1354,92 @@ def readout_loss_bwd(last_h, h0, graph_nodes_list, node_mask, num_graphs, gate_W
     return d_last_h, dgW, dgb, dtW, dtb
 
 
+# ---- multi-task readout: every entry of task_ids in one pass over the node states (ggnn_readout_multi_*) ------------
+def readout_multi_supported(D: int, K: int) -> bool:
+    """True when ggnn_readout_multi_{fwd,bwd}_f32 take kernel width D with K tasks (multiples of 4 up to 256, 1 <= K <= 16)."""
+    return bool(_lib.load().ggnn_readout_multi_supported(int(D), int(K)))
+
+
+def _task_ptrs(tensors: Sequence[torch.Tensor], numel: int, name: str):
+    for t in tensors:
+        _req(t, torch.float32, name)
+        if t.numel() != numel:
+            raise ValueError("%s: every task's tensor must have %d elements" % (name, numel))
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def readout_multi_fwd(last_h: torch.Tensor, h0: torch.Tensor, graph_nodes_list: torch.Tensor, graph_ptr: Optional[torch.Tensor],
+                      node_mask: Optional[torch.Tensor], num_graphs: int, gate_Ws: Sequence[torch.Tensor],
+                      gate_bs: Sequence[torch.Tensor], transform_Ws: Sequence[torch.Tensor], transform_bs: Sequence[torch.Tensor],
+                      targets: Optional[torch.Tensor], masks: Optional[torch.Tensor]):
+    """readout_loss_fwd for K tasks in one pass: gate_Ws[k] [2D], gate_bs[k] [1], transform_Ws[k] [D], transform_bs[k] [1] (separate
+    tensors per task), targets / masks [K,G] -> (out [K,G], node_gv [V,2K] = per node (gate of every task | value of every task),
+    stats [K,3] = per task (sum 0.5 diff^2, sum |diff|, sum mask), or None without targets).  Deterministic; graph_nodes_list sorted."""
+    lib = _lib.load()
+    _req(last_h, torch.float32, "last_h"); _req(h0, torch.float32, "h0"); _req(graph_nodes_list, torch.int32, "graph_nodes_list")
+    V, D = last_h.shape
+    G, K = int(num_graphs), len(gate_Ws)
+    if not (K == len(gate_bs) == len(transform_Ws) == len(transform_bs)) or K < 1:
+        raise ValueError("one gate_W, gate_b, transform_W and transform_b per task")
+    if h0.shape != last_h.shape:
+        raise ValueError("h0 must have the shape of last_h")
+    dev = last_h.device
+    for n, t in (("targets", targets), ("masks", masks)):
+        if t is not None:
+            _req(t, torch.float32, n)
+            if tuple(t.shape) != (K, G):
+                raise ValueError("%s must be [K, G] = [%d, %d]" % (n, K, G))
+    gW, gb = _task_ptrs(gate_Ws, 2 * D, "gate_W"), _task_ptrs(gate_bs, 1, "gate_b")
+    tW, tb = _task_ptrs(transform_Ws, D, "transform_W"), _task_ptrs(transform_bs, 1, "transform_b")
+    out = torch.empty(K, G, dtype=torch.float32, device=dev)
+    node_gv = torch.empty(max(V, 1), 2 * K, dtype=torch.float32, device=dev)
+    stats = torch.empty(K, 3, dtype=torch.float32, device=dev) if targets is not None else None
+    ws_bytes = lib.ggnn_readout_multi_workspace_bytes(V, D, K, G)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _launch("readout_multi_fwd[K=%d]" % K, lambda: lib.ggnn_readout_multi_fwd_f32(
+        _ptr(last_h), _ptr(h0), _ptr(graph_nodes_list), _ptr(graph_ptr), _ptr(node_mask), gW, gb, tW, tb, _ptr(targets), _ptr(masks),
+        _ptr(out), _ptr(node_gv), _ptr(stats), _ptr(ws), ws_bytes, V, D, K, G, _stream()))
+    return out, node_gv, stats
+
+
+def readout_multi_bwd(last_h, h0, graph_nodes_list, node_mask, num_graphs, gate_Ws, transform_Ws, node_gv, out, targets, masks,
+                      d_out: Optional[torch.Tensor], d_stats: Optional[torch.Tensor], d_last_h: Optional[torch.Tensor] = None,
+                      grad_out: Optional[Sequence[Sequence[torch.Tensor]]] = None):
+    """Backward of readout_multi_fwd: d_out [K,G] or None, d_stats [K,2] or None -> (d_last_h [V,D], d_gate_W [K,2D], d_gate_b [K],
+    d_transform_W [K,D], d_transform_b [K]).  d_last_h given: the gradient is ADDED to it.
+    grad_out: four sequences of K contiguous float32 buffers (2D, 1, D, 1 elements: the optimizer's flat gradient views) that
+    receive the weight gradients instead; they are returned in place of the stacked tensors."""
+    lib = _lib.load()
+    V, D = last_h.shape
+    G, K = int(num_graphs), len(gate_Ws)
+    dev = last_h.device
+    accumulate = d_last_h is not None
+    if d_last_h is None:
+        d_last_h = torch.empty_like(last_h) if V and G else torch.zeros_like(last_h)
+    for n, t, shape in (("d_out", d_out, (K, G)), ("d_stats", d_stats, (K, 2))):
+        if t is not None:
+            _req(t, torch.float32, n)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %r" % (n, shape))
+    if grad_out is not None:
+        res = tuple(list(g) for g in grad_out)
+        if len(res) != 4 or any(len(g) != K for g in res):
+            raise ValueError("grad_out: four sequences of K buffers")
+        dst = [_task_ptrs(g, n, "grad_out") for g, n in zip(res, (2 * D, 1, D, 1))]
+    else:
+        res = (torch.empty(K, 2 * D, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.float32, device=dev),
+               torch.empty(K, D, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.float32, device=dev))
+        dst = [(ctypes.c_void_p * K)(*[t.data_ptr() + k * t.stride(0) * 4 for k in range(K)]) for t in res]
+    gW, tW = _task_ptrs(gate_Ws, 2 * D, "gate_W"), _task_ptrs(transform_Ws, D, "transform_W")
+    ws_bytes = lib.ggnn_readout_multi_workspace_bytes(V, D, K, G)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _launch("readout_multi_bwd[K=%d]" % K, lambda: lib.ggnn_readout_multi_bwd_f32(
+        _ptr(last_h), _ptr(h0), _ptr(graph_nodes_list), _ptr(node_mask), gW, tW, _ptr(node_gv), _ptr(out), _ptr(targets), _ptr(masks),
+        _ptr(d_out), _ptr(d_stats), _ptr(d_last_h), 1 if accumulate else 0, dst[0], dst[1], dst[2], dst[3], _ptr(ws), ws_bytes,
+        V, D, K, G, _stream()))
+    return (d_last_h,) + tuple(res)
+
+
 # ---- the remaining switches of the same function: attention, RNN cell, cudnn-compatible GRU cell ------------------
 def gather_segment_sum_attn(H: torch.Tensor, h: torch.Tensor, index: MessageIndex, type_factors: torch.Tensor,
                             num_incoming_edges_per_type: Optional[torch.Tensor], edge_biases: Optional[torch.Tensor],

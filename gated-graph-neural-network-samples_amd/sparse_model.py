@@ -446,6 +446,34 @@ class SparseGGNNChemModel(ChemModel):
         self.output = out
         return out, num, ab, ms
 
+    def gated_regression_with_loss_multi(self, last_h):
+        """gated_regression_with_loss for every entry of task_ids in one pass over the node states (autograd.readout_loss_multi;
+        params['multitask_readout']): -> (out [K,G], num [K], ab [K], ms [K]), or None when the multi-task kernels do not apply
+        (then the per-task loop runs)."""
+        from .autograd import readout_loss_multi
+        task_ids = self.params['task_ids']
+        K = len(task_ids)
+        D, Dk = self.params['hidden_size'], self._kw
+        if not last_h.is_cuda or K < 2 or not ops.readout_multi_supported(Dk, K) or not self._graph_nodes_sorted():
+            return None
+        gates = [self.weights['regression_gate_task%i' % t] for t in task_ids]
+        transforms = [self.weights['regression_transform_task%i' % t] for t in task_ids]
+        if any(len(m.params["weights"]) != 1 for m in gates + transforms):
+            return None
+        ph = self.placeholders
+        h0 = ph['initial_node_representation']
+        gWs = [m.dropped_weight(0) for m in gates]                                               # utils.py:68 dropout on W, per task
+        tWs = [m.dropped_weight(0) for m in transforms]
+        if Dk != D:                                                                              # zero-padded width, as above
+            import torch.nn.functional as F
+            last_h = F.pad(last_h, (0, Dk - D))
+            h0 = h0 if h0.shape[1] == Dk else F.pad(h0, (0, Dk - h0.shape[1]))
+            gWs = [self._pad_blocks(w.reshape(-1), D, Dk) for w in gWs]
+            tWs = [self._pad_blocks(w.reshape(-1), D, Dk) for w in tWs]
+        return readout_loss_multi(last_h, h0.contiguous(), ph['graph_nodes_list'], ph.get('graph_ptr'), None, ph['num_graphs'],
+                                  gWs, [m.params["biases"][0] for m in gates], tWs, [m.params["biases"][0] for m in transforms],
+                                  ph['target_values'], ph['target_mask'])
+
     def gated_regression(self, last_h, regression_gate, regression_transform):
         """chem_tensorflow_sparse.py:220-231."""
         from .autograd import segment_sum_rows

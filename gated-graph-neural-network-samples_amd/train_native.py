@@ -7,7 +7,8 @@ train.train_step takes this path when the model is the default one (GRU cell, no
 hidden size with the gather-fused kernels, at most two residual inputs per layer, every graph variable trainable); everything
 else keeps the autograd path (backward.PropagationStepFn, variants.py), which is also what this one is tested against.
 
-Per step the host makes two C calls for the propagation, one ops call per task for the readout forward and one for its backward, a
+Per step the host makes two C calls for the propagation, one ops call per task for the readout forward and one for its backward
+(params['multitask_readout']: one of each for all tasks), a
 handful of launches for the weight images and masks, and the optimizer's two launches: ~1 ms of host time instead of ~4.4 ms.
 
 The dense model (chem_tensorflow_dense.py:93-117) has the same step on csrc/ggnn_dense_train.hip (ggnn_dense_train_forward_f32 /
@@ -40,6 +41,98 @@ def _ptrs(tensors):
 
 def _i32(xs):
     return (ctypes.c_int32 * max(len(xs), 1))(*[int(x) for x in xs])
+
+
+# ---- the readout + loss of a native step: per task (one forward and one backward ops call each), or all tasks at once -------------
+def _readout_per_task_forward(model, final, h0, gnl, gptr, node_mask, G: int):
+    """Gated regression + masked loss per task (chem_tensorflow_sparse.py:220-231 / chem_tensorflow_dense.py:119-129,
+    chem_tensorflow.py:158-170); fills model.ops / model.output.  -> (what the backward needs, the loss, the [K] mask counts)."""
+    p, ph = model.params, model.placeholders
+    per_task, losses = [], []
+    for internal_id, task_id in enumerate(p['task_ids']):
+        gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
+        gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
+        target = ph['target_values'][internal_id, :].contiguous()
+        mask = ph['target_mask'][internal_id, :].contiguous()
+        out, ngate, nval, stats = ops.readout_loss_fwd(final, h0, gnl, gptr, node_mask, G, gW, gate.params["biases"][0].reshape(-1), tW,
+                                                       tr.params["biases"][0].reshape(-1), target, mask)
+        per_task.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
+        num, ab, ms = stats[0], stats[1], stats[2]
+        den = ms + SMALL_NUMBER
+        ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
+        model.ops['accuracy_task%i' % task_id] = ab / den
+        model.ops['loss_numerator_task%i' % task_id] = num
+        model.ops['abs_error_sum_task%i' % task_id] = ab
+        model.ops['loss_denominator_task%i' % task_id] = ms
+        losses.append(num / den * ratio)
+        model.output = out
+    model.ops['losses'] = losses
+    loss = torch.stack(losses).sum()
+    model.ops['loss'] = loss
+    dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
+    return (per_task, final, h0, gnl, node_mask, G), loss, dens
+
+
+def _readout_per_task_backward(model, saved, dens, gviews):
+    """d loss / d stats[0] = ratio / (dens + eps) per task, the weight gradients straight into the optimizer's flat gradient views,
+    d_final accumulated over the tasks.  -> d_final [V,D]."""
+    per_task, final, h0, gnl, node_mask, G = saved
+    p, ph = model.params, model.placeholders
+    d_final = None
+    for internal_id, task_id in enumerate(p['task_ids']):
+        gate, tr, gW, tW, ngate, nval, out, target, mask = per_task[internal_id]
+        ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
+        d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=final.device)]).contiguous()
+        dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
+               gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
+        d_final = ops.readout_loss_bwd(final, h0, gnl, node_mask, G, gW, tW, ngate, nval, out, target, mask, None, d_stats,
+                                       d_last_h=d_final, grad_out=dst)[0]
+        keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
+        if keep < 1.0:                                                              # utils.py:68: the masks of the forward
+            ops.dropout(dst[0], keep, gate.dropout_seed(0), out=dst[0])
+            ops.dropout(dst[2], keep, tr.dropout_seed(0), out=dst[2])
+    return d_final
+
+
+# ---- params['multitask_readout']: the readout of EVERY task in one forward and one backward call (ops.readout_multi_*) ------------
+def _multitask_readout(model, width: int) -> bool:
+    """The step's readout runs on the multi-task kernels: the key is set (read with .get: not a key of default_params), two or
+    more tasks, and kernels for (width, K); anything else keeps the per-task loop."""
+    p = model.params
+    K = len(p['task_ids'])
+    return bool(p.get('multitask_readout')) and K >= 2 and ops.readout_multi_supported(width, K)
+
+
+def _readout_multi_forward(model, final, h0, gnl, gptr, node_mask, G: int):
+    """One forward call for all tasks; model.ops' per-task entries become views of the [K,3] stats (ChemModel.publish_task_stats).
+    -> (what the backward needs, its last entry the [K,3] stats; the loss; a copy of the [K] mask counts)."""
+    p, ph = model.params, model.placeholders
+    gates = [model.weights['regression_gate_task%i' % t] for t in p['task_ids']]
+    trs = [model.weights['regression_transform_task%i' % t] for t in p['task_ids']]
+    gWs = [m.dropped_weight(0).reshape(-1).contiguous() for m in gates]                          # utils.py:68, one mask per task
+    tWs = [m.dropped_weight(0).reshape(-1).contiguous() for m in trs]
+    targets, masks = ph['target_values'].contiguous(), ph['target_mask'].contiguous()
+    out, node_gv, stats = ops.readout_multi_fwd(final, h0, gnl, gptr, node_mask, G, gWs, [m.params["biases"][0].reshape(-1) for m in gates],
+                                                tWs, [m.params["biases"][0].reshape(-1) for m in trs], targets, masks)
+    loss = model.publish_task_stats(out, stats[:, 0], stats[:, 1], stats[:, 2])
+    return (gates, trs, gWs, tWs, node_gv, out, targets, masks, final, h0, gnl, node_mask, G, stats), loss, stats[:, 2].clone()
+
+
+def _readout_multi_backward(model, saved, dens, gviews):
+    """One backward call for all tasks: d loss / d stats[k,0] = ratio_k / (dens_k + eps), the weight gradients straight into the
+    optimizer's flat gradient views (then the forward's weight-dropout masks, per task).  -> d_final [V,D]."""
+    gates, trs, gWs, tWs, node_gv, out, targets, masks, final, h0, gnl, node_mask, G, _stats = saved
+    d_num = model.task_ratio_factors(dens.device) / (dens + SMALL_NUMBER)
+    d_stats = torch.stack([d_num, torch.zeros_like(d_num)], dim=1).contiguous()
+    dst = ([gviews[m.params["weights"][0].data_ptr()] for m in gates], [gviews[m.params["biases"][0].data_ptr()] for m in gates],
+           [gviews[m.params["weights"][0].data_ptr()] for m in trs], [gviews[m.params["biases"][0].data_ptr()] for m in trs])
+    d_final = ops.readout_multi_bwd(final, h0, gnl, node_mask, G, gWs, tWs, node_gv, out, targets, masks, None, d_stats, grad_out=dst)[0]
+    keep = float(model.placeholders.get('out_layer_dropout_keep_prob', 1.0))
+    if keep < 1.0:                                                                           # utils.py:68: the masks of the forward
+        for gate, tr, dgW, dtW in zip(gates, trs, dst[0], dst[2]):
+            ops.dropout(dgW, keep, gate.dropout_seed(0), out=dgW)
+            ops.dropout(dtW, keep, tr.dropout_seed(0), out=dtW)
+    return d_final
 
 
 def model_eligible(model) -> bool:
@@ -196,53 +289,24 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         # ---- gated regression + masked loss per task (:220-231, chem_tensorflow.py:158-170) ---------------------------------
         G = int(ph['num_graphs'])
         gnl, gptr = ph['graph_nodes_list'], ph.get('graph_ptr')
-        saved, losses = [], []
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
-            gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
-            target = ph['target_values'][internal_id, :].contiguous()
-            mask = ph['target_mask'][internal_id, :].contiguous()
-            out, ngate, nval, stats = ops.readout_loss_fwd(final, h0, gnl, gptr, None, G, gW, gate.params["biases"][0].reshape(-1), tW,
-                                                           tr.params["biases"][0].reshape(-1), target, mask)
-            saved.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
-            num, ab, ms = stats[0], stats[1], stats[2]
-            den = ms + SMALL_NUMBER
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
-            model.ops['accuracy_task%i' % task_id] = ab / den
-            model.ops['loss_numerator_task%i' % task_id] = num
-            model.ops['abs_error_sum_task%i' % task_id] = ab
-            model.ops['loss_denominator_task%i' % task_id] = ms
-            losses.append(num / den * ratio)
-            model.output = out
-        model.ops['losses'] = losses
-        loss = torch.stack(losses).sum()
-        model.ops['loss'] = loss
+        multi = _multitask_readout(model, D)
+        saved, loss, dens = (_readout_multi_forward if multi else _readout_per_task_forward)(model, final, h0, gnl, gptr, None, G)
 
         # data parallelism: the loss is normalised by the mask count of the WHOLE step (parallel.DataParallelContext.global_loss)
         dist = getattr(model, "dist", None)
         sharded = dist is not None and dist.active
-        dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
         if sharded:
             dist.all_reduce_sum_(dens)
-            loss = torch.stack([model.ops['loss_numerator_task%i' % t] / (dens[i] + SMALL_NUMBER) *
-                                (1.0 / (p['task_sample_ratios'].get(t) or 1.0)) for i, t in enumerate(p['task_ids'])]).sum()
+            if multi:
+                loss = (saved[-1][:, 0] / (dens + SMALL_NUMBER) * model.task_ratio_factors(dev)).sum()
+            else:
+                loss = torch.stack([model.ops['loss_numerator_task%i' % t] / (dens[i] + SMALL_NUMBER) *
+                                    (1.0 / (p['task_sample_ratios'].get(t) or 1.0)) for i, t in enumerate(p['task_ids'])]).sum()
 
         # ---- backward -----------------------------------------------------------------------------------------------------
         opt._flat["g"].zero_()
         gviews = opt.sink_targets()
-        d_final = None
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr, gW, tW, ngate, nval, out, target, mask = saved[internal_id]
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
-            d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=dev)]).contiguous()
-            dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
-                   gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
-            d_final = ops.readout_loss_bwd(final, h0, gnl, None, G, gW, tW, ngate, nval, out, target, mask, None, d_stats,
-                                           d_last_h=d_final, grad_out=dst)[0]
-            keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
-            if keep < 1.0:                                                              # utils.py:68: the masks of the forward
-                ops.dropout(dst[0], keep, gate.dropout_seed(0), out=dst[0])
-                ops.dropout(dst[2], keep, tr.dropout_seed(0), out=dst[2])
+        d_final = (_readout_multi_backward if multi else _readout_per_task_backward)(model, saved, dens, gviews)
         gv = lambda t: gviews[t.data_ptr()]
         check(lib.ggnn_sparse_train_backward_f32(
             h0.data_ptr(), V, D, T, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
@@ -373,45 +437,13 @@ def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         h0_rows = h0.view(b * v, D)
         gnl, gptr = model._readout_rows(b, v, dev)
         node_mask = ph['node_mask'].reshape(-1).contiguous()
-        saved, losses = [], []
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
-            gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
-            target = ph['target_values'][internal_id, :].contiguous()
-            mask = ph['target_mask'][internal_id, :].contiguous()
-            out, ngate, nval, stats = ops.readout_loss_fwd(final, h0_rows, gnl, gptr, node_mask, b, gW, gate.params["biases"][0].reshape(-1),
-                                                           tW, tr.params["biases"][0].reshape(-1), target, mask)
-            saved.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
-            num, ab, ms = stats[0], stats[1], stats[2]
-            den = ms + SMALL_NUMBER
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
-            model.ops['accuracy_task%i' % task_id] = ab / den
-            model.ops['loss_numerator_task%i' % task_id] = num
-            model.ops['abs_error_sum_task%i' % task_id] = ab
-            model.ops['loss_denominator_task%i' % task_id] = ms
-            losses.append(num / den * ratio)
-            model.output = out
-        model.ops['losses'] = losses
-        loss = torch.stack(losses).sum()
-        model.ops['loss'] = loss
-        dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
+        multi = _multitask_readout(model, D)
+        saved, loss, dens = (_readout_multi_forward if multi else _readout_per_task_forward)(model, final, h0_rows, gnl, gptr, node_mask, b)
 
         # ---- backward -----------------------------------------------------------------------------------------------------
         opt._flat["g"].zero_()
         gviews = opt.sink_targets()
-        d_final = None
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr, gW, tW, ngate, nval, out, target, mask = saved[internal_id]
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
-            d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=dev)]).contiguous()
-            dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
-                   gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
-            d_final = ops.readout_loss_bwd(final, h0_rows, gnl, node_mask, b, gW, tW, ngate, nval, out, target, mask, None, d_stats,
-                                           d_last_h=d_final, grad_out=dst)[0]
-            keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
-            if keep < 1.0:                                                              # utils.py:68: the masks of the forward
-                ops.dropout(dst[0], keep, gate.dropout_seed(0), out=dst[0])
-                ops.dropout(dst[2], keep, tr.dropout_seed(0), out=dst[2])
+        d_final = (_readout_multi_backward if multi else _readout_per_task_backward)(model, saved, dens, gviews)
         gv = lambda t: gviews[t.data_ptr()].data_ptr()
         ops._launch("dense_train_backward[steps=%d]" % steps, lambda: lib.ggnn_dense_train_backward_f32(
             d_final.data_ptr(), A.data_ptr(), ops._ptr(nin), bwd_packed.data_ptr(), b, v, E, D, steps, gv(W),
@@ -516,45 +548,13 @@ def native_gcn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         # ---- gated regression + masked loss per task (chem_tensorflow_gcn.py:84-93, chem_tensorflow.py:158-170) -----------------
         G = int(ph['num_graphs'])
         gnl, gptr = ph['graph_nodes_list'], ph.get('graph_ptr')
-        saved, losses = [], []
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr = model.weights['regression_gate_task%i' % task_id], model.weights['regression_transform_task%i' % task_id]
-            gW, tW = gate.dropped_weight(0).reshape(-1).contiguous(), tr.dropped_weight(0).reshape(-1).contiguous()    # utils.py:68
-            target = ph['target_values'][internal_id, :].contiguous()
-            mask = ph['target_mask'][internal_id, :].contiguous()
-            out, ngate, nval, stats = ops.readout_loss_fwd(final, h0, gnl, gptr, None, G, gW, gate.params["biases"][0].reshape(-1), tW,
-                                                           tr.params["biases"][0].reshape(-1), target, mask)
-            saved.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
-            num, ab, ms = stats[0], stats[1], stats[2]
-            den = ms + SMALL_NUMBER
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
-            model.ops['accuracy_task%i' % task_id] = ab / den
-            model.ops['loss_numerator_task%i' % task_id] = num
-            model.ops['abs_error_sum_task%i' % task_id] = ab
-            model.ops['loss_denominator_task%i' % task_id] = ms
-            losses.append(num / den * ratio)
-            model.output = out
-        model.ops['losses'] = losses
-        loss = torch.stack(losses).sum()
-        model.ops['loss'] = loss
-        dens = torch.stack([model.ops['loss_denominator_task%i' % t] for t in p['task_ids']]).to(torch.float32)
+        multi = _multitask_readout(model, D)
+        saved, loss, dens = (_readout_multi_forward if multi else _readout_per_task_forward)(model, final, h0, gnl, gptr, None, G)
 
         # ---- backward -----------------------------------------------------------------------------------------------------
         opt._flat["g"].zero_()
         gviews = opt.sink_targets()
-        d_final = None
-        for internal_id, task_id in enumerate(p['task_ids']):
-            gate, tr, gW, tW, ngate, nval, out, target, mask = saved[internal_id]
-            ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
-            d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=dev)]).contiguous()
-            dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
-                   gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
-            d_final = ops.readout_loss_bwd(final, h0, gnl, None, G, gW, tW, ngate, nval, out, target, mask, None, d_stats,
-                                           d_last_h=d_final, grad_out=dst)[0]
-            out_keep = float(ph.get('out_layer_dropout_keep_prob', 1.0))
-            if out_keep < 1.0:                                                          # utils.py:68: the masks of the forward
-                ops.dropout(dst[0], out_keep, gate.dropout_seed(0), out=dst[0])
-                ops.dropout(dst[2], out_keep, tr.dropout_seed(0), out=dst[2])
+        d_final = (_readout_multi_backward if multi else _readout_per_task_backward)(model, saved, dens, gviews)
         gW_arr = _ptrs([gviews[w.data_ptr()] for w in Ws])
         gb_arr = None if bs is None else _ptrs([gviews[b.data_ptr()] for b in bs])
         ops._launch("gcn_train_backward[L=%d]" % L, lambda: lib.ggnn_gcn_train_backward_f32(

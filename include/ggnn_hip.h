@@ -253,6 +253,46 @@ int ggnn_readout_loss_bwd_f32(const float* hT, const float* h0, const int32_t* g
                               float* d_transform_W, float* d_transform_b, void* ws, size_t ws_bytes, int V, int D,
                               int num_graphs, ggnn_stream_t stream);
 
+/* ---- (f-3) multi-task fused readout + masked loss: (f-2) for the K entries of task_ids in one pass ------------------------------
+ * chem_tensorflow.py:150-170 runs the gated regression and the masked loss once per task; these entry points compute all K
+ * tasks while reading hT and h0 ONCE in the forward and ONCE in the backward, and write d_hT once, whatever K is.  Same f32
+ * arithmetic as (f-2), DETERMINISTIC and atomics-free (graph_nodes_list NON-DECREASING); every per-task result (out, stats, the
+ * weight and bias gradients) is summed in an order that does not depend on K, so task k of two calls with different K agrees bit
+ * for bit.  Tasks >= K are neither read nor written.
+ *
+ * ggnn_readout_multi_supported(D, K): 1 for D a multiple of 4 in 4..256 and 1 <= K <= 16 (no scratch at any of them), else 0.
+ * ggnn_readout_multi_fwd_f32
+ *   hT, h0 [V,D]; graph_nodes_list [V] int32 sorted; graph_ptr [G+1] int32 or NULL; node_mask [V] or NULL -- as in (f-2).
+ *   gate_W, gate_b, transform_W, transform_b: HOST arrays of K DEVICE pointers (as ggnn_sparse_propagate_f32's per-layer arrays):
+ *   gate_W[k] [2D], gate_b[k] [1], transform_W[k] [D], transform_b[k] [1]; gate_W[k] and transform_W[k] 16-byte aligned.
+ *   target, mask [K,G] row-major or NULL (mask NULL with a target: all ones)
+ *   out [K,G]:  out[k,g] = sum_{v in g} sigmoid([hT|h0][v] . gate_W[k] + gate_b[k]) (hT[v] . transform_W[k] + transform_b[k]) (node_mask[v])
+ *   node_gv [V, 2K]: row v = gate[v,0..K) | val[v,0..K), the per-node gate and value of every task, kept for the backward pass
+ *   stats DEVICE [K,3] or NULL (needs target): per task sum_g 0.5 diff^2, sum_g |diff|, sum_g mask, diff = (out - target) mask
+ *   ws: ggnn_readout_multi_workspace_bytes(V, D, K, G) bytes.
+ *   V == 0 with G > 0: out = 0 and the stats of an all-zero prediction.  G == 0: GGNN_OK with zeroed stats.
+ * ggnn_readout_multi_bwd_f32
+ *   d_out [K,G] or NULL; d_stats DEVICE [K,2] or NULL (gradients w.r.t. stats[k,0] and stats[k,1]);
+ *   d_hT [V,D] written (accumulate = 0; zeros when G == 0) or added to (accumulate != 0), once, with the K tasks summed in task
+ *   order;
+ *   d_gate_W, d_gate_b, d_transform_W, d_transform_b: HOST arrays of K DEVICE destinations ([2D], [1], [D], [1]; any 4-byte
+ *   alignment: e.g. the optimizer's flat gradient views), written.
+ * Errors: null / misaligned pointers GGNN_E_INVALID, ggnn_readout_multi_supported(D, K) == 0 GGNN_E_UNSUPPORTED, a short workspace
+ * GGNN_E_WORKSPACE -- all found before anything is launched. */
+int ggnn_readout_multi_supported(int D, int K);
+size_t ggnn_readout_multi_workspace_bytes(int V, int D, int K, int num_graphs);
+int ggnn_readout_multi_fwd_f32(const float* hT, const float* h0, const int32_t* graph_nodes_list, const int32_t* graph_ptr,
+                               const float* node_mask, const float* const* gate_W, const float* const* gate_b,
+                               const float* const* transform_W, const float* const* transform_b, const float* target,
+                               const float* mask, float* out, float* node_gv, float* stats, void* ws, size_t ws_bytes, int V,
+                               int D, int K, int num_graphs, ggnn_stream_t stream);
+int ggnn_readout_multi_bwd_f32(const float* hT, const float* h0, const int32_t* graph_nodes_list, const float* node_mask,
+                               const float* const* gate_W, const float* const* transform_W, const float* node_gv,
+                               const float* out, const float* target, const float* mask, const float* d_out,
+                               const float* d_stats, float* d_hT, int accumulate, float* const* d_gate_W,
+                               float* const* d_gate_b, float* const* d_transform_W, float* const* d_transform_b, void* ws,
+                               size_t ws_bytes, int V, int D, int K, int num_graphs, ggnn_stream_t stream);
+
 /* ---- (a-8, a-G) residual concat + GRU node update: chem_tensorflow_sparse.py:211-216 -----------
  * TF-1.3 GRUCell: [r|u] = sigmoid([x|h] Wg + bg); c = act([x | r*h] Wc + bc); h' = u*h + (1-u)*c
  * with x = [x_segs[0] | ... | x_segs[nx-1]] read through nx pointers (no concat is materialised;
