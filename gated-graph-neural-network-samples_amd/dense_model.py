@@ -350,9 +350,7 @@ class DenseGGNNChemModel(ChemModel):
                         if bucket_list[ex_to_sample:]:
                             label_mask[np.asarray(bucket_list[ex_to_sample:]), internal_id] = 0.0
         # :160-162 one entry per full batch of a bucket (remainder graphs are dropped)
-        bucket_at_step = [[bucket_idx for _ in range(len(bucket_data) // self.params['batch_size'])]
-                          for bucket_idx, bucket_data in bucketed.items()]
-        bucket_at_step = [x for y in bucket_at_step for x in y]
+        bucket_at_step = [b for b, graphs in bucketed.items() for _ in range(len(graphs) // self.params['batch_size'])]
         return {"molecules": ms, "bucketed": dict(bucketed), "bucket_sizes": np.asarray(bucket_sizes),
                 "bucket_at_step": bucket_at_step, "device_batches": {}, "label_mask": label_mask}
 
@@ -447,20 +445,18 @@ class DenseGGNNChemModel(ChemModel):
         shuffles, in the same order: the same feeds bit for bit."""
         ms: MoleculeSet = data["molecules"]
         bucketed, bucket_sizes, bucket_at_step = data["bucketed"], data["bucket_sizes"], data["bucket_at_step"]
-        if is_training:                                   # :197-200 both shuffles are in place (orders compose over epochs)
-            np.random.shuffle(bucket_at_step)
-            for bucket in bucketed.values():
-                np.random.shuffle(bucket)
-        bucket_counters = defaultdict(int)
-        dropout_keep_prob = self.params['graph_state_dropout_keep_prob'] if is_training else 1.
+        if is_training:                                   # :197-200 the step list, then every bucket; in place (orders compose over epochs)
+            for shuffled in (bucket_at_step, *bucketed.values()):
+                np.random.shuffle(shuffled)
+        batches_taken = defaultdict(int)                  # per bucket, so far in this epoch
+        keep_prob = self.params['graph_state_dropout_keep_prob'] if is_training else 1.0
         bs = self.params['batch_size']
         on_device = bool(self.params.get('pack_on_device'))
         epoch_tab, starts = None, None                    # pack_on_device: the epoch's order on the device, formed at the first batch
-        for step in range(len(bucket_at_step)):
-            bucket = bucket_at_step[step]
-            start_idx = bucket_counters[bucket] * bs
+        for step, bucket in enumerate(bucket_at_step):
+            start_idx = batches_taken[bucket] * bs
             ids = np.asarray(bucketed[bucket][start_idx:start_idx + bs])
-            key = (bucket, bucket_counters[bucket])
+            key = (bucket, batches_taken[bucket])
             if is_training or key not in data["device_batches"]:
                 if on_device:
                     if epoch_tab is None:
@@ -478,7 +474,7 @@ class DenseGGNNChemModel(ChemModel):
                 feed = data["device_batches"][key]
             feed = dict(feed)
             # :222-223 the dense model feeds graph_state_dropout_keep_prob into BOTH keep-prob placeholders
-            feed['graph_state_keep_prob'] = dropout_keep_prob
-            feed['edge_weight_dropout_keep_prob'] = dropout_keep_prob
-            bucket_counters[bucket] += 1
+            feed['graph_state_keep_prob'] = keep_prob
+            feed['edge_weight_dropout_keep_prob'] = keep_prob
+            batches_taken[bucket] += 1
             yield feed

@@ -302,13 +302,9 @@ class SparseGGNNChemModel(ChemModel):
             final = self._propagate_native(h0, index, nin, use_avg, act, gru_fmts)
             return final if Dk == h_dim else final[:, :h_dim].contiguous()
 
-        for (layer_idx, num_timesteps) in enumerate(self.params['layer_timesteps']):   # :131
-            layer_residual_connections = self.params['residual_connections'].get(str(layer_idx))   # :140
-            if layer_residual_connections is None:
-                layer_residual_states = []
-            else:
-                layer_residual_states = [node_states_per_layer[residual_layer_idx]
-                                         for residual_layer_idx in layer_residual_connections]
+        for layer_idx, num_timesteps in enumerate(self.params['layer_timesteps']):     # :131
+            residual_from = self.params['residual_connections'].get(str(layer_idx)) or ()          # :140 (keyed by str: JSON)
+            layer_residual_states = [node_states_per_layer[earlier] for earlier in residual_from]
             ew_var, edge_biases, attn_w, cell = self._kernel_layer(layer_idx, need_grad)
             # :91 one weight-dropout mask per layer per run, shared by the layer's timesteps
             ew_mask = None
@@ -650,25 +646,21 @@ class SparseGGNNChemModel(ChemModel):
             yield feed, states, st
 
     def evaluate_one_batch(self, data):
-        """chem_tensorflow_sparse.py:352-362."""
-        outs = []
-        for item in self.make_minibatch_iterator(data, is_training=False):
-            item['graph_state_keep_prob'] = 1.0
-            item['edge_weight_dropout_keep_prob'] = 1.0
-            item['out_layer_dropout_keep_prob'] = 1.0
+        """The predictions for every batch of `data`, all dropout off: printed batch by batch and returned as a list of arrays."""
+        predictions = []
+        for batch in self.make_minibatch_iterator(data, is_training=False):
+            batch.update(graph_state_keep_prob=1.0, edge_weight_dropout_keep_prob=1.0, out_layer_dropout_keep_prob=1.0)
             with torch.no_grad():
-                self.forward_batch(item)
-            outs.append(self.output.detach().cpu().numpy())
-            print(outs[-1])
-        return outs
+                self.forward_batch(batch)
+            predictions.append(self.output.detach().cpu().numpy())
+            print(predictions[-1])
+        return predictions
 
     def example_evaluation(self, molecules_file: str = 'molecules_valid.json'):
-        """chem_tensorflow_sparse.py:364-376: first 10 validation molecules, predictions next to targets."""
+        """Prints the targets of the file's first 10 molecules, then evaluate_one_batch's predictions for them."""
         import json
-        n_example_molecules = 10
-        with open(molecules_file, 'r') as valid_file:
-            example_molecules = json.load(valid_file)[:n_example_molecules]
-        for mol in example_molecules:
-            print(mol['targets'])
-        example_molecules = self.process_raw_graphs(example_molecules, is_training_data=False)
-        return self.evaluate_one_batch(example_molecules)
+        with open(molecules_file) as f:
+            examples = json.load(f)[:10]
+        for molecule in examples:
+            print(molecule['targets'])
+        return self.evaluate_one_batch(self.process_raw_graphs(examples, is_training_data=False))

@@ -59,7 +59,7 @@ def _readout_per_task_forward(model, final, h0, gnl, gptr, node_mask, G: int):
         per_task.append((gate, tr, gW, tW, ngate, nval, out, target, mask))
         num, ab, ms = stats[0], stats[1], stats[2]
         den = ms + SMALL_NUMBER
-        ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)                 # chem_tensorflow.py:168
+        ratio = model.task_ratio(task_id)                                           # chem_tensorflow.py:168
         model.ops['accuracy_task%i' % task_id] = ab / den
         model.ops['loss_numerator_task%i' % task_id] = num
         model.ops['abs_error_sum_task%i' % task_id] = ab
@@ -81,7 +81,7 @@ def _readout_per_task_backward(model, saved, dens, gviews):
     d_final = None
     for internal_id, task_id in enumerate(p['task_ids']):
         gate, tr, gW, tW, ngate, nval, out, target, mask = per_task[internal_id]
-        ratio = 1.0 / (p['task_sample_ratios'].get(task_id) or 1.0)
+        ratio = model.task_ratio(task_id)
         d_stats = torch.stack([ratio / (dens[internal_id] + SMALL_NUMBER), torch.zeros((), dtype=torch.float32, device=final.device)]).contiguous()
         dst = [gviews[gate.params["weights"][0].data_ptr()], gviews[gate.params["biases"][0].data_ptr()],
                gviews[tr.params["weights"][0].data_ptr()], gviews[tr.params["biases"][0].data_ptr()]]
@@ -301,7 +301,7 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
                 loss = (saved[-1][:, 0] / (dens + SMALL_NUMBER) * model.task_ratio_factors(dev)).sum()
             else:
                 loss = torch.stack([model.ops['loss_numerator_task%i' % t] / (dens[i] + SMALL_NUMBER) *
-                                    (1.0 / (p['task_sample_ratios'].get(t) or 1.0)) for i, t in enumerate(p['task_ids'])]).sum()
+                                    model.task_ratio(t) for i, t in enumerate(p['task_ids'])]).sum()
 
         # ---- backward -----------------------------------------------------------------------------------------------------
         opt._flat["g"].zero_()

@@ -189,8 +189,8 @@ class StreamPrefetcher:
 
 def glorot_init(shape):
     """utils.py:11-13 -- uniform(+-sqrt(6/(shape[-2]+shape[-1]))) from the global NumPy RNG."""
-    initialization_range = np.sqrt(6.0 / (shape[-2] + shape[-1]))
-    return np.random.uniform(low=-initialization_range, high=initialization_range, size=shape).astype(np.float32)
+    limit = np.sqrt(6.0 / (shape[-2] + shape[-1]))
+    return np.random.uniform(low=-limit, high=limit, size=shape).astype(np.float32)
 
 
 def tf_glorot_uniform(shape, generator: torch.Generator) -> torch.Tensor:
@@ -306,10 +306,10 @@ class MLP(object):
         self.params = self.make_network_params()
 
     def make_network_params(self):
-        dims = [self.in_size] + self.hid_sizes + [self.out_size]
-        weight_sizes = list(zip(dims[:-1], dims[1:]))
-        weights = [torch.from_numpy(self.init_weights(s)).to(self.device) for s in weight_sizes]
-        biases = [torch.zeros(s[-1], dtype=torch.float32, device=self.device) for s in weight_sizes]
+        widths = [self.in_size, *self.hid_sizes, self.out_size]
+        shapes = list(zip(widths, widths[1:]))                       # (fan-in, fan-out) of each layer
+        weights = [torch.from_numpy(self.init_weights(shape)).to(self.device) for shape in shapes]
+        biases = [torch.zeros(fan_out, dtype=torch.float32, device=self.device) for _, fan_out in shapes]
         return {"weights": weights, "biases": biases}
 
     def init_weights(self, shape):

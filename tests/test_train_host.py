@@ -335,7 +335,7 @@ def _epoch_stats_worker(rank, world, port, ret):
     ab = rng.uniform(1, 2, (steps, world, 2)); graphs = rng.integers(1, 9, (steps, world)).astype(float)
     graphs[2, 1] = 0; num[2, 1] = 0; den[2, 1] = 0; ab[2, 1] = 0    # rank 1's last batch is an empty padding batch
     stats = [torch.tensor(np.concatenate([num[s, rank], den[s, rank], ab[s, rank]])) for s in range(steps)]
-    loss, accs, total = pkg.chem_model.ChemModel._reduce_epoch_stats(stub, stats, list(graphs[:, rank]))
+    loss, accs, total = pkg.chem_model.EpochStats.reduce_over_ranks(stub, stats, list(graphs[:, rank]))
     N, Dn, A, G = num.sum(1), den.sum(1), ab.sum(1), graphs.sum(1)
     want_loss = float(((N / (Dn + 1e-7)).sum(1) * G).sum() / G.sum())
     want_acc = ((A / (Dn + 1e-7)) * G[:, None]).sum(0) / G.sum()
