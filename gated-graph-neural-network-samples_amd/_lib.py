@@ -86,6 +86,15 @@ SYMBOLS = {
                                           POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                           POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32),
                                           POINTER(c_int32), c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    # propagation attention over the compacted transform's rows (ggnn_attn_compact.hip) and its one-call driver
+    "ggnn_gather_segment_sum_attn_compact_f32": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ggnn_attn_bwd_target_compact_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "ggnn_sparse_propagate_attn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                               c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                               POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                               POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                               POINTER(c_int32), POINTER(c_int32), c_int, c_int, POINTER(c_void_p), c_void_p,
+                                               c_size_t, c_void_p, POINTER(c_void_p), c_void_p]),
     "ggnn_gru_bwd_stage1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ggnn_gru_bwd_stage2_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -6,7 +6,9 @@
 //
 // Per timestep it launches either 3 kernels (transform, gather/segment-sum, GRU) or -- with `fuse_gather`, packed
 // GRU weights, a fused hidden size and no edge bias -- 2 kernels (transform, GRU with the segment sum gathered
-// inside: ggnn_gru_packed_gather_f32).
+// inside: ggnn_gru_packed_gather_f32).  With propagation attention (:147-149, 170-196; ggnn_sparse_propagate_attn_f32) the
+// segment sum is ggnn_gather_segment_sum_attn_compact_f32 over the compacted rows: always 3 kernels.  Both entry points run the
+// one driver below; without attention it launches what it always launched.
 #include "ggnn_common.h"
 #include <cstring>
 
@@ -28,7 +30,7 @@ static inline char* bump(char*& p, size_t bytes) {
     return r;
 }
 
-extern "C" int ggnn_sparse_propagate_f32(
+static int propagate(
         const float* h0, int V, int D, int T,
         const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
         const float* nin, int use_avg,
@@ -36,7 +38,8 @@ extern "C" int ggnn_sparse_propagate_f32(
         const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
         const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
         const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act, int fuse_gather,
-        float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
+        float* const* layer_out, void* ws, size_t ws_bytes, const int32_t* slot_pair, const float* const* attn_factors,
+        ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0 && T > 0, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(num_layers > 0 && layer_timesteps && res_ptr && layer_out, "bad layer description");
     GGNN_CHECK_ARG(edge_w || edge_packed, "edge weights missing");
@@ -44,6 +47,7 @@ extern "C" int ggnn_sparse_propagate_f32(
     if (V == 0) return GGNN_OK;
     GGNN_CHECK_ARG(h0 && row_ptr && ws, "null pointer");
     const bool compact = pair_node != nullptr && type_row_off != nullptr;
+    GGNN_CHECK_ARG(!attn_factors || compact, "propagation attention needs the compacted transform (pair_node, type_row_off)");
     const int64_t rows = compact ? type_row_off[T] : -1;
     if (ws_bytes < ggnn_sparse_propagate_workspace_bytes(V, D, T, rows))
         return ggnn::fail(GGNN_E_WORKSPACE, "propagate workspace too small: %zu < %zu", ws_bytes,
@@ -90,7 +94,9 @@ extern "C" int ggnn_sparse_propagate_f32(
         const int fmt_l = gru_fmt ? gru_fmt[l] : GGNN_GRU_FMT_BF16X3;      // the format gru_packed[l] was packed in
         // fuse_gather = the largest number of concatenated GRU inputs (residuals + messages) for which the segment sum
         // is gathered inside the GRU kernel; 0 = never.
-        const bool gather_in_gru = fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
+        const float* factors_l = attn_factors ? attn_factors[l] : nullptr;
+        GGNN_CHECK_ARG(!attn_factors || factors_l, "attn_factors[%d] is null", l);
+        const bool gather_in_gru = !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
                                    (unsigned long long)V * T * D < (1ULL << 30);      // (its 32-bit byte offsets)
         for (int s = 0; s < steps; ++s) {          // :153
             int rc;
@@ -113,7 +119,9 @@ extern "C" int ggnn_sparse_propagate_f32(
                 rc = ggnn_gru_packed_gather_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, H, row_ptr, gather_row, nin, T,
                                                 use_avg, V, D, act, fmt_l, counter, stream);
             } else {
-                rc = ggnn_gather_segment_sum_f32(H, row_ptr, gather_row, nin, bias_l, use_avg, incoming, V, D, T, stream);
+                rc = factors_l ? ggnn_gather_segment_sum_attn_compact_f32(H, cur, row_ptr, slot_pair, gather_row, factors_l, nin, bias_l,
+                                                                          use_avg, incoming, V, D, T, stream)
+                               : ggnn_gather_segment_sum_f32(H, row_ptr, gather_row, nin, bias_l, use_avg, incoming, V, D, T, stream);
                 if (rc) return rc;
                 if (packed_gru)
                     rc = ggnn_gru_packed_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, nullptr, nullptr, nullptr, V, D, act,
@@ -133,4 +141,35 @@ extern "C" int ggnn_sparse_propagate_f32(
         states[l + 1] = layer_out[l];
     }
     return GGNN_OK;
+}
+
+extern "C" int ggnn_sparse_propagate_f32(
+        const float* h0, int V, int D, int T,
+        const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
+        const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+        const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
+        const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act, int fuse_gather,
+        float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
+    return propagate(h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                     res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
+                     layer_out, ws, ws_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int ggnn_sparse_propagate_attn_f32(
+        const float* h0, int V, int D, int T,
+        const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
+        const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+        const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
+        const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act, int fuse_gather,
+        float* const* layer_out, void* ws, size_t ws_bytes, const int32_t* slot_pair, const float* const* attn_factors,
+        ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(attn_factors, "attn_factors is null");
+    if (D > 256) return ggnn::fail(GGNN_E_UNSUPPORTED, "propagation attention supports hidden sizes up to 256 (got %d)", D);
+    return propagate(h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                     res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
+                     layer_out, ws, ws_bytes, slot_pair, attn_factors, stream);
 }

@@ -1211,11 +1211,13 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
                      Wg: Sequence[torch.Tensor], bg: Sequence[torch.Tensor], Wc: Sequence[torch.Tensor], bc: Sequence[torch.Tensor],
                      gru_packed: Optional[Sequence[torch.Tensor]], activation: str,
                      fuse_gather: Optional[bool] = None, gru_fmt: Optional[Sequence[int]] = None,
-                     edge_fmt: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+                     edge_fmt: Optional[Sequence[int]] = None, attn: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
     """chem_tensorflow_sparse.py:131-218 in ONE native call (ggnn_sparse_propagate_f32): returns
     node_states_per_layer[1:], the last entry being the final node representations.
     gru_fmt / edge_fmt: per layer, the operand format gru_packed[l] / edge_packed[l] was packed in (None: BF16X3 for every layer).
-    fuse_gather (default FUSE_GATHER): gather the segment sum inside the GRU kernel where the layer allows it."""
+    fuse_gather (default FUSE_GATHER): gather the segment sum inside the GRU kernel where the layer allows it.
+    attn: per layer, the [T] edge_type_attention_weights (:94-96): the propagation-attention form of the loop
+    (ggnn_sparse_propagate_attn_f32; needs `comp`)."""
     if fuse_gather is None:
         fuse_gather = FUSE_GATHER
     lib = _lib.load()
@@ -1237,6 +1239,21 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
     i32 = lambda xs: (ctypes.c_int32 * max(len(xs), 1))(*xs)
     off = None if comp is None else (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
     gather = index.gather_row if comp is None else comp.gather_row
+    if attn is not None:
+        if comp is None or len(attn) != L:
+            raise ValueError("propagation attention needs the compacted transform and one [T] factor tensor per layer")
+        for l, f in enumerate(attn):
+            _req(f, torch.float32, "attn[%d]" % l)
+            if f.shape != (T,):
+                raise ValueError("attn[%d] must be [T]" % l)
+        _launch("sparse_propagate_attn", lambda: lib.ggnn_sparse_propagate_attn_f32(
+            _ptr(h0), V, D, T, _ptr(index.row_ptr), _ptr(gather), _ptr(comp.pair_node), off,
+            _ptr(nin), 1 if use_avg else 0, L, i32([int(x) for x in layer_timesteps]), i32(res_ptr), i32(res_idx),
+            _ptr_array(edge_w), _ptr_array(edge_packed), _ptr_array(edge_bias), _ptr_array(Wg), _ptr_array(bg), _ptr_array(Wc),
+            _ptr_array(bc), _ptr_array(gru_packed), None if gru_fmt is None else i32([int(f) for f in gru_fmt]),
+            None if edge_fmt is None else i32([int(f) for f in edge_fmt]), act, 0,
+            _ptr_array(outs), _ptr(ws), ws_bytes, _ptr(index.gather_row), _ptr_array(attn), _stream()))
+        return outs
     _launch("sparse_propagate", lambda: lib.ggnn_sparse_propagate_f32(
         _ptr(h0), V, D, T, _ptr(index.row_ptr), _ptr(gather), None if comp is None else _ptr(comp.pair_node), off,
         _ptr(nin), 1 if use_avg else 0, L, i32([int(x) for x in layer_timesteps]), i32(res_ptr), i32(res_idx),
@@ -1459,6 +1476,51 @@ def gather_segment_sum_attn(H: torch.Tensor, h: torch.Tensor, index: MessageInde
         _ptr(H), _ptr(h), _ptr(index.row_ptr), _ptr(index.gather_row), _ptr(type_factors), _ptr(nin), _ptr(edge_biases),
         1 if use_avg else 0, _ptr(out), V, D, T, _stream()))
     return out
+
+
+def gather_segment_sum_attn_compact(Hc: torch.Tensor, h: torch.Tensor, index: MessageIndex, comp: CompactSources,
+                                    type_factors: torch.Tensor, num_incoming_edges_per_type: Optional[torch.Tensor],
+                                    edge_biases: Optional[torch.Tensor], use_avg: bool,
+                                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gather_segment_sum_attn over the compacted transform's rows (ggnn_gather_segment_sum_attn_compact_f32): the message of slot
+    e is Hc[comp.gather_row[e]] (Hc [R,D] from msg_transform_compact[_packed]); index.gather_row still names source and type."""
+    lib = _lib.load()
+    _req(Hc, torch.float32, "Hc"); _req(h, torch.float32, "h"); _req(type_factors, torch.float32, "type_factors")
+    V, T = index.num_nodes, index.num_edge_types
+    D = h.shape[1]
+    if h.shape[0] != V or Hc.dim() != 2 or Hc.shape[1] != D or Hc.shape[0] < comp.num_rows or type_factors.shape != (T,):
+        raise ValueError("shape mismatch: Hc [R,D], h [V,D], type_factors [T]")
+    nin = num_incoming_edges_per_type
+    if nin is not None:
+        _req(nin, torch.float32, "num_incoming_edges_per_type")
+    if edge_biases is not None:
+        _req(edge_biases, torch.float32, "edge_biases")
+    if out is None:
+        out = torch.empty((V, D), dtype=torch.float32, device=h.device)
+    else:
+        _req(out, torch.float32, "out")
+    _launch("gather_segment_sum_attn_compact", lambda: lib.ggnn_gather_segment_sum_attn_compact_f32(
+        _ptr(Hc), _ptr(h), _ptr(index.row_ptr), _ptr(index.gather_row), _ptr(comp.gather_row), _ptr(type_factors), _ptr(nin),
+        _ptr(edge_biases), 1 if use_avg else 0, _ptr(out), V, D, T, _stream()))
+    return out
+
+
+def attn_backward_target_compact(Hc: torch.Tensor, h: torch.Tensor, d_att: torch.Tensor, index: MessageIndex, comp: CompactSources,
+                                 type_factors: torch.Tensor, dh: torch.Tensor):
+    """attn_backward_target over the compacted transform's rows (ggnn_attn_bwd_target_compact_f32): adds the target-side state
+    gradient to dh and returns the per-message (coef_a, coef_s, dfac), indexed by message id."""
+    lib = _lib.load()
+    _req(Hc, torch.float32, "Hc"); _req(h, torch.float32, "h"); _req(d_att, torch.float32, "d_att"); _req(dh, torch.float32, "dh")
+    V, D = h.shape
+    T, M = index.num_edge_types, index.num_messages
+    if Hc.dim() != 2 or Hc.shape[1] != D or Hc.shape[0] < comp.num_rows or d_att.shape != (V, D) or dh.shape != (V, D):
+        raise ValueError("shape mismatch: Hc [R,D], h / d_att / dh [V,D]")
+    dev = h.device
+    ca = torch.empty(max(M, 1), dtype=torch.float32, device=dev); cs = torch.empty_like(ca); df = torch.empty_like(ca)
+    _launch("attn_bwd_target_compact", lambda: lib.ggnn_attn_bwd_target_compact_f32(
+        _ptr(Hc), _ptr(h), _ptr(d_att), _ptr(index.row_ptr), _ptr(index.gather_row), _ptr(comp.gather_row), _ptr(index.msg_perm),
+        _ptr(type_factors), _ptr(ca), _ptr(cs), _ptr(df), _ptr(dh), 1, V, D, T, _stream()))
+    return ca, cs, df
 
 
 def rnn(x_segs: Sequence[torch.Tensor], h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, activation: str = "tanh") -> torch.Tensor:

@@ -273,6 +273,15 @@ class SparseGGNNChemModel(ChemModel):
         self.last_gru_formats, self.last_edge_formats = fm, em
         return fm
 
+    def attention_route(self) -> bool:
+        """True when propagation attention (:147-149, 170-196) runs on the compacted fast route: the opt-in key
+        params['compact_attention'], use_propagation_attention, the GRU cell, a GPU model and a kernel width that has a compacted
+        transform (32 / 64 / 100 / 128 / 192 / 256 and what pads to them) within the attention kernels' 256 columns.  Anything else
+        keeps the dense-transform variant route."""
+        p = self.params
+        return bool(p.get('compact_attention')) and bool(p['use_propagation_attention']) and self.cell_type == 'gru' \
+            and torch.device(self.device).type == 'cuda' and self._kw <= 256 and ops.compact_supported(self._kw)
+
     # ---- the hot path -----------------------------------------------------------------------------------
     def compute_final_node_representations(self) -> torch.Tensor:
         """chem_tensorflow_sparse.py:117-218."""
@@ -296,7 +305,12 @@ class SparseGGNNChemModel(ChemModel):
         need_grad = self.training and torch.is_grad_enabled()
         variant = self.params['use_propagation_attention'] or self.cell_type != 'gru'
         gru_fmts = self.gru_formats(h0, ew_keep, st_keep, need_grad)
+        attn_route = self.attention_route() and h0.is_cuda
 
+        if attn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
+            # inference with attention on the compacted route: the same ONE native call, every product in the exact format
+            final = self._propagate_native(h0, index, nin, use_avg, act, gru_fmts, attention=True)
+            return final if Dk == h_dim else final[:, :h_dim].contiguous()
         if not variant and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
             # inference: the whole layer/timestep loop below runs inside ONE native call
             final = self._propagate_native(h0, index, nin, use_avg, act, gru_fmts)
@@ -330,10 +344,10 @@ class SparseGGNNChemModel(ChemModel):
                     # non-default switches, training: HIP forward, autograd-derived backward (variants.py)
                     from .variants import variant_step
                     cur = variant_step(cur, index, nin, edge_weights, edge_biases, attn_w, use_avg, layer_residual_states,
-                                       self.cell_type, tuple(cell), act)
+                                       self.cell_type, tuple(cell), act, compact_attention=attn_route)
                 elif variant:
                     cur = self._variant_step(cur, index, nin, edge_weights.contiguous(), edge_biases, attn_w, use_avg,
-                                             layer_residual_states, cell, act)
+                                             layer_residual_states, cell, act, compact_attention=attn_route)
                 else:
                     cur = propagation_step(cur, index, nin, edge_weights, edge_biases, use_avg,
                                            layer_residual_states, cell, act, need_grad,
@@ -359,9 +373,21 @@ class SparseGGNNChemModel(ChemModel):
             ph['node_uid'] = uid = uid.contiguous()
         return uid
 
-    def _variant_step(self, h, index, nin, edge_weights, edge_biases, attn_w, use_avg, residual_states, cell, act):
+    def _variant_step(self, h, index, nin, edge_weights, edge_biases, attn_w, use_avg, residual_states, cell, act,
+                      compact_attention: bool = False):
         """One timestep with the non-default switches of chem_tensorflow_sparse.py: propagation attention
-        (:147-149, 170-196) and/or the BasicRNNCell / CudnnCompatibleGRUCell cells (:105-110).  Dense transform."""
+        (:147-149, 170-196) and/or the BasicRNNCell / CudnnCompatibleGRUCell cells (:105-110).  Dense transform, unless
+        compact_attention (attention_route()): compacted transform, attention sum over the compact rows, packed GRU."""
+        if compact_attention:
+            from .autograd import _PACKED
+            from .variants import compact_sources
+            comp = compact_sources(index)
+            Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(edge_weights), edge_weights.shape[0], comp)
+            xs = list(residual_states) + [ops.gather_segment_sum_attn_compact(Hc, h, index, comp, attn_w, nin, edge_biases, use_avg)]
+            if ops.gru_is_fused(h.shape[1]) and len(xs) <= ops.GRU_FUSED_MAX_INPUTS:
+                packed = _PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(xs), h.shape[1])
+                return ops.gru_packed(xs, h, packed, cell.gates_bias, cell.candidate_bias, act)
+            return ops.gru(xs, h, cell.gates_kernel, cell.gates_bias, cell.candidate_kernel, cell.candidate_bias, act)
         H = ops.msg_transform(h, edge_weights)
         if self.params['use_propagation_attention']:
             incoming = ops.gather_segment_sum_attn(H, h, index, attn_w, nin, edge_biases, use_avg)
@@ -374,20 +400,23 @@ class SparseGGNNChemModel(ChemModel):
             return ops.rnn(xs, h, cell.kernel, cell.bias, act)
         return ops.cudnn_gru(xs, h, *cell)
 
-    def _propagate_native(self, h0, index, nin, use_avg, act, gru_fmts) -> torch.Tensor:
+    def _propagate_native(self, h0, index, nin, use_avg, act, gru_fmts, attention: bool = False) -> torch.Tensor:
         """compute_final_node_representations through ggnn_sparse_propagate_f32 (the loop of :131-218 in C):
-        source-compacted transform and pre-packed weight images where the hidden size supports them."""
+        source-compacted transform and pre-packed weight images where the hidden size supports them.
+        attention (attention_route()): ggnn_sparse_propagate_attn_f32, always compacted, every product in the exact format."""
         from .autograd import USE_COMPACT_TRANSFORM, _PACKED
         D, T = self._kw, self.num_edge_types
         L = len(self.params['layer_timesteps'])
         comp = None
-        if USE_COMPACT_TRANSFORM and ops.compact_supported(D):
+        if attention:
+            gru_fmts = [ops.GRU_FMT_EXACT] * L
+        if attention or (USE_COMPACT_TRANSFORM and ops.compact_supported(D)):
             comp = getattr(index, "_compact", None)
             if comp is None:
                 comp = index._compact = ops.build_compact_sources(index)
         layers = [self._kernel_layer(l, False) for l in range(L)]
         edge_w = [lay[0].contiguous() for lay in layers]
-        edge_fmts = list(self.last_edge_formats)
+        edge_fmts = [ops.GRU_FMT_EXACT] * L if attention else list(self.last_edge_formats)
         edge_packed = [_PACKED.edge(w, edge_fmts[l]) for l, w in enumerate(edge_w)] if comp is not None else None
         edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
         cells = [lay[3] for lay in layers]
@@ -401,7 +430,8 @@ class SparseGGNNChemModel(ChemModel):
                                     edge_w, edge_packed, edge_bias,
                                     [c.gates_kernel for c in cells], [c.gates_bias for c in cells],
                                     [c.candidate_kernel for c in cells], [c.candidate_bias for c in cells],
-                                    gru_packed, act, gru_fmt=gru_fmts, edge_fmt=edge_fmts)
+                                    gru_packed, act, gru_fmt=gru_fmts, edge_fmt=edge_fmts,
+                                    attn=[lay[2] for lay in layers] if attention else None)
         return outs[-1]
 
     def _graph_nodes_sorted(self) -> bool:

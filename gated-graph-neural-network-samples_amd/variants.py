@@ -9,6 +9,9 @@ ops.gru), exactly what inference runs.  The backward is hand-written on the same
   attention ggnn_attn_bwd_target_f32 (softmax backward per target node, no [M,D] tensor), ggnn_weighted_segment_sum_f32
             (transpose gathers with the per-message coefficients), ggnn_range_sum_f32 (d attention factor per type)
   transform backward.transform_backward (compact rows; the compacted transform kernel on W^T)
+With params['compact_attention'] (SparseGGNNChemModel.attention_route: attention, GRU cell, a width with a compacted transform) the
+step is CompactAttentionStepFn: forward ops.msg_transform_compact_packed -> ops.gather_segment_sum_attn_compact -> ops.gru_packed,
+backward the same kernels with ggnn_attn_bwd_target_compact_f32 on the recomputed compact rows -- no dense [V, T*D] product at all.
 Hidden sizes beyond the fused kernels' (128 / 192 / 256 and what pads to them) run the same backward on the generic kernels:
 the un-fused GRU backward, ggnn_gemm_tn_f32 / ggnn_colsum_f32 for the weight and bias gradients.  The timestep restated in
 differentiable torch ops lives in tests/variant_oracle.py (a test oracle; BACKWARD_ORACLE below is its hook).
@@ -32,23 +35,39 @@ class VariantStepFn(torch.autograd.Function):
              attention_weights|None, *cell tensors, *residual states)"""
 
     @staticmethod
-    def forward(ctx, h, index, nin, use_avg, cell_type, activation, num_cell, num_res, edge_weights, edge_biases,
-                attention_weights, *rest):
+    def forward(ctx, *args):
+        return VariantStepFn.step_forward(ctx, False, *args)
+
+    @staticmethod
+    def step_forward(ctx, compact_attention, h, index, nin, use_avg, cell_type, activation, num_cell, num_res, edge_weights,
+                     edge_biases, attention_weights, *rest):
         cell, residuals = rest[:num_cell], rest[num_cell:num_cell + num_res]
         h = h.contiguous()
         W = edge_weights.contiguous()
-        H = ops.msg_transform(h, W)
-        if attention_weights is not None:
-            incoming = ops.gather_segment_sum_attn(H, h, index, attention_weights, nin, edge_biases, use_avg)
-        else:
-            incoming = ops.gather_segment_sum(H, index, nin, edge_biases, use_avg)
-        xs = list(residuals) + [incoming]
         D = h.shape[1]       # (any kernel width: sizes without a compacted transform kernel take the per-type GEMM in transform_backward)
+        ctx.compact_attention = compact_attention
+        if compact_attention:
+            # attention, GRU cell, a width with a compacted transform: only the active (node, type) rows are transformed, the
+            # attention-weighted sum reads them through the compact slot rows (no dense [V, T*D] product, forward or backward)
+            from .autograd import _PACKED
+            assert attention_weights is not None and cell_type == 'gru'
+            Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(W), W.shape[0], compact_sources(index))
+            incoming = ops.gather_segment_sum_attn_compact(Hc, h, index, index._compact, attention_weights, nin, edge_biases, use_avg)
+        else:
+            H = ops.msg_transform(h, W)
+            if attention_weights is not None:
+                incoming = ops.gather_segment_sum_attn(H, h, index, attention_weights, nin, edge_biases, use_avg)
+            else:
+                incoming = ops.gather_segment_sum(H, index, nin, edge_biases, use_avg)
+        xs = list(residuals) + [incoming]
         ctx.hip_backward = BACKWARD_ORACLE is None
         extra = []                                              # what the hand-written backward needs beyond the inputs
         if cell_type == 'gru':
             save = {} if ctx.hip_backward else None
-            out = ops.gru(xs, h, cell[0], cell[1], cell[2], cell[3], activation, save=save)
+            if compact_attention and ops.gru_is_fused(D) and len(xs) <= ops.GRU_FUSED_MAX_INPUTS:
+                out = ops.gru_packed(xs, h, _PACKED.gru(cell[0], cell[2], len(xs), D), cell[1], cell[3], activation, save=save)
+            else:
+                out = ops.gru(xs, h, cell[0], cell[1], cell[2], cell[3], activation, save=save)
             if save is not None:
                 extra = [incoming, save["r"], save["u"], save["c"]]
         elif cell_type == 'rnn':
@@ -85,6 +104,22 @@ class VariantStepFn(torch.autograd.Function):
             extra = saved[k + ctx.num_cell + ctx.num_res:]
             return _hip_backward(ctx, g.contiguous(), h, nin, W, bias, attn, cell, residuals, extra)
         return BACKWARD_ORACLE(ctx, g.contiguous(), h, nin, W, bias, attn, cell, residuals)
+
+
+class CompactAttentionStepFn(VariantStepFn):
+    """VariantStepFn with the attention step on the compacted route; same arguments, same saved tensors, same backward hook."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return VariantStepFn.step_forward(ctx, True, *args)
+
+
+def compact_sources(index):
+    """The batch's active (source node, type) pairs (ops.CompactSources), built once per message index."""
+    comp = getattr(index, "_compact", None)
+    if comp is None:
+        comp = index._compact = ops.build_compact_sources(index)
+    return comp
 
 
 def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
@@ -139,13 +174,18 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
 
     # ---- aggregation: dinc is dL/d(sum of (attention-weighted) messages + nin @ bias) --------------------------------------------
     dbias = ops.gemm_tn(nin, dinc) if bias is not None else None                                 # :202-204  nin^T dinc  [T, D]
-    comp = getattr(index, "_compact", None)
-    if comp is None:
-        comp = index._compact = ops.build_compact_sources(index)
+    comp = compact_sources(index)
     dattn = None
     weights = None
     if attn is not None and not index.num_messages:                     # no message: nothing attends, no gradient
         dattn = torch.zeros_like(attn)
+    elif attn is not None and getattr(ctx, "compact_attention", False):   # :170-196 on the compact rows, recomputed
+        Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(W), T, comp)
+        weights, coef_s, dfac = ops.attn_backward_target_compact(Hc, h, dinc, index, comp, attn, dh)
+        del Hc
+        dattn = ops.range_sum(dfac, index.type_off)
+        bwd = ops.compact_backward(index, comp)
+        ops.weighted_segment_sum(h, bwd.source_node_index, bwd.source_node_index.msg, coef_s, out=dh, accumulate=True)
     elif attn is not None:                                              # :170-196
         H = ops.msg_transform(h, W)                                     # the messages' values, recomputed (dense form)
         weights, coef_s, dfac = ops.attn_backward_target(H.view(-1, D), h, dinc, index, attn, dh)
@@ -159,6 +199,8 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
 
 def variant_step(h, index, nin, edge_weights, edge_biases: Optional[torch.Tensor], attention_weights: Optional[torch.Tensor],
                  use_avg: bool, residual_states: Sequence[torch.Tensor], cell_type: str, cell: Sequence[torch.Tensor],
-                 activation: str) -> torch.Tensor:
-    return VariantStepFn.apply(h, index, nin, use_avg, cell_type, activation, len(cell), len(residual_states), edge_weights,
-                               edge_biases, attention_weights, *cell, *residual_states)
+                 activation: str, compact_attention: bool = False) -> torch.Tensor:
+    """compact_attention: the step of SparseGGNNChemModel.attention_route() (attention, GRU cell, a compacted-transform width)."""
+    fn = CompactAttentionStepFn if compact_attention else VariantStepFn
+    return fn.apply(h, index, nin, use_avg, cell_type, activation, len(cell), len(residual_states), edge_weights,
+                    edge_biases, attention_weights, *cell, *residual_states)

@@ -206,6 +206,25 @@ int ggnn_weighted_segment_sum_f32(const float* rows, const int32_t* row_ptr, con
                                   const float* weights, float* out, int accumulate, int num_segments, int D, ggnn_stream_t stream);
 int ggnn_range_sum_f32(const float* values, const int64_t* range_off, int num_ranges, float* out, ggnn_stream_t stream);
 
+/* Propagation attention over the rows of the COMPACTED transform (chem_tensorflow_sparse.py:147-149, 170-196; the per-type
+ * gathers and matmuls of :160-164 only for the active (source node, type) pairs).  The score <h[src], h[tgt]> * type_factors[type]
+ * does not read the transformed rows, so no dense [V, T*D] product is needed:
+ * ggnn_gather_segment_sum_attn_compact_f32: ggnn_gather_segment_sum_attn_f32 (same arithmetic, same results) with the message of
+ *   slot e taken from Hc[slot_row[e]] -- Hc [R,D] = ggnn_msg_transform_compact_f32's output, slot_row = ggnn_remap_gather_rows'
+ *   output -- while slot_pair[e] = src*T + type (ggnn_build_target_csr's gather_row) names the source node and the factor.  The
+ *   scores of a target's first 8 slots stay in registers between the max pass and the exp pass: per message one h[src] row and one
+ *   Hc row are read.  D <= 256 (GGNN_E_UNSUPPORTED beyond), D % 4 == 0; V == 0 is a no-op; a node without messages gets the zero
+ *   row (before bias).  No atomics: deterministic.
+ * ggnn_attn_bwd_target_compact_f32: ggnn_attn_bwd_target_f32 (TF autodiff of :170-196, target side) with the same addressing;
+ *   outputs as there (coef_a, coef_s, dfac by message id, dh (+)=). */
+int ggnn_gather_segment_sum_attn_compact_f32(const float* Hc, const float* h, const int32_t* row_ptr, const int32_t* slot_pair,
+                                             const int32_t* slot_row, const float* type_factors, const float* nin,
+                                             const float* bias, int use_avg, float* out, int V, int D, int T, ggnn_stream_t stream);
+int ggnn_attn_bwd_target_compact_f32(const float* Hc, const float* h, const float* d_att, const int32_t* row_ptr,
+                                     const int32_t* slot_pair, const int32_t* slot_row, const int32_t* msg_perm,
+                                     const float* type_factors, float* coef_a, float* coef_s, float* dfac, float* dh, int accumulate,
+                                     int V, int D, int T, ggnn_stream_t stream);
+
 /* tf.unsorted_segment_sum in its general form (chem_tensorflow_sparse.py:198-200, 226-228):
  * out[ids[m],:] += data[m,:] with out zero-filled first; fp32 atomics, any id order.  Used for the
  * readout's per-graph sum and available for un-bucketed message lists. */
@@ -406,6 +425,23 @@ int ggnn_sparse_propagate_f32(const float* h0, int V, int D, int T,
                               const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
                               const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act,
                               int fuse_gather, float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream);
+
+/* ggnn_sparse_propagate_f32 with use_propagation_attention (chem_tensorflow_sparse.py:131-218 with :147-149, 170-196): per timestep
+ * the compacted transform, ggnn_gather_segment_sum_attn_compact_f32 and the GRU (ggnn_gru_packed_f32, or ggnn_gru_f32 for layers
+ * without packed images).  The compact form is REQUIRED: pair_node / type_row_off non-NULL, gather_row = the remapped rows
+ * (slot_row).  Two more arguments:
+ *   slot_pair       the by-target index's own gather rows, src*T + type (ggnn_build_target_csr)
+ *   attn_factors    HOST [num_layers] of DEVICE [T]: edge_type_attention_weights per layer (:94-96)
+ * fuse_gather is ignored (the attention-weighted sum is never gathered inside the GRU).  Same workspace. */
+int ggnn_sparse_propagate_attn_f32(const float* h0, int V, int D, int T,
+                                   const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node,
+                                   const int64_t* type_row_off, const float* nin, int use_avg,
+                                   int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+                                   const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+                                   const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
+                                   const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act,
+                                   int fuse_gather, float* const* layer_out, void* ws, size_t ws_bytes,
+                                   const int32_t* slot_pair, const float* const* attn_factors, ggnn_stream_t stream);
 
 /* ---- (a-B) element-wise stages of the GRU backward (TF autodiff of GRUCell, chem_tensorflow.py:184) -------
  * stage 1: dpc = g*(1-u)*act'(c) -> dpc [V,D];  g*(h-c)*u*(1-u) -> dpg[:, D:2D];  g*u -> dh [V,D];
