@@ -89,6 +89,7 @@ SYMBOLS = {
     # propagation attention over the compacted transform's rows (ggnn_attn_compact.hip) and its one-call driver
     "ggnn_gather_segment_sum_attn_compact_f32": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ggnn_attn_bwd_target_compact_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "ggnn_attn_bwd_source_compact_f32": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),
     "ggnn_sparse_propagate_attn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
                                                c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
@@ -172,6 +173,18 @@ SYMBOLS = {
                                                c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the same step with propagation attention on the compacted route (params['compact_attention'] == 'native')
+    "ggnn_sparse_attn_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64, c_int, c_int64]),
+    "ggnn_sparse_attn_train_forward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   POINTER(c_int64), c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32),
+                                                   POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                                   POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_size_t, POINTER(c_int64),
+                                                   c_void_p]),
+    "ggnn_sparse_attn_train_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p, c_int, c_int,
+                                                    POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)] + [c_void_p] * 8 +
+                                                   [POINTER(c_void_p)] * 4 + [c_int] + [POINTER(c_void_p)] * 6 +
+                                                   [c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p]),
     "ggnn_dropout_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_float, c_int64, c_int, c_void_p]),
     "ggnn_gcn_fused_supported": (c_int, [c_int]),
     "ggnn_gcn_image_bytes": (c_size_t, [c_int]),

@@ -12,6 +12,7 @@
 // (molecule batches never have more than kHeld messages into a node).  Per message the forward reads one h[src] row and one
 // Hc row (dense-row kernel: two h[src] rows and one H row), the backward one of each (dense-row kernel: four and two).
 // VALU only, no atomics, slot order = the reference's accumulation order: deterministic.
+// attn_bwd_source_compact_kernel (the native training step's) closes the backward on the source side: see its comment.
 #include "ggnn_common.h"
 
 namespace ggnn {
@@ -207,6 +208,90 @@ __global__ __launch_bounds__(256) void attn_bwd_target_compact_kernel(
     }
 }
 
+// Source side of the backward, both transpose gathers in ONE pass over the messages LEAVING a node (by-(source, type) slots:
+// a node's slots are consecutive, the slots of one (node, type) pair -- one compact row -- consecutive inside them):
+//   dHc[slot_row[e]] = sum over the pair's slots of coef_a[msg_e] * d[dst_e]        (the weighted transpose of the forward gather)
+//   dh[u]           += sum over the node's slots of coef_s[msg_e] * h[dst_e]        (the source-side state gradient)
+// Bit for bit the two ggnn_weighted_segment_sum_f32 launches it replaces (same slot order, same acc += w * row, the old contents of
+// dh added last).  Those walk every slot index -> weight -> row with nothing in flight; here the first kHeldSrc slots' indices come
+// with one coalesced read each, their coefficients with one gathered read, and all their rows are in flight together.
+// kHeldSrc = 4, not kHeld: two rows per slot are held and a molecule's atom sends ~2 messages (at most 4 bonds).  With 8 held slots
+// the kernel took 110 VGPRs (4 waves/SIMD) and ran at 51.1 us against the two launches' 47.0 us (V = 99 989, M = 197 656, D = 100);
+// with 4 it takes 62 (8 waves/SIMD) and runs at 40.9 us against 47.3 us (tools/attention_bench.py --leg source).
+constexpr int kHeldSrc = 4;         // slots per source node whose rows are held in registers
+template <int LPR>
+__global__ __launch_bounds__(256) void attn_bwd_source_compact_kernel(
+        const float* __restrict__ d, const float* __restrict__ h, const int* __restrict__ node_ptr, const int* __restrict__ slot_dst,
+        const int* __restrict__ slot_msg, const int* __restrict__ slot_row, const float* __restrict__ coef_a,
+        const float* __restrict__ coef_s, float* __restrict__ dHc, float* __restrict__ dh, int V, int D) {
+    constexpr int NODES = 256 / LPR;
+    const int l = threadIdx.x % LPR;
+    int u = blockIdx.x * NODES + threadIdx.x / LPR;
+    const bool live = u < V;
+    u = live ? u : V - 1;                                    // dead sub-waves stay in every shuffle, with no slots
+    const int beg = node_ptr[u], end = live ? node_ptr[u + 1] : beg;
+    const int n = end - beg;
+    const int D4 = D >> 2;                                   // D4 <= LPR (checked by the launcher)
+    const bool col_ok = l < D4;
+    const int c4 = col_ok ? l : 0;
+    const bool with_dh = dh != nullptr;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+
+    // lane k holds the indices and coefficients of held slot k; lane kHeldSrc the row of the slot after them (kHeldSrc < LPR)
+    int dl = 0, rl = -1;
+    float al = 0.f, sl = 0.f;
+    if (l <= kHeldSrc && l < n) rl = slot_row[beg + l];
+    if (l < kHeldSrc && l < n) {
+        dl = slot_dst[beg + l];
+        const int mid = slot_msg[beg + l];
+        al = coef_a[mid];
+        sl = with_dh ? coef_s[mid] : 0.f;
+    }
+    int row[kHeldSrc + 1];
+    float ca[kHeldSrc], cs[kHeldSrc];
+    f32x4 dr[kHeldSrc], hr[kHeldSrc];
+#pragma unroll
+    for (int k = 0; k <= kHeldSrc; ++k) row[k] = __shfl(rl, k, LPR);       // (-1 past the node's last slot)
+#pragma unroll
+    for (int k = 0; k < kHeldSrc; ++k) {
+        const int dst = __shfl(dl, k, LPR);
+        ca[k] = __shfl(al, k, LPR);
+        cs[k] = __shfl(sl, k, LPR);
+        const bool on = col_ok && k < n;
+        dr[k] = on ? row4(d, dst, D, c4) : zero;
+        hr[k] = on && with_dh ? row4(h, dst, D, c4) : zero;
+    }
+    f32x4 acc_a = zero, acc_s = zero;
+#pragma unroll
+    for (int k = 0; k < kHeldSrc; ++k) {
+        if (k < n) {
+            acc_a += ca[k] * dr[k];
+            acc_s += cs[k] * hr[k];
+            if (row[k + 1] != row[k]) {                      // the pair's last slot
+                if (col_ok) *reinterpret_cast<f32x4*>(dHc + (size_t)row[k] * D + 4 * c4) = acc_a;
+                acc_a = zero;
+            }
+        }
+    }
+    for (int e = beg + kHeldSrc; e < end; ++e) {                // beyond the held slots: slot by slot
+        const int dst = slot_dst[e], mid = slot_msg[e], r = slot_row[e];
+        const int r_next = e + 1 < end ? slot_row[e + 1] : -1;
+        if (col_ok) {
+            acc_a += coef_a[mid] * row4(d, dst, D, c4);
+            if (with_dh) acc_s += coef_s[mid] * row4(h, dst, D, c4);
+            if (r_next != r) {
+                *reinterpret_cast<f32x4*>(dHc + (size_t)r * D + 4 * c4) = acc_a;
+                acc_a = zero;
+            }
+        }
+    }
+    if (col_ok && live && with_dh) {
+        float* o = dh + (size_t)u * D + 4 * c4;
+        acc_s += *reinterpret_cast<const f32x4*>(o);
+        *reinterpret_cast<f32x4*>(o) = acc_s;
+    }
+}
+
 }  // namespace ggnn
 
 using namespace ggnn;
@@ -252,6 +337,28 @@ extern "C" int ggnn_attn_bwd_target_compact_f32(const float* Hc, const float* h,
     else if (D4 <= 32) GGNN_ATTN_BWD_COMPACT(32, 8);
     else GGNN_ATTN_BWD_COMPACT(64, 4);
 #undef GGNN_ATTN_BWD_COMPACT
+    GGNN_CHECK_HIP(hipGetLastError());
+    return GGNN_OK;
+}
+
+extern "C" int ggnn_attn_bwd_source_compact_f32(const float* d_att, const float* h, const int32_t* node_ptr, const int32_t* slot_dst,
+                                                const int32_t* slot_msg, const int32_t* slot_row, const float* coef_a,
+                                                const float* coef_s, float* dHc, float* dh, int V, int D, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0, "bad sizes V=%d D=%d", V, D);
+    if (D > 256) return fail(GGNN_E_UNSUPPORTED, "propagation attention supports hidden sizes up to 256 (got %d)", D);
+    if (V == 0) return GGNN_OK;
+    GGNN_CHECK_ARG(d_att && node_ptr && slot_dst && slot_msg && slot_row && coef_a && dHc, "null pointer");
+    GGNN_CHECK_ARG(!dh || (h && coef_s), "h and coef_s are required with dh");
+    GGNN_CHECK_ARG(aligned16(d_att) && aligned16(dHc) && (!dh || (aligned16(h) && aligned16(dh))), "pointers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int D4 = D / 4;
+#define GGNN_ATTN_BWD_SOURCE(LPR, NODES)                                                                                       \
+    hipLaunchKernelGGL(attn_bwd_source_compact_kernel<LPR>, dim3((V + NODES - 1) / NODES), dim3(256), 0, st, d_att, h,         \
+                       node_ptr, slot_dst, slot_msg, slot_row, coef_a, coef_s, dHc, dh, V, D)
+    if (D4 <= 16) GGNN_ATTN_BWD_SOURCE(16, 16);
+    else if (D4 <= 32) GGNN_ATTN_BWD_SOURCE(32, 8);
+    else GGNN_ATTN_BWD_SOURCE(64, 4);
+#undef GGNN_ATTN_BWD_SOURCE
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }

@@ -35,6 +35,10 @@ int num_cus();
 // recorded on `producer` and waited for on `waiter`.  A no-op when the two are the same stream.
 int stream_order_after(hipStream_t waiter, hipStream_t producer);
 
+// ggnn_range_sum_f32 with the choice of adding to out's contents (ggnn_scatter.hip): the native attention training step sums a
+// layer's attention-factor gradients over its timesteps straight into the optimizer's gradient view.
+int range_sum(const float* values, const int64_t* range_off, int num_ranges, float* out, int accumulate, hipStream_t stream);
+
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): `done` is a per-kernel bitmask of the devices that have
 // it (the attribute is per device; one process may drive several).  Thread-safe; a lost race only repeats the call.
 template <class Kernel>

@@ -399,9 +399,10 @@ __global__ __launch_bounds__(256) void weighted_segment_sum_kernel(
     }
 }
 
-// out[b] = sum of values[off[b] .. off[b+1])   (one block per range, fixed-order tree: deterministic)
+// out[b] (+)= sum of values[off[b] .. off[b+1])   (one block per range, fixed-order tree: deterministic)
 struct RangeOffsets { long long off[kMaxTypes + 1]; };
-__global__ __launch_bounds__(256) void range_sum_kernel(const float* __restrict__ values, RangeOffsets ro, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void range_sum_kernel(const float* __restrict__ values, RangeOffsets ro, float* __restrict__ out,
+                                                        int accumulate) {
     __shared__ float red[256];
     const long long beg = ro.off[blockIdx.x], end = ro.off[blockIdx.x + 1];
     float s = 0.f;
@@ -412,7 +413,7 @@ __global__ __launch_bounds__(256) void range_sum_kernel(const float* __restrict_
         if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    if (threadIdx.x == 0) out[blockIdx.x] = accumulate ? out[blockIdx.x] + red[0] : red[0];
 }
 
 __global__ void unsorted_segment_sum_kernel(const float* __restrict__ data, const int* __restrict__ ids,
@@ -661,13 +662,19 @@ extern "C" int ggnn_weighted_segment_sum_f32(const float* rows, const int32_t* r
     return GGNN_OK;
 }
 
-extern "C" int ggnn_range_sum_f32(const float* values, const int64_t* range_off, int num_ranges, float* out, ggnn_stream_t stream) {
+namespace ggnn {
+int range_sum(const float* values, const int64_t* range_off, int num_ranges, float* out, int accumulate, hipStream_t stream) {
     GGNN_CHECK_ARG(num_ranges >= 0 && num_ranges <= kMaxTypes && range_off && out, "bad ranges");
     if (num_ranges == 0) return GGNN_OK;
     RangeOffsets ro;
     for (int b = 0; b <= num_ranges; ++b) { ro.off[b] = range_off[b]; GGNN_CHECK_ARG(b == 0 || range_off[b] >= range_off[b - 1], "ranges not monotone"); }
     GGNN_CHECK_ARG(values || ro.off[num_ranges] == ro.off[0], "null pointer");
-    hipLaunchKernelGGL(range_sum_kernel, dim3(num_ranges), dim3(256), 0, (hipStream_t)stream, values, ro, out);
+    hipLaunchKernelGGL(range_sum_kernel, dim3(num_ranges), dim3(256), 0, stream, values, ro, out, accumulate);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
+}
+}  // namespace ggnn
+
+extern "C" int ggnn_range_sum_f32(const float* values, const int64_t* range_off, int num_ranges, float* out, ggnn_stream_t stream) {
+    return ggnn::range_sum(values, range_off, num_ranges, out, 0, (hipStream_t)stream);
 }

@@ -10,6 +10,15 @@
 // lock) fresh-batch epochs ran at 6.9-7.3 ms per step instead of 6.1.  Here a step is two calls; nothing is allocated (one
 // caller-provided workspace, laid out by train_layout below), nothing synchronises.
 //
+// With propagation attention (:147-149, 170-196) on the compacted route (params['compact_attention'] == 'native') the same two
+// sequences run as ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32: the segment sum is
+// ggnn_gather_segment_sum_attn_compact_f32 in front of ggnn_gru_packed_f32 (three launches per timestep instead of two), and in
+// the backward the unweighted transpose gather into dHc gives way to: the compact rows recomputed, ggnn_attn_bwd_target_compact_f32
+// (softmax backward per target: coef_a / coef_s / dfac per message, target-side dh), ggnn_range_sum_f32 of dfac added to the layer's
+// attention-factor gradient, and ggnn_attn_bwd_source_compact_f32 (dHc and the source-side dh in one pass).  Everything else --
+// layout, layer plan, merged products, the node sum deferred into the next GRU backward -- is shared: the drivers below take the
+// attention arguments as an optional struct and launch what they always launched without it.
+//
 // Cross-stream hazards: everything a side-stream product reads (dpc, dpg, r*h, incoming, states, dHc) has its own buffer per
 // timestep, so the main stream never waits for the side stream inside a step; the call ends with the main stream waiting for the
 // side stream's last product, which orders the next step's forward (it reuses the workspace) behind them.
@@ -28,11 +37,13 @@ inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 struct TrainLayout {
     size_t Hc, state, r, u, c, inc, counters;           // forward
     size_t dpc, rh, dh, dpg, dx, dHc, Z, xty;            // backward
+    size_t coef, md;                                     // attention: coef_a | coef_s | dfac, md bytes each (one set: main stream only)
     size_t vd, rd, total;
     int steps;
 };
 
-TrainLayout train_layout(int V, int D, int T, int64_t R, int steps) {
+// M > 0: the layout of the attention sequences (M messages); M == 0: the default model's, unchanged
+TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 0) {
     TrainLayout L{};
     L.steps = steps;
     // per-timestep buffers follow each other WITHOUT padding (V*D*4 is a multiple of 16): the buffers of consecutive timesteps then
@@ -49,6 +60,8 @@ TrainLayout train_layout(int V, int D, int T, int64_t R, int steps) {
     L.dpc = take(L.vd * steps); L.rh = take(L.vd * steps); L.dh = take(L.vd * steps); L.dpg = take(2 * L.vd * steps);
     L.dx = take(L.vd * steps * kMaxNx);
     L.dHc = take(L.rd * steps); L.Z = take(L.rd);
+    L.md = al256((size_t)M * sizeof(float));
+    if (M > 0) L.coef = take(3 * L.md);
     L.xty = take(ggnn_xty_workspace_bytes((V > R ? V : (int)R) * (steps > 1 ? steps : 1), 4 * D, 2 * D, T));
     L.total = p + 256;
     (void)T;
@@ -182,6 +195,22 @@ bool merge_products() {
     return v;
 }
 
+// what the attention form of the two sequences needs beyond the default model's arguments
+struct AttnForward {
+    const int32_t* slot_pair;              // by-target slot -> src*T + type (gather_row_c is then the slot -> compact row table)
+    const float* const* factors;           // per layer: edge_type_attention_weights [T]
+    int64_t M;
+};
+struct AttnBackward {
+    const int32_t *row_ptr, *slot_pair, *slot_row, *msg_perm;        // the by-target index of the forward
+    const int64_t* msg_type_off;                                     // host [T+1]: message ids of type t (dfac is by message id)
+    const int32_t *src_node_ptr, *src_dst, *src_msg, *src_row;       // by-(source, type) slots: ggnn_attn_bwd_source_compact_f32
+    const float* const* edge_packed;                                 // forward images: the compact rows are recomputed
+    const float* const* factors;
+    float* const* g_attn;                                            // per layer: gradient view of the attention factors [T]
+    int64_t M;
+};
+
 struct LayerPlan { int first_step, steps, nres; int res[kMaxNx]; };
 
 int plan_layers(int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx, LayerPlan* plan,
@@ -255,12 +284,17 @@ extern "C" size_t ggnn_sparse_train_workspace_bytes(int V, int D, int T, int64_t
     return train_layout(V, D, T, compact_rows, total_steps).total;
 }
 
-extern "C" int ggnn_sparse_train_forward_f32(
+extern "C" size_t ggnn_sparse_attn_train_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps, int64_t M) {
+    if (V < 0 || D <= 0 || T <= 0 || total_steps <= 0 || compact_rows < 0 || M <= 0 || M >= (1LL << 31)) return 0;
+    return train_layout(V, D, T, compact_rows, total_steps, M).total;
+}
+
+static int train_forward(
         const float* h0, int V, int D, int T, const int32_t* row_ptr, const int32_t* gather_row_c, const int32_t* pair_node,
         const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
         const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* bg,
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
-        int64_t* final_state_offset, ggnn_stream_t stream) {
+        int64_t* final_state_offset, const AttnForward* at, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(h0 && row_ptr && gather_row_c && pair_node && type_row_off && ws && final_state_offset, "null pointer");
     GGNN_CHECK_ARG(edge_packed && bg && bc && gru_packed, "weights missing");
@@ -272,7 +306,8 @@ extern "C" int ggnn_sparse_train_forward_f32(
     if (int rc = plan_layers(num_layers, layer_timesteps, res_ptr, res_idx, plan, &steps)) return rc;
     const int64_t R = type_row_off[T];
     GGNN_CHECK_ARG(R > 0, "no messages in the batch");
-    const TrainLayout L = train_layout(V, D, T, R, steps);
+    GGNN_CHECK_ARG(!at || (at->slot_pair && at->factors && at->M > 0 && at->M < (1LL << 31) && (!use_avg || nin)), "attention arguments missing");
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
     char* base = static_cast<char*>(ws);
     float* Hc = reinterpret_cast<float*>(base + L.Hc);
@@ -292,12 +327,21 @@ extern "C" int ggnn_sparse_train_forward_f32(
         const int nx = P.nres + 1;
         const float* cur = states[l];                                           // :152
         GGNN_CHECK_ARG(edge_packed[l] && bg[l] && bc[l] && gru_packed[l], "layer %d: weights missing", l);
+        GGNN_CHECK_ARG(!at || at->factors[l], "layer %d: attention factors missing", l);
         for (int s = 0; s < P.steps; ++s) {                                     // :153
             const int k = P.first_step + s;
             if (int rc = ggnn_msg_transform_compact_f32(cur, nullptr, pair_node, type_row_off, Hc, const_cast<float*>(edge_packed[l]),
                                                         edge_img_bytes, V, D, T, GGNN_GRU_FMT_BF16X3, stream)) return rc;
             float* out = buf(L.state, k + 1);
-            if (int rc = ggnn_gru_packed_gather_train_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, Hc, row_ptr, gather_row_c,
+            if (at) {
+                // :170-196 the attention-weighted sum into this timestep's `incoming`, then the GRU on it (every product exact:
+                // the two-piece f16 range proof does not cover attention-weighted sums)
+                if (int rc = ggnn_gather_segment_sum_attn_compact_f32(Hc, cur, row_ptr, at->slot_pair, gather_row_c, at->factors[l], nin,
+                                                                      nullptr, use_avg ? 1 : 0, buf(L.inc, k), V, D, T, stream)) return rc;
+                xs[nx - 1] = buf(L.inc, k);
+                if (int rc = ggnn_gru_packed_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, buf(L.r, k), buf(L.u, k), buf(L.c, k), V, D,
+                                                 act, GGNN_GRU_FMT_BF16X3, counters + k, stream)) return rc;
+            } else if (int rc = ggnn_gru_packed_gather_train_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, Hc, row_ptr, gather_row_c,
                                                           use_avg ? nin : nullptr, T, use_avg ? 1 : 0, buf(L.r, k), buf(L.u, k),
                                                           buf(L.c, k), buf(L.inc, k), V, D, act,
                                                           gru_fmt ? gru_fmt[l] : GGNN_GRU_FMT_BF16X3, counters + k, stream)) return rc;
@@ -309,17 +353,21 @@ extern "C" int ggnn_sparse_train_forward_f32(
     return GGNN_OK;
 }
 
-extern "C" int ggnn_sparse_train_backward_f32(
+static int train_backward(
         const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg,
         int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
         const int32_t* rows_rp, const int32_t* rows_gather, const int32_t* rows_heads,
         const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
         const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
         float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc, float* const* g_bc,
-        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, const AttnBackward* at, ggnn_stream_t stream,
+        ggnn_stream_t side_stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0 && T <= 64, "bad sizes V=%d D=%d T=%d", V, D, T);
-    GGNN_CHECK_ARG(h0 && pair_node && type_row_off && rows_rp && rows_gather && node_rp && node_order && identity_rows && d_final && ws,
+    GGNN_CHECK_ARG(h0 && pair_node && type_row_off && (at || (rows_rp && rows_gather)) && node_rp && node_order && identity_rows && d_final && ws,
                    "null pointer");
+    GGNN_CHECK_ARG(!at || (at->row_ptr && at->slot_pair && at->slot_row && at->msg_perm && at->msg_type_off && at->src_node_ptr && at->src_dst &&
+                           at->src_msg && at->src_row && at->edge_packed && at->factors && at->g_attn && at->M > 0 && at->M < (1LL << 31)),
+                   "attention arguments missing");
     GGNN_CHECK_ARG(edge_packed_t && gru_bwd_packed && g_edge && g_Wg && g_bg && g_Wc && g_bc && d_state_ws, "weights / gradient buffers missing");
     GGNN_CHECK_ARG(!use_avg || nin, "nin is required for mean aggregation");
     GGNN_CHECK_ARG((reinterpret_cast<size_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
@@ -330,7 +378,7 @@ extern "C" int ggnn_sparse_train_backward_f32(
     const int64_t R64 = type_row_off[T];
     GGNN_CHECK_ARG(R64 > 0 && R64 < (1LL << 31), "bad compact row count");
     const int R = (int)R64;
-    const TrainLayout L = train_layout(V, D, T, R, steps);
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
     char* base = static_cast<char*>(ws);
     hipStream_t st = (hipStream_t)stream, side = side_stream ? (hipStream_t)side_stream : (hipStream_t)stream;
@@ -370,6 +418,7 @@ extern "C" int ggnn_sparse_train_backward_f32(
         const int nx = P.nres + 1;
         GGNN_CHECK_ARG(has[l + 1], "no gradient reaches the output of layer %d", l);
         GGNN_CHECK_ARG(edge_packed_t[l] && gru_bwd_packed[l] && g_edge[l] && g_Wg[l] && g_bg[l] && g_Wc[l] && g_bc[l], "layer %d: pointers missing", l);
+        GGNN_CHECK_ARG(!at || (at->edge_packed[l] && at->factors[l] && at->g_attn[l]), "layer %d: attention pointers missing", l);
         const float* g = dstate[l + 1];
         for (int s = P.steps - 1; s >= 0; --s) {
             const int k = P.first_step + s;
@@ -436,14 +485,29 @@ extern "C" int ggnn_sparse_train_backward_f32(
 
             // ---- back through the segment sum and the compacted transform (main stream)
             float* dHc = reinterpret_cast<float*>(base + L.dHc + (size_t)k * L.rd);
-            if (rows_heads) {
+            // The gradient of the step's INPUT state: not needed for the very first timestep (h0 is data: nothing upstream of it is
+            // trained, and nobody reads d_state_ws[0]) -- its transform and node sum are not run at all.
+            const bool first_step = l == 0 && s == 0;
+            if (at) {
+                // :170-196 under autodiff.  The compact rows are recomputed (one transform launch; saving them per step would cost
+                // steps * R * D floats of workspace and as many bytes written in the forward as are read back here), then the
+                // softmax backward per target node and both transpose gathers of the source side in one launch.
+                float* Hc = reinterpret_cast<float*>(base + L.Hc);
+                float* coef_a = reinterpret_cast<float*>(base + L.coef);
+                float* coef_s = reinterpret_cast<float*>(base + L.coef + L.md);
+                float* dfac = reinterpret_cast<float*>(base + L.coef + 2 * L.md);
+                if (int rc = ggnn_msg_transform_compact_f32(h_in, nullptr, pair_node, type_row_off, Hc, const_cast<float*>(at->edge_packed[l]),
+                                                            edge_img_bytes, V, D, T, GGNN_GRU_FMT_BF16X3, stream)) return rc;
+                if (int rc = ggnn_attn_bwd_target_compact_f32(Hc, h_in, dinc, at->row_ptr, at->slot_pair, at->slot_row, at->msg_perm,
+                                                              at->factors[l], coef_a, coef_s, dfac, dh_dst, 1, V, D, T, stream)) return rc;
+                if (int rc = range_sum(dfac, at->msg_type_off, T, at->g_attn[l], 1, st)) return rc;
+                if (int rc = ggnn_attn_bwd_source_compact_f32(dinc, h_in, at->src_node_ptr, at->src_dst, at->src_msg, at->src_row, coef_a,
+                                                              coef_s, dHc, first_step ? nullptr : dh_dst, V, D, stream)) return rc;
+            } else if (rows_heads) {
                 if (int rc = ggnn_gather_segment_sum_heads_f32(dinc, rows_rp, rows_gather, rows_heads, nullptr, nullptr, 0, dHc, R, D, 1, 0, stream)) return rc;
             } else {
                 if (int rc = ggnn_gather_segment_sum_f32(dinc, rows_rp, rows_gather, nullptr, nullptr, 0, dHc, R, D, 1, stream)) return rc;
             }
-            // The gradient of the step's INPUT state: not needed for the very first timestep (h0 is data: nothing upstream of it is
-            // trained, and nobody reads d_state_ws[0]) -- its transform and node sum are not run at all.
-            const bool first_step = l == 0 && s == 0;
             if (!first_step) {
                 if (int rc = ggnn_msg_transform_compact_f32(dHc, nullptr, identity_rows, type_row_off, Z, const_cast<float*>(edge_packed_t[l]),
                                                             edge_img_bytes, R, D, T, GGNN_GRU_FMT_BF16X3, stream)) return rc;
@@ -474,4 +538,63 @@ extern "C" int ggnn_sparse_train_backward_f32(
     // consumer would be the very first one, which runs no transform): a pending one here means a gradient was dropped
     GGNN_CHECK_ARG(!z_pending, "internal: a deferred node sum of the transform backward was never added (fuse_node_sum invariant)");
     return order_after(st, side);          // the caller's next launches (optimizer, next forward) see every product
+}
+
+extern "C" int ggnn_sparse_train_forward_f32(
+        const float* h0, int V, int D, int T, const int32_t* row_ptr, const int32_t* gather_row_c, const int32_t* pair_node,
+        const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+        const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* bg,
+        const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
+        int64_t* final_state_offset, ggnn_stream_t stream) {
+    return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, stream);
+}
+
+extern "C" int ggnn_sparse_train_backward_f32(
+        const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const int32_t* rows_rp, const int32_t* rows_gather, const int32_t* rows_heads,
+        const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+        const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
+        float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc, float* const* g_bc,
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
+                          rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act,
+                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, stream, side_stream);
+}
+
+// ---- the same two sequences with propagation attention on the compacted route (see the header comment) -----------------------------
+extern "C" int ggnn_sparse_attn_train_forward_f32(
+        const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr, const int32_t* slot_pair, const int32_t* slot_row,
+        const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg, int num_layers,
+        const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed,
+        const float* const* attn_factors, const float* const* bg, const float* const* bc, const float* const* gru_packed, int act,
+        void* ws, size_t ws_bytes, int64_t* final_state_offset, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(slot_pair && slot_row && attn_factors, "null pointer (attention index / factors)");
+    GGNN_CHECK_ARG(M > 0 && M < (1LL << 31), "bad message count %lld", (long long)M);
+    const AttnForward at{slot_pair, attn_factors, M};
+    return train_forward(h0, V, D, T, row_ptr, slot_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                         res_idx, edge_packed, bg, bc, gru_packed, nullptr, act, ws, ws_bytes, final_state_offset, &at, stream);
+}
+
+extern "C" int ggnn_sparse_attn_train_backward_f32(
+        const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr, const int32_t* slot_pair, const int32_t* slot_row,
+        const int32_t* msg_perm, const int64_t* msg_type_off, const int32_t* pair_node, const int64_t* type_row_off, const float* nin,
+        int use_avg, int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const int32_t* src_node_ptr, const int32_t* src_dst, const int32_t* src_msg, const int32_t* src_row,
+        const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+        const float* const* edge_packed, const float* const* edge_packed_t, const float* const* gru_bwd_packed,
+        const float* const* attn_factors, int act, float* const* g_edge, float* const* g_attn, float* const* g_Wg, float* const* g_bg,
+        float* const* g_Wc, float* const* g_bc, float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes,
+        ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    GGNN_CHECK_ARG(row_ptr && slot_pair && slot_row && msg_perm && msg_type_off && src_node_ptr && src_dst && src_msg && src_row &&
+                   edge_packed && attn_factors && g_attn, "null pointer (attention index / factors / gradient views)");
+    GGNN_CHECK_ARG(M > 0 && M < (1LL << 31), "bad message count %lld", (long long)M);
+    if (D > 0 && (ggnn_gru_is_fused(D) != 1 || !ggnn_msg_transform_compact_supported(D)))          // (what the forward call takes)
+        return fail(GGNN_E_UNSUPPORTED, "native training step: hidden size %d has no gather-fused GRU / compacted transform", D);
+    const AttnBackward at{row_ptr, slot_pair, slot_row, msg_perm, msg_type_off, src_node_ptr, src_dst, src_msg, src_row,
+                          edge_packed, attn_factors, g_attn, M};
+    return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, nullptr,
+                          nullptr, nullptr, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act, g_edge,
+                          g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, &at, stream, side_stream);
 }

@@ -1523,6 +1523,64 @@ def attn_backward_target_compact(Hc: torch.Tensor, h: torch.Tensor, d_att: torch
     return ca, cs, df
 
 
+def source_slot_rows(index: MessageIndex, comp: CompactSources) -> torch.Tensor:
+    """[M] int32: the compact row of every by-(source, type) slot (the slots of CompactBackward.source_node_index), i.e. the row of
+    the slot's (source node, type) pair.  Built once per batch (torch index arithmetic, no read-back), kept on the CompactBackward."""
+    bwd = compact_backward(index, comp)
+    rows = getattr(bwd, "_source_slot_row", None)
+    if rows is None:
+        ri = bwd.rows_index                                  # segments = compact rows, their slots in by-source order
+        R, M = comp.num_rows, index.num_messages
+        dev = index.adj.device
+        src = index._source_index
+        T = index.num_edge_types
+        # a pair's by-source slots start at row_ptr[node*T + type]; the pairs of rows_index are in compact-row order
+        length = (ri.row_ptr[1:] - ri.row_ptr[:-1]).long()
+        typ = torch.repeat_interleave(torch.arange(T, device=dev), torch.as_tensor(
+            [comp.type_row_off[t + 1] - comp.type_row_off[t] for t in range(T)], device=dev), output_size=R)
+        start = src.row_ptr.long()[comp.pair_node[:R].long() * T + typ]
+        slots = torch.repeat_interleave(start - ri.row_ptr[:-1].long(), length, output_size=M) + torch.arange(M, device=dev)
+        rows = torch.empty(M, dtype=torch.int32, device=dev)
+        rows[slots] = torch.repeat_interleave(torch.arange(R, dtype=torch.int32, device=dev), length, output_size=M)
+        bwd._source_slot_row = rows
+    return rows
+
+
+def attn_backward_source_compact(d_att: torch.Tensor, h: torch.Tensor, source_node_index: "SegmentIndex", slot_row: torch.Tensor,
+                                 num_rows: int, coef_a: torch.Tensor, coef_s: torch.Tensor, dh: Optional[torch.Tensor],
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Source-side pass of the propagation-attention backward over the compacted rows (ggnn_attn_bwd_source_compact_f32), one launch
+    for  weighted_segment_sum(d_att, rows_index, .., coef_a)  and  weighted_segment_sum(h, source_node_index, .., coef_s, out=dh,
+    accumulate=True)  -- bit for bit.  source_node_index: CompactBackward.source_node_index (segments = nodes, gather_row = target,
+    msg = message id); slot_row: source_slot_rows.  Adds the source-side state gradient to dh (None: skipped) and returns
+    dHc [num_rows, D]."""
+    lib = _lib.load()
+    _req(d_att, torch.float32, "d_att"); _req(h, torch.float32, "h")
+    _req(coef_a, torch.float32, "coef_a"); _req(coef_s, torch.float32, "coef_s"); _req(slot_row, torch.int32, "slot_row")
+    V, D = h.shape
+    sni = source_node_index
+    _req(sni.row_ptr, torch.int32, "source_node_index.row_ptr"); _req(sni.gather_row, torch.int32, "source_node_index.gather_row")
+    if sni.msg is None:
+        raise ValueError("source_node_index needs its slot -> message id table")
+    _req(sni.msg, torch.int32, "source_node_index.msg")
+    M = sni.gather_row.shape[0]
+    if d_att.shape != (V, D) or sni.num_nodes != V or sni.row_ptr.shape[0] != V + 1 or slot_row.shape[0] != M or sni.msg.shape[0] != M \
+            or coef_a.shape[0] < M or coef_s.shape[0] < M or (dh is not None and dh.shape != (V, D)):
+        raise ValueError("shape mismatch: d_att / h / dh [V,D], index over V nodes and M slots, coef_a / coef_s [M]")
+    if dh is not None:
+        _req(dh, torch.float32, "dh")
+    if out is None:
+        out = torch.empty((max(int(num_rows), 1), D), dtype=torch.float32, device=h.device)
+    else:
+        _req(out, torch.float32, "out")
+    if out.dim() != 2 or out.shape[1] != D or out.shape[0] < num_rows:
+        raise ValueError("out must be [num_rows, D]")
+    _launch("attn_bwd_source_compact", lambda: lib.ggnn_attn_bwd_source_compact_f32(
+        _ptr(d_att), _ptr(h), _ptr(sni.row_ptr), _ptr(sni.gather_row), _ptr(sni.msg), _ptr(slot_row), _ptr(coef_a), _ptr(coef_s),
+        _ptr(out), _ptr(dh), V, D, _stream()))
+    return out
+
+
 def rnn(x_segs: Sequence[torch.Tensor], h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, activation: str = "tanh") -> torch.Tensor:
     """tf.nn.rnn_cell.BasicRNNCell (chem_tensorflow_sparse.py:109-110): act([x|h] W + b)."""
     lib = _lib.load()

@@ -16,6 +16,11 @@ ggnn_dense_train_backward_f32) when its config asks for it with graph_resident_t
 native_dense_train_step below.  The sparse GCN (chem_tensorflow_gcn.py:62-82) has it on csrc/ggnn_gcn_train.hip
 (ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32) under native_training = True: gcn_eligible / native_gcn_train_step at
 the end of this file.
+
+The sparse model with propagation attention on the compacted route (chem_tensorflow_sparse.py:147-149, 170-196;
+SparseGGNNChemModel.attention_route) has it on ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32 when its
+config says compact_attention = 'native' (True keeps variants.CompactAttentionStepFn): attn_eligible / native_attn_train_step, the
+default model's step below with the attention arguments added.
 """
 from __future__ import annotations
 
@@ -137,14 +142,33 @@ def _readout_multi_backward(model, saved, dens, gviews):
 
 def model_eligible(model) -> bool:
     """The part of `eligible` that depends on the model only (run_epoch uses it to choose how batches are prefetched)."""
+    return _sparse_model_eligible(model, False)
+
+
+def attn_model_eligible(model) -> bool:
+    """The part of `attn_eligible` that depends on the model only: a sparse model whose config asks for the native step with
+    params['compact_attention'] == 'native' (read with .get: not a key of default_params, whose keys a reference checkpoint must
+    match; True keeps the autograd step) and whose attention runs on the compacted route (attention_route()), under the default
+    model's conditions otherwise -- hidden size 32 / 64 / 100 unpadded, no edge bias, no graph-state dropout, at most two residual
+    inputs per layer, the fused optimizer over exactly the trainable variables, nothing frozen, one-layer readout MLPs -- and no
+    active data-parallel context."""
+    return _sparse_model_eligible(model, True)
+
+
+def _sparse_model_eligible(model, attention: bool) -> bool:
     p = getattr(model, "params", None)
     if p is None or not hasattr(model, "_edge_weight_vars") or not torch.cuda.is_available():
         return False
     if not backward.USE_NATIVE_STEP or not backward.USE_COMPACT_TRANSFORM or not backward.TRAIN_GATHER_IN_GRU:
         return False
     D = p['hidden_size']
-    if getattr(model, "cell_type", None) != 'gru' or p['use_propagation_attention'] or p['use_edge_bias'] or not p['use_graph']:
+    if getattr(model, "cell_type", None) != 'gru' or bool(p['use_propagation_attention']) != attention or p['use_edge_bias'] \
+            or not p['use_graph']:
         return False
+    if attention:
+        dist = getattr(model, "dist", None)
+        if p.get('compact_attention') != 'native' or not model.attention_route() or (dist is not None and dist.active):
+            return False
     if torch.device(model.device).type != 'cuda':
         return False
     if model._kw != D or not ops.gru_gather_fused(D) or not ops.compact_supported(D) or D > 104 or not ops.gru_bwd_is_fused(D):
@@ -171,7 +195,17 @@ def model_eligible(model) -> bool:
 
 def eligible(model, batch_data: Dict[str, Any]) -> bool:
     """True when this step can run on the native sequences (see the module docstring)."""
-    if ops._timing is not None or not model_eligible(model):
+    return _sparse_eligible(model, batch_data, False)
+
+
+def attn_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """True when this step of a model with propagation attention can run on the native sequences: attn_model_eligible, no
+    per-launch timing, and a batch on the GPU, sorted by graph, with at least one message."""
+    return _sparse_eligible(model, batch_data, True)
+
+
+def _sparse_eligible(model, batch_data: Dict[str, Any], attention: bool) -> bool:
+    if ops._timing is not None or not _sparse_model_eligible(model, attention):
         return False
     D = model.params['hidden_size']
     if float(batch_data.get('graph_state_keep_prob', 1.0)) < 1.0:
@@ -202,6 +236,16 @@ class _Workspace:
 
 
 def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    return _native_sparse_step(model, batch_data, False)
+
+
+def native_attn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    """native_train_step with propagation attention: the same two C calls in their attention form, the same readout, loss, clip and
+    Adam; the attention factors' gradients arrive in the optimizer's gradient views like every other graph variable's."""
+    return _native_sparse_step(model, batch_data, True)
+
+
+def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> torch.Tensor:
     from .autograd import _PACKED
     lib = _lib.load()
     p = model.params
@@ -243,6 +287,8 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         # operand format of each layer's GRU forward: two-piece f16 only where this step's operands are provably in its range
         # (formats.py: max|h0|, the weights' maxima tracked across optimizer steps, tanh cell, mean aggregation), else exact bf16x3
         gru_fmts = model.gru_formats(h0, ew_keep, 1.0, training=True)
+        if attention:                      # (the range proof does not cover attention-weighted sums: every product exact)
+            gru_fmts = [ops.GRU_FMT_EXACT] * L
         fm = _i32(gru_fmts)
         if L <= 16 and USE_FUSED_PREPARE:
             # all ~120 images of the step in ONE launch, the weight-dropout mask applied on the fly (ggnn_sparse_train_prepare_f32)
@@ -272,16 +318,27 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
                 gru_bwd_packed.append(_PACKED.gru_bwd(cells[l].gates_kernel, cells[l].candidate_kernel, nxs[l], D))
 
         # ---- forward ------------------------------------------------------------------------------------------------------
-        ws_bytes = lib.ggnn_sparse_train_workspace_bytes(V, D, T, R, steps)
+        M = index.num_messages
+        if attention:
+            ws_bytes = lib.ggnn_sparse_attn_train_workspace_bytes(V, D, T, R, steps, M)
+            factors = _ptrs(model.gnn_weights.edge_type_attention_weights)
+        else:
+            ws_bytes = lib.ggnn_sparse_train_workspace_bytes(V, D, T, R, steps)
         ws, dstate = model._native_ws.get(ws_bytes, L, V, D, dev)
         tro = (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
         lt, rp, ri = _i32(p['layer_timesteps']), _i32(res_ptr), _i32(res_idx)
         bg = _ptrs([c.gates_bias for c in cells]); bc = _ptrs([c.candidate_bias for c in cells])
         final_off = ctypes.c_int64(0)
-        check(lib.ggnn_sparse_train_forward_f32(
-            h0.data_ptr(), V, D, T, index.row_ptr.data_ptr(), comp.gather_row.data_ptr(), comp.pair_node.data_ptr(), tro,
-            nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), bg, bc, _ptrs(gru_packed), fm, act,
-            ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
+        if attention:
+            ops._launch("sparse_attn_train_forward[steps=%d]" % steps, lambda: lib.ggnn_sparse_attn_train_forward_f32(
+                h0.data_ptr(), V, D, T, M, index.row_ptr.data_ptr(), index.gather_row.data_ptr(), comp.gather_row.data_ptr(),
+                comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), factors, bg, bc,
+                _ptrs(gru_packed), act, ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
+        else:
+            check(lib.ggnn_sparse_train_forward_f32(
+                h0.data_ptr(), V, D, T, index.row_ptr.data_ptr(), comp.gather_row.data_ptr(), comp.pair_node.data_ptr(), tro,
+                nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), bg, bc, _ptrs(gru_packed), fm, act,
+                ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
         off = int(final_off.value)
         final = ws[off:off + V * D * 4].view(torch.float32).view(V, D)
         model.ops['final_node_representations'] = final
@@ -308,17 +365,28 @@ def native_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         gviews = opt.sink_targets()
         d_final = (_readout_multi_backward if multi else _readout_per_task_backward)(model, saved, dens, gviews)
         gv = lambda t: gviews[t.data_ptr()]
-        check(lib.ggnn_sparse_train_backward_f32(
-            h0.data_ptr(), V, D, T, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
-            bwd.rows_index.row_ptr.data_ptr(), bwd.rows_index.gather_row.data_ptr(),
-            ops._ptr(ops.slot_heads(bwd.rows_index, bwd.rows_index.row_ptr, bwd.rows_index.gather_row, R)),
-            bwd.node_index.row_ptr.data_ptr(), bwd.node_index.gather_row.data_ptr(),
-            ops._ptr(ops.slot_heads(bwd.node_index, bwd.node_index.row_ptr, bwd.node_index.gather_row, V)),
-            bwd.identity.pair_node.data_ptr(), _ptrs(edge_packed_t), _ptrs(gru_bwd_packed), act,
-            _ptrs([gv(model._edge_weight_vars[l]) for l in range(L)]), _ptrs([gv(c.gates_kernel) for c in cells]),
-            _ptrs([gv(c.gates_bias) for c in cells]), _ptrs([gv(c.candidate_kernel) for c in cells]),
-            _ptrs([gv(c.candidate_bias) for c in cells]), d_final.data_ptr(), _ptrs(dstate), ws.data_ptr(), ws.numel(),
-            st.cuda_stream, side.cuda_stream))
+        node_heads = ops._ptr(ops.slot_heads(bwd.node_index, bwd.node_index.row_ptr, bwd.node_index.gather_row, V))
+        g_edge = _ptrs([gv(model._edge_weight_vars[l]) for l in range(L)])
+        g_cells = [_ptrs([gv(getattr(c, name)) for c in cells]) for name in ('gates_kernel', 'gates_bias', 'candidate_kernel', 'candidate_bias')]
+        if attention:
+            sni = bwd.source_node_index
+            mto = (ctypes.c_int64 * (T + 1))(*index.type_off)
+            ops._launch("sparse_attn_train_backward[steps=%d]" % steps, lambda: lib.ggnn_sparse_attn_train_backward_f32(
+                h0.data_ptr(), V, D, T, M, index.row_ptr.data_ptr(), index.gather_row.data_ptr(), comp.gather_row.data_ptr(),
+                index.msg_perm.data_ptr(), mto, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
+                sni.row_ptr.data_ptr(), sni.gather_row.data_ptr(), sni.msg.data_ptr(), ops.source_slot_rows(index, comp).data_ptr(),
+                bwd.node_index.row_ptr.data_ptr(), bwd.node_index.gather_row.data_ptr(), node_heads, bwd.identity.pair_node.data_ptr(),
+                _ptrs(edge_packed), _ptrs(edge_packed_t), _ptrs(gru_bwd_packed), factors, act, g_edge,
+                _ptrs([gv(a) for a in model.gnn_weights.edge_type_attention_weights]), *g_cells, d_final.data_ptr(), _ptrs(dstate),
+                ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
+        else:
+            check(lib.ggnn_sparse_train_backward_f32(
+                h0.data_ptr(), V, D, T, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
+                bwd.rows_index.row_ptr.data_ptr(), bwd.rows_index.gather_row.data_ptr(),
+                ops._ptr(ops.slot_heads(bwd.rows_index, bwd.rows_index.row_ptr, bwd.rows_index.gather_row, R)),
+                bwd.node_index.row_ptr.data_ptr(), bwd.node_index.gather_row.data_ptr(), node_heads,
+                bwd.identity.pair_node.data_ptr(), _ptrs(edge_packed_t), _ptrs(gru_bwd_packed), act, g_edge, *g_cells,
+                d_final.data_ptr(), _ptrs(dstate), ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
         for l, (keep, seed) in enumerate(masks):             # :91 d variable = mask / keep * d masked weights, once per layer
             g = gv(model._edge_weight_vars[l])
             ops.dropout(g, keep, seed, out=g)

@@ -216,7 +216,15 @@ int ggnn_range_sum_f32(const float* values, const int64_t* range_off, int num_ra
  *   Hc row are read.  D <= 256 (GGNN_E_UNSUPPORTED beyond), D % 4 == 0; V == 0 is a no-op; a node without messages gets the zero
  *   row (before bias).  No atomics: deterministic.
  * ggnn_attn_bwd_target_compact_f32: ggnn_attn_bwd_target_f32 (TF autodiff of :170-196, target side) with the same addressing;
- *   outputs as there (coef_a, coef_s, dfac by message id, dh (+)=). */
+ *   outputs as there (coef_a, coef_s, dfac by message id, dh (+)=).
+ * ggnn_attn_bwd_source_compact_f32: the SOURCE side of that backward, both transpose gathers in one pass over the messages leaving a
+ *   node.  By-(source, type) slots (ggnn_build_source_csr): node u's slots are node_ptr[u] .. node_ptr[u+1]-1 (every T-th entry of
+ *   that index's row_ptr), slot_dst = target node, slot_msg = message id, slot_row = compact row of the slot's (source, type) pair
+ *   (the slots of one pair are consecutive).  dHc[slot_row] = sum over the pair's slots of coef_a[msg] * d_att[dst] (every compact row
+ *   is written: each has a message);  dh[u] += sum over u's slots of coef_s[msg] * h[dst]  (dh NULL: skipped, h / coef_s unused).
+ *   Bit for bit ggnn_weighted_segment_sum_f32 over the compact rows' segments, and over the nodes' with accumulate = 1 (same slot
+ *   order, acc += w * row, dh's contents added last).  The first 4 slots' indices, coefficients and rows are loaded together.
+ *   D <= 256, D % 4 == 0; V == 0 is a no-op.  No atomics: deterministic. */
 int ggnn_gather_segment_sum_attn_compact_f32(const float* Hc, const float* h, const int32_t* row_ptr, const int32_t* slot_pair,
                                              const int32_t* slot_row, const float* type_factors, const float* nin,
                                              const float* bias, int use_avg, float* out, int V, int D, int T, ggnn_stream_t stream);
@@ -224,6 +232,9 @@ int ggnn_attn_bwd_target_compact_f32(const float* Hc, const float* h, const floa
                                      const int32_t* slot_pair, const int32_t* slot_row, const int32_t* msg_perm,
                                      const float* type_factors, float* coef_a, float* coef_s, float* dfac, float* dh, int accumulate,
                                      int V, int D, int T, ggnn_stream_t stream);
+int ggnn_attn_bwd_source_compact_f32(const float* d_att, const float* h, const int32_t* node_ptr, const int32_t* slot_dst,
+                                     const int32_t* slot_msg, const int32_t* slot_row, const float* coef_a, const float* coef_s,
+                                     float* dHc, float* dh, int V, int D, ggnn_stream_t stream);
 
 /* tf.unsorted_segment_sum in its general form (chem_tensorflow_sparse.py:198-200, 226-228):
  * out[ids[m],:] += data[m,:] with out zero-filled first; fp32 atomics, any id order.  Used for the
@@ -764,6 +775,37 @@ int ggnn_sparse_train_backward_f32(const float* h0, int V, int D, int T, const i
                                    const float* const* gru_bwd_packed, int act, float* const* g_edge, float* const* g_Wg,
                                    float* const* g_bg, float* const* g_Wc, float* const* g_bc, float* d_final, float* const* d_state_ws,
                                    void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
+
+/* The same step with propagation attention (chem_tensorflow_sparse.py:147-149, 170-196) on the compacted route: the conditions and
+ * conventions of the pair above (GRU cell, no edge bias, hidden size 32 / 64 / 100, images from ggnn_sparse_train_prepare_f32 with
+ * gru_fmt NULL: every product in GGNN_GRU_FMT_BF16X3), a batch with M >= 1 messages.  `ws`: ggnn_sparse_attn_train_workspace_bytes
+ * (0 on bad arguments), the SAME buffer for both calls.
+ *   forward:  per timestep ggnn_msg_transform_compact_f32, ggnn_gather_segment_sum_attn_compact_f32 over (row_ptr, slot_pair,
+ *     slot_row) with attn_factors[l] [T] into that timestep's `incoming`, ggnn_gru_packed_f32 saving r / u / c.
+ *   backward: per timestep, last to first: the fused GRU backward, the compact rows recomputed (edge_packed[l]),
+ *     ggnn_attn_bwd_target_compact_f32 (msg_perm: by-target slot -> message id), ggnn_range_sum_f32 of dfac over msg_type_off (HOST
+ *     [T+1]: the message ids of type t) ADDED to g_attn[l] [T], ggnn_attn_bwd_source_compact_f32 over (src_node_ptr, src_dst,
+ *     src_msg, src_row), then as above: the transform on W^T, the per-node sum, the products on `side_stream`. */
+size_t ggnn_sparse_attn_train_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps, int64_t M);
+int ggnn_sparse_attn_train_forward_f32(const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr,
+                                       const int32_t* slot_pair, const int32_t* slot_row, const int32_t* pair_node,
+                                       const int64_t* type_row_off, const float* nin, int use_avg, int num_layers,
+                                       const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+                                       const float* const* edge_packed, const float* const* attn_factors, const float* const* bg,
+                                       const float* const* bc, const float* const* gru_packed, int act, void* ws, size_t ws_bytes,
+                                       int64_t* final_state_offset, ggnn_stream_t stream);
+int ggnn_sparse_attn_train_backward_f32(const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr,
+                                        const int32_t* slot_pair, const int32_t* slot_row, const int32_t* msg_perm,
+                                        const int64_t* msg_type_off, const int32_t* pair_node, const int64_t* type_row_off,
+                                        const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+                                        const int32_t* res_ptr, const int32_t* res_idx, const int32_t* src_node_ptr,
+                                        const int32_t* src_dst, const int32_t* src_msg, const int32_t* src_row, const int32_t* node_rp,
+                                        const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+                                        const float* const* edge_packed, const float* const* edge_packed_t,
+                                        const float* const* gru_bwd_packed, const float* const* attn_factors, int act,
+                                        float* const* g_edge, float* const* g_attn, float* const* g_Wg, float* const* g_bg,
+                                        float* const* g_Wc, float* const* g_bc, float* d_final, float* const* d_state_ws, void* ws,
+                                        size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
 
 /* ---- tf.nn.dropout with a counter-based mask (chem_tensorflow_sparse.py:91 edge-weight dropout, :113-114 DropoutWrapper on the
  * new node state; chem_tensorflow_dense.py:104; utils.py:68 readout weights) ------------------------------------------------------
