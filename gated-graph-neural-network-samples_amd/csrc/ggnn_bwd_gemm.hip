@@ -271,7 +271,7 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
     using IM = std::integral_constant<int, MTM>; using IM1 = std::integral_constant<int, MTM - 1>;
     using IN = std::integral_constant<int, NTM>; using IN1 = std::integral_constant<int, NTM - 1>;
     // (the last K block can be short of whole groups: a wave whose X group is empty or smaller than MTM - 1 has no tiles there --
-    //  the host plan keeps that from happening for groups that do hold output rows, see xty_plan)
+    //  the host plan keeps that from happening for groups that do hold output rows, see xty_select)
     if (my_mt == MTM && my_nt == NTM) run(IM{}, IN{});
     else if (my_mt == MTM - 1 && my_nt == NTM) run(IM1{}, IN{});
     else if (my_mt == MTM && my_nt == NTM - 1) run(IM{}, IN1{});
@@ -298,6 +298,23 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
 #endif
 constexpr int kXtySplitWaves = 8;
 constexpr int kXtySplitMaxI = 8;
+
+// The three bf16 pieces of two operand values, cut by ROUNDING (v_cvt_pk_bf16_f32): hi = RN(a), mid = RN(a - hi), lo = a - hi - mid
+// (exact: 8 bits are left).  split_pair (ggnn_split.hpp) cuts by truncation; its pieces all carry a's sign, so what the six-product
+// form drops -- x_mid y_lo + x_lo y_mid + x_lo y_lo -- is a bias of up to 2^-21 |x y| per product.  Forward products sum 100+
+// terms of mixed sign and a batch of thousands of rows averages it out, but here BOTH operands are activations and a batch (an
+// edge type, a graph) can be a single row: a one-row product missed 4e-7 |x y| (tests/test_gpu_xty_cells.py::test_batches; 3.2e-7
+// of it the dropped part).  Rounded pieces halve |mid| and |lo| and have mixed signs: the dropped part is < 2^-23 |x y|.  Same
+// instruction count as the truncating form (3 conversions for 3 v_perm, 4 shifts / masks, 4 subtractions per pair).
+__device__ __forceinline__ void xty_split_pair(float a0, float a1, unsigned& h, unsigned& m, unsigned& l) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a0, a1}, bf16x2));
+    const float r0 = a0 - __uint_as_float(h << 16), r1 = a1 - __uint_as_float(h & 0xffff0000u);
+    m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
+    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
+    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
+}
 
 template <bool GATHER, int ROWS, int MTM, int NTM>
 __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs a) {
@@ -433,7 +450,7 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs 
                         for (int j = 0; j < 8; ++j) v[j] = col[(size_t)(32 * s + 4 * j + kq) * pitch];
                         unsigned h[4], m[4], l[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) split_pair(v[2 * q], v[2 * q + 1], h[q], m[q], l[q]);
+                        for (int q = 0; q < 4; ++q) xty_split_pair(v[2 * q], v[2 * q + 1], h[q], m[q], l[q]);
                         hi = u32x4{h[0], h[1], h[2], h[3]}; mid = u32x4{m[0], m[1], m[2], m[3]}; lo = u32x4{l[0], l[1], l[2], l[3]};
                     };
 #pragma unroll
@@ -593,7 +610,7 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_planes_kernel(XtyArgs
             char* base = reinterpret_cast<char*>(slab) + (size_t)buf * buf_b;
             unsigned h[4], m[4], l[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) split_pair(stage[2 * q][k], stage[2 * q + 1][k], h[q], m[q], l[q]);
+            for (int q = 0; q < 4; ++q) xty_split_pair(stage[2 * q][k], stage[2 * q + 1][k], h[q], m[q], l[q]);
             if (uon) {
                 const unsigned d = udbase + ((urot + (unsigned)k) & 15u) * 16u;
                 *reinterpret_cast<u32x4*>(base + d) = u32x4{h[0], h[1], h[2], h[3]};
@@ -750,24 +767,112 @@ __global__ __launch_bounds__(256) void xty_reduce_kernel(const float* __restrict
     }
 }
 
+// ---- selection: which instantiation of which kernel a product runs on --------------------------------------------------------
+// THE dispatch table: every instantiation of the three product kernels, one entry each, X(family, gathered, rows, mtm, ntm) with
+// family 0 = xty_kernel (f32 MFMA), 1 = xty_split_kernel, 2 = xty_planes_kernel (its step is 32 rows; ungathered only).  The
+// launcher instantiates from it, xty_select() looks cells up in it and ggnn_xty_cells() lists it: a kernel that is not here is
+// not compiled, and one that is here can be asked for by name (tests/test_xty_dispatch_host.py, tests/test_gpu_xty_cells.py).
+#define GGNN_XTY_ROW32(X, M) X(0, false, 32, M, 1) X(0, false, 32, M, 2) X(0, false, 32, M, 3) X(0, false, 32, M, 4)
+#define GGNN_XTY_TABLE(X)                                                                                                   \
+    GGNN_XTY_ROW32(X, 1) GGNN_XTY_ROW32(X, 2) GGNN_XTY_ROW32(X, 3) GGNN_XTY_ROW32(X, 4)                                       \
+    /* 64-row slabs exist for the group shapes whose two slabs can fit the LDS (xty_select picks them when they do) */          \
+    X(0, false, 64, 1, 1) X(0, false, 64, 1, 2) X(0, false, 64, 1, 3) X(0, false, 64, 1, 4)                                   \
+    X(0, false, 64, 2, 1) X(0, false, 64, 2, 2) X(0, false, 64, 2, 3) X(0, false, 64, 2, 4)                                   \
+    X(0, false, 64, 3, 1) X(0, false, 64, 3, 2) X(0, false, 64, 3, 3)                                                         \
+    X(0, false, 64, 4, 1) X(0, false, 64, 4, 2)                                                                               \
+    /* row-gathered X: <= 8 x 8 tiles (edge-weight gradients) */                                                             \
+    X(0, true, 64, 1, 1) X(0, true, 64, 1, 2) X(0, true, 64, 2, 1) X(0, true, 64, 2, 2)                                       \
+    /* split form (K0), operands split per wave: the shapes of the training step at D = 100.  (The row-gathered edge-weight  \
+       products, 2 x 2 tile groups per wave, measure slower in split form -- 52 vs 48 us: with so few tile pairs per operand \
+       tile the split work is not amortised -- and stay on the f32 kernel) */                                                \
+    X(1, false, 32, 4, 4) X(1, false, 32, 3, 4) X(1, false, 64, 4, 2) X(1, false, 64, 3, 2)                                   \
+    /* split form, operands split once into LDS planes */                                                                    \
+    X(2, false, 32, 4, 4) X(2, false, 32, 3, 4) X(2, false, 32, 4, 2) X(2, false, 32, 3, 2)
+
+struct XtyCell { int family; bool gathered; int rows, mtm, ntm; };
+#define GGNN_XTY_ENTRY(F, G, R, M, Nn) {F, G, R, M, Nn},
+static const XtyCell kXtyCells[] = {GGNN_XTY_TABLE(GGNN_XTY_ENTRY)};
+#undef GGNN_XTY_ENTRY
+constexpr int kXtyNumCells = (int)(sizeof(kXtyCells) / sizeof(kXtyCells[0]));
+
+static bool xty_has_cell(const XtyCell& c) {
+    for (const XtyCell& t : kXtyCells)
+        if (t.family == c.family && t.gathered == c.gathered && t.rows == c.rows && t.mtm == c.mtm && t.ntm == c.ntm) return true;
+    return false;
+}
+
+// the process defaults of the selection's switches (read once)
+static bool xty_default_split() {
+    static const bool v = [] { const char* e = getenv("GGNN_XTY_SPLIT"); return split_matrix_path() && (!e || atoi(e) != 0); }();
+    return v;
+}
+static bool xty_default_planes() {
+    static const bool v = [] { const char* e = getenv("GGNN_XTY_PLANES"); return !e || atoi(e) != 0; }();
+    return v;
+}
+static int xty_default_rows() {                                                                               // (experiments)
+    static const int v = [] { const char* e = getenv("GGNN_XTY_ROWS"); return e ? atoi(e) : 0; }();
+    return v;
+}
+
+// What a product of Kout x N outputs runs on: the geometry of a workgroup (rows: slab height of the f32 / per-wave split kernels
+// and the unit of the workgroup-row deal) and the table cell.
+struct XtySel { int rows, kb_tiles, n_tiles, kblocks, px, py; size_t lds; XtyCell cell; };
+
+static inline int xty_dma_per_wave(int rows, int pitch, int waves) { return (rows * pitch / 256 + waves - 1) / waves; }
+
+// The ONE selection function: ggnn_xty_acc_f32 launches what it returns and ggnn_xty_describe reports it.  Host arithmetic only.
+static int xty_select(int K, int N, int Kout, bool g, bool split_on, bool planes_on, int rows_override, XtySel& s) {
+    s = XtySel{};
+    const int ktiles = (Kout + 15) / 16;
+    s.kblocks = (ktiles + 15) / 16;
+    s.kb_tiles = (ktiles + s.kblocks - 1) / s.kblocks;
+    s.n_tiles = (N + 15) / 16;
+    s.px = xty_pitch(s.kb_tiles * 16); s.py = xty_pitch(s.n_tiles * 16);
+    const int mtm = (s.kb_tiles + 3) / 4, ntm = (s.n_tiles + 3) / 4;
+    // 64-row slabs when two of them fit the 160 KiB of LDS (half the barriers, and a slab's MFMA time then covers the latency of the
+    // next slab's DMA also for the narrow edge-weight products) and a wave's share of a slab fits its kXtyMaxI DMA instructions (a
+    // 16-tile operand, pitch 272, does not: 68 instructions per 64 rows), else 32
+    const bool fits64 = (size_t)2 * 64 * (s.px + s.py) * sizeof(float) <= (size_t)160 * 1024 && mtm + ntm <= 6 &&
+                        xty_dma_per_wave(64, s.px, kXtyWaves) <= kXtyMaxI && xty_dma_per_wave(64, s.py, kXtyWaves) <= kXtyMaxI;
+    s.rows = fits64 ? 64 : 32;
+    if (rows_override == 32) s.rows = 32;
+    s.lds = (size_t)2 * s.rows * (s.px + s.py) * sizeof(float);
+    if (xty_dma_per_wave(s.rows, s.px, kXtyWaves) > kXtyMaxI || xty_dma_per_wave(s.rows, s.py, kXtyWaves) > kXtyMaxI)
+        return fail(GGNN_E_UNSUPPORTED, "xty: slab too wide (K=%d N=%d)", K, N);
+    // split form (K0): the tile groups of a wave must come out as (MTM or MTM-1) x (2 NTM .. 2 NTM - 2) tiles: true whenever no
+    // group is empty
+    if (split_on && s.kb_tiles >= 4 && s.n_tiles >= 4 && xty_dma_per_wave(s.rows, s.px, kXtySplitWaves) <= kXtySplitMaxI &&
+        xty_dma_per_wave(s.rows, s.py, kXtySplitWaves) <= kXtySplitMaxI) {
+        // operands split once into LDS planes (xty_planes_kernel; GGNN_XTY_PLANES=0: the per-wave split below): ungathered X, both
+        // plane buffers within the 160 KiB of LDS, every unit of a step owned by a thread
+        if (planes_on && !g && (size_t)2 * 192 * 16 * (s.kb_tiles + s.n_tiles) <= (size_t)160 * 1024 &&
+            16 * (s.kb_tiles + s.n_tiles) <= kXtySplitWaves * 64) {
+            s.cell = XtyCell{2, false, 32, mtm, ntm};
+            if (xty_has_cell(s.cell)) return GGNN_OK;
+        }
+        s.cell = XtyCell{1, g, s.rows, mtm, ntm};
+        if (xty_has_cell(s.cell)) return GGNN_OK;
+    }
+    s.cell = XtyCell{0, g, s.rows, mtm, ntm};
+    if (xty_has_cell(s.cell)) return GGNN_OK;
+    return fail(GGNN_E_UNSUPPORTED, "xty: no kernel for %d x %d tile groups (K=%d N=%d%s)", mtm, ntm, K, N, g ? ", row-gathered" : "");
+}
+
+// the checks of the product's sizes that ggnn_xty_acc_f32 and ggnn_xty_describe share
+static int xty_check_sizes(int K, int N) {
+    GGNN_CHECK_ARG(K > 0 && K % 4 == 0, "K = %d must be a positive multiple of 4", K);
+    GGNN_CHECK_ARG(N > 0 && N % 4 == 0 && N <= 256, "N = %d must be a multiple of 4, <= 256", N);
+    return GGNN_OK;
+}
+
 struct XtyPlan { int rows, kb_tiles, n_tiles, kblocks, px, py, wg_rows; size_t lds; int wg_off[kXtyMaxBatch + 1]; };
 
 // Workgroup rows (one 16-wave workgroup per CU and K block) are dealt to the batches in proportion to their row counts, at least
 // one per non-empty batch and at most one per 4 slabs of rows; an empty batch gets none (its product is the empty sum, 0).
-static XtyPlan xty_plan(const int* row_off, int nbatch, int Kout, int N) {
+static XtyPlan xty_plan(const int* row_off, int nbatch, const XtySel& s) {
     XtyPlan p{};
-    const int ktiles = (Kout + 15) / 16;
-    p.kblocks = (ktiles + 15) / 16;
-    p.kb_tiles = (ktiles + p.kblocks - 1) / p.kblocks;
-    p.n_tiles = (N + 15) / 16;
-    p.px = xty_pitch(p.kb_tiles * 16); p.py = xty_pitch(p.n_tiles * 16);
-    // 64-row slabs when two of them fit the 160 KiB of LDS (half the barriers, and a slab's MFMA time then covers the latency of the
-    // next slab's DMA also for the narrow edge-weight products), else 32
-    const int mtm = (p.kb_tiles + 3) / 4, ntm = (p.n_tiles + 3) / 4;
-    p.rows = (size_t)2 * 64 * (p.px + p.py) * sizeof(float) <= (size_t)160 * 1024 && mtm + ntm <= 6 ? 64 : 32;
-    static const int rows_env = [] { const char* e = getenv("GGNN_XTY_ROWS"); return e ? atoi(e) : 0; }();   // (experiments)
-    if (rows_env == 32) p.rows = 32;
-    p.lds = (size_t)2 * p.rows * (p.px + p.py) * sizeof(float);
+    p.rows = s.rows; p.kb_tiles = s.kb_tiles; p.n_tiles = s.n_tiles; p.kblocks = s.kblocks; p.px = s.px; p.py = s.py; p.lds = s.lds;
     long long total = 0;
     for (int b = 0; b < nbatch; ++b) total += row_off[b + 1] - row_off[b];
     int target = num_cus() / p.kblocks;
@@ -837,6 +942,13 @@ static int launch_xty_split(const XtyArgs& a, const XtyPlan& p, float* C, float*
     return GGNN_OK;
 }
 
+template <int F, bool GATHER, int ROWS, int MTM, int NTM>
+static int launch_xty_cell(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, int accumulate, hipStream_t st) {
+    if constexpr (F == 2) return launch_xty_planes<MTM, NTM>(a, p, C, Cb, accumulate, st);
+    else if constexpr (F == 1) return launch_xty_split<GATHER, ROWS, MTM, NTM>(a, p, C, Cb, accumulate, st);
+    else return launch_xty<GATHER, ROWS, MTM, NTM>(a, p, C, Cb, accumulate, st);
+}
+
 // ---- deterministic column sums -----------------------------------------------------------------------------------------
 constexpr int kColsumBlocks = 256;
 
@@ -896,7 +1008,7 @@ extern "C" int ggnn_xty_acc_f32(const float* const* x_segs, int nseg, int Dseg, 
     const int Kout = ones_row ? K + 1 : K;
     GGNN_CHECK_ARG(!Cb || ones_row, "a bias destination needs the ones row");
     GGNN_CHECK_ARG(nseg >= 1 && nseg <= 4 && Dseg > 0 && Dseg % 4 == 0 && K == nseg * Dseg, "X is nseg <= 4 segments of Dseg columns (K = %d, nseg = %d, Dseg = %d)", K, nseg, Dseg);
-    GGNN_CHECK_ARG(N > 0 && N % 4 == 0 && N <= 256, "N = %d must be a multiple of 4, <= 256", N);
+    if (int rc = xty_check_sizes(K, N)) return rc;
     GGNN_CHECK_ARG(nbatch >= 1 && nbatch <= kXtyMaxBatch && row_off && C && ldx, "bad batch description");
     GGNN_CHECK_ARG(ldy >= N && ldy % 4 == 0, "ldy %d", ldy);
     hipStream_t st = (hipStream_t)stream;
@@ -919,50 +1031,44 @@ extern "C" int ggnn_xty_acc_f32(const float* const* x_segs, int nseg, int Dseg, 
         a.X[s] = x_segs[s]; a.ldx[s] = ldx[s];
     }
     if (ws_bytes < ggnn_xty_workspace_bytes(m_max, K, N, nbatch)) return fail(GGNN_E_WORKSPACE, "xty workspace too small");
-    const XtyPlan p = xty_plan(row_off, nbatch, Kout, N);
+    XtySel sel;
+    const bool g = x_rows != nullptr;
+    if (int rc = xty_select(K, N, Kout, g, xty_default_split(), xty_default_planes(), xty_default_rows(), sel)) return rc;
+    const XtyPlan p = xty_plan(row_off, nbatch, sel);
     a.Kout = Kout;
     a.nseg = nseg; a.Dseg = Dseg; a.x_rows = x_rows; a.Y = Y; a.ldy = ldy; a.part = static_cast<float*>(ws);
     a.K = K; a.N = N; a.nbatch = nbatch; a.kb_tiles = p.kb_tiles; a.n_tiles = p.n_tiles;
     a.pitch_x = p.px; a.pitch_y = p.py;
     for (int b = 0; b <= kXtyMaxBatch; ++b) a.wg_off[b] = p.wg_off[b <= nbatch ? b : nbatch];
     { const char* e = getenv("GGNN_XTY_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
-    if ((p.rows * p.px / 256 + kXtyWaves - 1) / kXtyWaves > kXtyMaxI || (p.rows * p.py / 256 + kXtyWaves - 1) / kXtyWaves > kXtyMaxI)
-        return fail(GGNN_E_UNSUPPORTED, "xty: slab too wide (K=%d N=%d)", K, N);
-    const int mtm = (p.kb_tiles + 3) / 4, ntm = (p.n_tiles + 3) / 4;
-    const bool g = x_rows != nullptr;
-    // split form (K0): the shapes of the training step at D = 100 (the others stay on the f32 kernel); the tile groups of a
-    // wave must come out as (MTM or MTM-1) x (2 NTM .. 2 NTM - 2) tiles: true whenever no group is empty
-    static const bool xty_split = [] { const char* e = getenv("GGNN_XTY_SPLIT"); return !e || atoi(e) != 0; }();
-    if (split_matrix_path() && xty_split && p.kb_tiles >= 4 && p.n_tiles >= 4 && (p.rows * p.px / 256 + kXtySplitWaves - 1) / kXtySplitWaves <= kXtySplitMaxI &&
-        (p.rows * p.py / 256 + kXtySplitWaves - 1) / kXtySplitWaves <= kXtySplitMaxI) {
-        // operands split once into LDS planes (xty_planes_kernel; GGNN_XTY_PLANES=0: the per-wave split below): ungathered X, both
-        // plane buffers within the 160 KiB of LDS, every unit of a step owned by a thread
-        static const bool xty_planes = [] { const char* e = getenv("GGNN_XTY_PLANES"); return !e || atoi(e) != 0; }();
-        if (xty_planes && !g && (size_t)2 * 192 * 16 * (p.kb_tiles + p.n_tiles) <= (size_t)160 * 1024 &&
-            16 * (p.kb_tiles + p.n_tiles) <= kXtySplitWaves * 64) {
-#define GGNN_XTYP_CASE(M, Nn) if (mtm == M && ntm == Nn) return launch_xty_planes<M, Nn>(a, p, C, Cb, accumulate, st);
-            GGNN_XTYP_CASE(4, 4) GGNN_XTYP_CASE(3, 4) GGNN_XTYP_CASE(4, 2) GGNN_XTYP_CASE(3, 2)
-#undef GGNN_XTYP_CASE
-        }
-#define GGNN_XTYS_CASE(G, R, M, Nn) if (g == G && p.rows == R && mtm == M && ntm == Nn) return launch_xty_split<G, R, M, Nn>(a, p, C, Cb, accumulate, st);
-        GGNN_XTYS_CASE(false, 32, 4, 4) GGNN_XTYS_CASE(false, 32, 3, 4) GGNN_XTYS_CASE(false, 64, 4, 2) GGNN_XTYS_CASE(false, 64, 3, 2)
-        // (the row-gathered edge-weight products, 2 x 2 tile groups per wave, measure slower in split form -- 52 vs 48 us: with so
-        //  few tile pairs per operand tile the split work is not amortised -- and stay on the f32 kernel)
-#undef GGNN_XTYS_CASE
+    const XtyCell& c = sel.cell;
+#define GGNN_XTY_LAUNCH(F, G, R, M, Nn)                                                                     \
+    if (c.family == F && c.gathered == G && c.rows == R && c.mtm == M && c.ntm == Nn)                        \
+        return launch_xty_cell<F, G, R, M, Nn>(a, p, C, Cb, accumulate, st);
+    GGNN_XTY_TABLE(GGNN_XTY_LAUNCH)
+#undef GGNN_XTY_LAUNCH
+    return fail(GGNN_E_UNSUPPORTED, "xty: selected cell is not in the dispatch table (K=%d N=%d)", K, N);
+}
+
+extern "C" int ggnn_xty_describe(int K, int N, int ones_row, int gathered, int matrix_split, int planes, int rows_override,
+                                 int32_t out[8]) {
+    GGNN_CHECK_ARG(out, "null output");
+    if (int rc = xty_check_sizes(K, N)) return rc;
+    XtySel s;
+    const int rc = xty_select(K, N, ones_row ? K + 1 : K, gathered != 0, matrix_split < 0 ? xty_default_split() : matrix_split != 0,
+                              planes < 0 ? xty_default_planes() : planes != 0, rows_override < 0 ? xty_default_rows() : rows_override, s);
+    if (rc) return rc;
+    out[0] = s.cell.family; out[1] = s.cell.gathered ? 1 : 0; out[2] = s.cell.rows; out[3] = s.cell.mtm; out[4] = s.cell.ntm;
+    out[5] = s.kblocks; out[6] = s.kb_tiles; out[7] = s.n_tiles;
+    return GGNN_OK;
+}
+
+extern "C" int ggnn_xty_cells(int32_t* out, int capacity) {
+    for (int i = 0; out && i < kXtyNumCells && i < capacity; ++i) {
+        const XtyCell& c = kXtyCells[i];
+        out[5 * i] = c.family; out[5 * i + 1] = c.gathered ? 1 : 0; out[5 * i + 2] = c.rows; out[5 * i + 3] = c.mtm; out[5 * i + 4] = c.ntm;
     }
-#define GGNN_XTY_CASE(G, R, M, Nn) if (g == G && p.rows == R && mtm == M && ntm == Nn) return launch_xty<G, R, M, Nn>(a, p, C, Cb, accumulate, st);
-#define GGNN_XTY_ROW32(M) GGNN_XTY_CASE(false, 32, M, 1) GGNN_XTY_CASE(false, 32, M, 2) GGNN_XTY_CASE(false, 32, M, 3) GGNN_XTY_CASE(false, 32, M, 4)
-    GGNN_XTY_ROW32(1) GGNN_XTY_ROW32(2) GGNN_XTY_ROW32(3) GGNN_XTY_ROW32(4)
-    // 64-row slabs exist for the group shapes whose two slabs can fit the LDS (xty_plan picks them when they do)
-    GGNN_XTY_CASE(false, 64, 1, 1) GGNN_XTY_CASE(false, 64, 1, 2) GGNN_XTY_CASE(false, 64, 1, 3) GGNN_XTY_CASE(false, 64, 1, 4)
-    GGNN_XTY_CASE(false, 64, 2, 1) GGNN_XTY_CASE(false, 64, 2, 2) GGNN_XTY_CASE(false, 64, 2, 3) GGNN_XTY_CASE(false, 64, 2, 4)
-    GGNN_XTY_CASE(false, 64, 3, 1) GGNN_XTY_CASE(false, 64, 3, 2) GGNN_XTY_CASE(false, 64, 3, 3)
-    GGNN_XTY_CASE(false, 64, 4, 1) GGNN_XTY_CASE(false, 64, 4, 2)
-    // row-gathered X: one segment of <= 128 columns (edge-weight gradients)
-    GGNN_XTY_CASE(true, 64, 1, 1) GGNN_XTY_CASE(true, 64, 1, 2) GGNN_XTY_CASE(true, 64, 2, 1) GGNN_XTY_CASE(true, 64, 2, 2)
-#undef GGNN_XTY_ROW32
-#undef GGNN_XTY_CASE
-    return fail(GGNN_E_UNSUPPORTED, "xty: no kernel for %d x %d tile groups (K=%d N=%d)", mtm, ntm, K, N);
+    return kXtyNumCells;
 }
 
 extern "C" size_t ggnn_colsum_workspace_bytes(int N) { return (size_t)kColsumBlocks * (N > 0 ? N : 1) * sizeof(float) + 256; }

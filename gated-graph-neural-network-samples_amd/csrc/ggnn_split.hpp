@@ -5,7 +5,9 @@
 // 16 clocks, 2.5 PF), and there is no TF32-like middle.  An f32 value is EXACTLY the sum of three bf16 values
 //     a = a_hi + a_mid + a_lo        (8 + 8 + 8 significand bits; bf16 has the f32 exponent range)
 // so the f32 product a*b is the sum of nine bf16 x bf16 products, each of which is exact in f32 (16-bit significands).
-// Dropping the three smallest (a_mid*b_lo, a_lo*b_mid, a_lo*b_lo: < 2^-23 |a b| together) leaves SIX products
+// Dropping the three smallest (a_mid*b_lo, a_lo*b_mid, a_lo*b_lo: < 2^-21 |a b| together for ONE product -- the pieces are cut by
+// truncation, so all carry a's sign and the dropped part is a bias, 2^-24 |a b| on average; measured on a one-row X^T dY product:
+// 3.2e-7, tests/test_gpu_xty_cells.py::test_batches, which is why the X^T dY kernels cut by rounding: xty_split_pair) leaves SIX products
 //     a_hi b_hi + (a_hi b_mid + a_mid b_hi) + (a_mid b_mid + a_hi b_lo + a_lo b_hi)
 // accumulated in f32 by the MFMA: 6 MFMAs of k = 32 do the work of 8 MFMAs of k = 4 x 32 clocks -- 96 clocks instead of
 // 256 per 16 x 16 x 32 block -- with an error bound no worse than the f32 FMA chain's (one rounding per k there, one per

@@ -378,7 +378,9 @@ def xty(x_segs: Sequence[torch.Tensor], dy: torch.Tensor, x_rows: Optional[torch
         row_off: Optional[Sequence[int]] = None, ones_row: bool = False, add_to: Optional[torch.Tensor] = None,
         add_bias_to: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Weight-gradient product  concat(x_segs, dim=1)^T @ dy  on ggnn_xty_f32 (no concat materialised; deterministic).
-    x_segs: [M', Dseg] float32 tensors with unit column stride (any row stride: column slices are fine); dy [M, N], N <= 208.
+    x_segs: [M', Dseg] float32 tensors with unit column stride (any row stride: column slices are fine), Dseg % 4 == 0;
+    dy [M, N], N % 4 == 0, N <= 256.  Row-gathered products (x_rows) take K + ones_row <= 128 and N <= 128; every other shape
+    in that domain has a kernel (include/ggnn_hip.h; ggnn_xty_describe tells which).
     x_rows (int32 [M]): row r of the X operand is x_segs[.][x_rows[r]] (edge-weight gradients on compact rows).
     row_off (host ints [B+1]): B independent products over the row ranges -> [B, K, N]; default one product -> [K, N].
     ones_row: the result has K + 1 rows, the last one the column sums of dy (the bias gradient next to the weight gradient).

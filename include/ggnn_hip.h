@@ -572,8 +572,12 @@ int ggnn_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, float* C,
  *   X is given as nseg <= 4 column segments of Dseg columns each (HOST arrays x_segs / ldx: pointers and row strides), so the
  *   [residuals | incoming | h] operand of the GRU kernels is never concatenated; x_rows (device int32, or NULL) gathers the X
  *   rows (edge-weight gradients: X row of compact row r = h[pair_node[r]]); row_off HOST [nbatch+1] splits the rows into batches
- *   with one [K,N] output each (one per edge type).  K = nseg * Dseg, N <= 208, N % 4 == 0.  Deterministic (fixed-order split
- *   reduction).  ones_row != 0: X gets a virtual column of ones, i.e. C is [K+1, N] per batch and its last row is the column
+ *   with one [K,N] output each (one per edge type).  Deterministic (fixed-order split reduction).
+ *   Accepted: nseg 1..4, Dseg % 4 == 0, K = nseg * Dseg (tested up to K = 1024: the product is cut into ceil(ceil(Kout / 16) / 16)
+ *   K blocks of <= 16 tiles), N % 4 == 0 and N <= 256, 1 <= nbatch <= 64; anything else is GGNN_E_INVALID.  With Kout = K +
+ *   (ones_row != 0), REFUSED inside that domain (GGNN_E_UNSUPPORTED) is exactly: x_rows != NULL with Kout > 128 or N > 128
+ *   (the row-gathered kernels hold <= 8 x 8 tiles), and every row-gathered product under the experiment GGNN_XTY_ROWS=32 (they
+ *   exist with 64-row slabs only).  Every ungathered shape has a kernel on both matrix paths.  ones_row != 0: X gets a virtual column of ones, i.e. C is [K+1, N] per batch and its last row is the column
  *   sum of Y -- the bias gradient comes out of the same pass.  ws: ggnn_xty_workspace_bytes(largest batch, K, N, nbatch).
  * ggnn_colsum_f32: out[n] = sum_v Y[v, n]  (bias gradients), deterministic.
  * ggnn_gru_bwd_dx_cand_f32:  P = dpc Wc^T (WcT = Wc^T, [D, (nx+1)D] row-major):  dx [V, nx*D] = P[:, x columns];
@@ -591,6 +595,15 @@ int ggnn_xty_f32(const float* const* x_segs, int nseg, int Dseg, const int32_t* 
 int ggnn_xty_acc_f32(const float* const* x_segs, int nseg, int Dseg, const int32_t* ldx, const int32_t* x_rows, const float* Y,
                      int ldy, float* C, float* Cb, int accumulate, int K, int N, int ones_row, const int32_t* row_off, int nbatch,
                      void* ws, size_t ws_bytes, ggnn_stream_t stream);
+/* Which kernel ggnn_xty_acc_f32 runs for a shape -- the launcher's own selection function, host arithmetic only (never touches
+ * the GPU).  gathered: x_rows != NULL.  matrix_split / planes / rows_override: 0 or 1 / 0 or 1 / 0 or 32 for the switches
+ * GGNN_MATRIX (with GGNN_XTY_SPLIT), GGNN_XTY_PLANES, GGNN_XTY_ROWS; -1 = this process's value.  out = {family (0 f32 MFMA, 1 split
+ * per wave, 2 split into LDS planes), gathered, rows per slab, mtm, ntm (tiles of a wave's largest X / dY group), K blocks, X
+ * tiles per K block, dY tiles}.  Returns what ggnn_xty_acc_f32 returns for these sizes (GGNN_E_INVALID / GGNN_E_UNSUPPORTED / 0).
+ * ggnn_xty_cells: the dispatch table, {family, gathered, rows, mtm, ntm} per instantiation into out (up to `capacity` entries;
+ * out may be NULL); returns the number of instantiations. */
+int ggnn_xty_describe(int K, int N, int ones_row, int gathered, int matrix_split, int planes, int rows_override, int32_t out[8]);
+int ggnn_xty_cells(int32_t* out, int capacity);
 size_t ggnn_colsum_workspace_bytes(int N);
 int ggnn_colsum_f32(const float* Y, int ldy, int M, int N, float* out, void* ws, size_t ws_bytes, ggnn_stream_t stream);
 int ggnn_gru_bwd_dx_cand_f32(const float* dpc, const float* WcT, const float* h, const float* r, float* dx, float* dh,
