@@ -197,6 +197,15 @@ SYMBOLS = {
     "ggnn_gcn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ggnn_gcn_propagate_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p),
                                        POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ggnn_gcn_panel_supported": (c_int, [c_int]),
+    "ggnn_gcn_panel_image_bytes": (c_size_t, [c_int]),
+    "ggnn_gcn_panel_launch_geometry": (None, [POINTER(c_int), POINTER(c_int)]),
+    "ggnn_gcn_panel_pack_weights_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_gcn_panel_layer_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                         c_uint64, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ggnn_gcn_panel_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ggnn_gcn_panel_propagate_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p),
+                                             POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
     "ggnn_gcn_layer_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_uint64,
                                        c_float, c_void_p, c_int, c_int, c_void_p]),
     "ggnn_gcn_train_pack_f32": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),

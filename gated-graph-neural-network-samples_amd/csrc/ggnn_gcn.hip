@@ -22,8 +22,7 @@
 // Memory per layer at V = 1e5, D = 100, ~3.1 nonzeros per row: x is read ~once through L2 (each row is gathered by ~3 neighbours
 // of nearby rows), out written once, the CSR read once -- about 83 MB, against ~245 MB for the segment sum + GEMM + epilogue
 // composition.
-#include "ggnn_split.hpp"
-#include "ggnn_philox.hpp"
+#include "ggnn_gcn.hpp"
 
 namespace ggnn {
 namespace {
@@ -55,42 +54,6 @@ __global__ __launch_bounds__(256) void gcn_train_pack_kernel(GcnPackList w, int 
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     if (transpose) pack_split_image<D, kSplitBf16x3>(StageValueT<D>{W, 0, 0, D}, img, first, stride);
     else pack_split_image<D, kSplitBf16x3>(StageValue<D>{W, 0, 0, D, -1, nullptr, 0, 0, -1}, img, first, stride);
-}
-
-template <int D>
-__device__ __forceinline__ void frag_fma(Frag<D>& a, float w, const Frag<D>& t) {
-#pragma unroll
-    for (int c = 0; c < StageCfg<D>::NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a.v[c][e] = __builtin_fmaf(w, t.v[c][e], a.v[c][e]);
-#pragma unroll
-    for (int q = 0; q < StageCfg<D>::NR; ++q) a.r[q] = __builtin_fmaf(w, t.r[q], a.r[q]);
-}
-
-struct GcnEpilogue {
-    const float* bias;          // [D] or null
-    int relu;
-    const int64_t* row_key;     // [V] or null: row_key_base + row
-    int64_t row_key_base;
-    uint32_t k0, k1;            // dropout seed
-    float keep;                 // >= 1: no dropout
-};
-
-// tf.nn.dropout's factor for the 4 columns 4q .. 4q+3 of a row: the expression of ggnn_dropout_f32, term for term
-__device__ __forceinline__ f32x4 gcn_epilogue(f32x4 v, int row, int col, const GcnEpilogue& ep) {
-    if (ep.bias) v += *reinterpret_cast<const f32x4*>(ep.bias + col);
-    if (ep.relu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.f ? 0.f : v[e];
-    }
-    if (ep.keep < 1.0f) {
-        const uint64_t key = (uint64_t)(ep.row_key ? ep.row_key[row] : ep.row_key_base + row);
-        uint32_t u[4];
-        philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)(col >> 2), 0u, ep.k0, ep.k1, u);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] / ep.keep * floorf(ep.keep + (float)(u[e] >> 8) * (1.0f / 16777216.0f));
-    }
-    return v;
 }
 
 // d v / d P of out = dropout(relu(P)) given out: ggnn_act_bwd_f32's ReLU select, term for term
@@ -192,8 +155,6 @@ __global__ __launch_bounds__(256) void gcn_epilogue_kernel(const float* __restri
     }
 }
 
-size_t align256g(size_t x) { return (x + 255) / 256 * 256; }
-
 template <int D>
 int gcn_pack(const float* W, int transpose, float* img, hipStream_t st) {
     hipLaunchKernelGGL((gcn_pack_kernel<D>), dim3(16), dim3(256), 0, st, W, transpose, img);
@@ -242,10 +203,6 @@ int gcn_dispatch_bwd(const float* dP, const int* row_ptr_t, const int* col_t, co
         case 64: return gcn_launch<64, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
         default: return gcn_launch<32, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
     }
-}
-
-bool gcn_epilogue_args(const float* bias, float keep_prob) {
-    return (keep_prob > 0.0f && keep_prob <= 1.0f) && (!bias || aligned16(bias));
 }
 
 }  // namespace

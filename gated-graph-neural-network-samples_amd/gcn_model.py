@@ -3,7 +3,8 @@
     out = dropout(relu(A_hat h W_l + b_l))          (ReLU and dropout on all but the last layer; chem_tensorflow_gcn.py:68-80)
 
 running as one fused aggregate-transform HIP launch (csrc/ggnn_gcn.hip) at hidden sizes 32 / 64 / 100, and as the composition
-weighted segment sum -> GEMM -> epilogue at the others.  Inference runs all layers behind one native call
+weighted segment sum -> GEMM -> epilogue at the others -- or, with params['gcn_panel_layers'] = True, as one launch of the
+column-panel kernel (csrc/ggnn_gcn_panel.hip) at hidden sizes 128 / 192 / 256.  Inference runs all layers behind one native call
 (ggnn_gcn_propagate_f32); training runs GCNLayerFn per layer (hand-written backward, no autograd on the kernels), or with
 params['native_training'] = True the whole step as two native calls (train_native.native_gcn_train_step, csrc/ggnn_gcn_train.hip).
 The readout and loss are the fused kernels of the sparse GGNN (chem_tensorflow_gcn.py:84-93 is the same formula).
@@ -55,11 +56,13 @@ class GCNLayerFn(torch.autograd.Function):
     """One GCN layer with its hand-written backward.  With P = S W + b, S = A_hat x, out = drop(relu(P)):
         dP = act_bwd(dropout(dOut), out)   (identity on the linear layer)
         dW = S^T dP (ggnn_gemm_tn_f32), db = colsum(dP), dx = A_hat^T (dP W^T) (the same layer launch on the transposed CSR).
-    Inside backward.weight_gradient_sink the dW / db products go to the optimiser's flat gradient buffer on the side stream."""
+    Inside backward.weight_gradient_sink the dW / db products go to the optimiser's flat gradient buffer on the side stream.
+    panel: the layer launch and the dx launch take ops.gcn_layer's panel route (hidden sizes 128 / 192 / 256)."""
 
     @staticmethod
-    def forward(ctx, x, W, b, graph, relu, keep_prob, seed, row_key):
-        out, S = ops.gcn_layer(x.contiguous(), graph, W, b, relu, keep_prob, seed, row_key, save_s=True)
+    def forward(ctx, x, W, b, graph, relu, keep_prob, seed, row_key, panel=False):
+        out, S = ops.gcn_layer(x.contiguous(), graph, W, b, relu, keep_prob, seed, row_key, save_s=True, panel=bool(panel))
+        ctx.panel = bool(panel)
         ctx.save_for_backward(S, out, W)
         ctx.graph, ctx.relu, ctx.keep, ctx.seed, ctx.row_key = graph, bool(relu), float(keep_prob), int(seed), row_key
         ctx.w_ptr = W.data_ptr()
@@ -88,8 +91,8 @@ class GCNLayerFn(torch.autograd.Function):
                 dW = _tn(S, dP)
             if has_b and ctx.needs_input_grad[2]:
                 db = ops.colsum(dP)
-        dx = ops.gcn_layer(dP, ctx.graph, W, transpose=True)[0] if ctx.needs_input_grad[0] else None
-        return dx, dW, db, None, None, None, None, None
+        dx = ops.gcn_layer(dP, ctx.graph, W, transpose=True, panel=ctx.panel)[0] if ctx.needs_input_grad[0] else None
+        return dx, dW, db, None, None, None, None, None, None
 
 
 class SparseGCNChemModel(ChemModel):
@@ -107,7 +110,8 @@ class SparseGCNChemModel(ChemModel):
                        })
         # (params['pack_on_device'], default False, is read with .get like the sparse model's: a key in this dict would break
         # restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340.  So is
-        # params['native_training'], default False: the optimisation step on train_native.native_gcn_train_step)
+        # params['native_training'], default False: the optimisation step on train_native.native_gcn_train_step, and
+        # params['gcn_panel_layers'], default False: hidden sizes 128 / 192 / 256 on the column-panel kernel, gcn_panel_route)
         return params
 
     DERIVED_PLACEHOLDERS = dict(ChemModel.DERIVED_PLACEHOLDERS, adjacency_list=('gcn_graph',), adjacency_weights=('gcn_graph',))
@@ -160,6 +164,12 @@ class SparseGCNChemModel(ChemModel):
             graph = ph['gcn_graph'] = ops.gcn_graph(ph['adjacency_list'], ph['adjacency_weights'], V, self.device)
         return graph
 
+    def gcn_panel_route(self) -> bool:
+        """params['gcn_panel_layers'] (default False) asks for the column-panel layer kernel (csrc/ggnn_gcn_panel.hip); it is
+        available on a CUDA/HIP device at hidden sizes 128 / 192 / 256.  Anywhere else the key changes nothing."""
+        return bool(self.params.get('gcn_panel_layers')) and torch.device(self.device).type == 'cuda' \
+            and ops.gcn_panel_supported(self.params['hidden_size'])
+
     def compute_final_node_representations(self) -> torch.Tensor:
         """chem_tensorflow_gcn.py:62-82."""
         ph = self.placeholders
@@ -171,8 +181,12 @@ class SparseGCNChemModel(ChemModel):
         need_grad = self.training and torch.is_grad_enabled()
         L = len(Ws)
         D = self.params['hidden_size']
-        if not need_grad and keep >= 1.0 and ops.gcn_fused_supported(D) and ops._timing is None:
-            return ops.gcn_propagate(h, graph, Ws, bs)                        # every layer in one native call
+        panel = self.gcn_panel_route()
+        if not need_grad and keep >= 1.0 and ops._timing is None:            # every layer in one native call
+            if panel:
+                return ops.gcn_panel_propagate(h, graph, Ws, bs)
+            if ops.gcn_fused_supported(D):
+                return ops.gcn_propagate(h, graph, Ws, bs)
         uid = self._node_uid() if keep < 1.0 else None
         for l in range(L):
             last = l == L - 1
@@ -180,9 +194,9 @@ class SparseGCNChemModel(ChemModel):
             seed = self.dropout_seed('gcn_state', l) if kp < 1.0 else 0
             b = bs[l] if bs is not None else None
             if need_grad:
-                h = GCNLayerFn.apply(h, Ws[l], b, graph, not last, kp, seed, uid)
+                h = GCNLayerFn.apply(h, Ws[l], b, graph, not last, kp, seed, uid, panel)
             else:
-                h = ops.gcn_layer(h, graph, Ws[l], b, relu=not last, keep_prob=kp, seed=seed, row_key=uid)[0]
+                h = ops.gcn_layer(h, graph, Ws[l], b, relu=not last, keep_prob=kp, seed=seed, row_key=uid, panel=panel)[0]
         return h
 
     def _node_uid(self) -> Optional[torch.Tensor]:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1919,14 +1919,39 @@ def gcn_pack(W: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     return img
 
 
+def gcn_panel_supported(D: int) -> bool:
+    """Hidden sizes with the column-panel fused GCN layer (128 / 192 / 256; csrc/ggnn_gcn_panel.hip)."""
+    return bool(_lib.load().ggnn_gcn_panel_supported(int(D)))
+
+
+def gcn_panel_launch_geometry() -> Tuple[int, int]:
+    """(rows a workgroup of the panel GCN layer takes per pass, the launcher's cap on workgroups)."""
+    rows, cap = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().ggnn_gcn_panel_launch_geometry(ctypes.byref(rows), ctypes.byref(cap))
+    return rows.value, cap.value
+
+
+def gcn_panel_pack(W: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """The D / 64 column-panel images of W [D, D] (or of W^T) for the panel GCN layer."""
+    lib = _lib.load()
+    _req(W, torch.float32, "W")
+    D = W.shape[0]
+    if tuple(W.shape) != (D, D) or not gcn_panel_supported(D):
+        raise ValueError("gcn_panel_pack: W must be [D, D] with D in 128 / 192 / 256 (got %s)" % (tuple(W.shape),))
+    img = torch.empty(lib.ggnn_gcn_panel_image_bytes(D) // 4, dtype=torch.float32, device=W.device)
+    _launch("gcn_panel_pack", lambda: lib.ggnn_gcn_panel_pack_weights_f32(_ptr(W), D, 1 if transpose else 0, _ptr(img), _stream()))
+    return img
+
+
 def gcn_layer(x: torch.Tensor, graph: GCNGraph, W: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
               keep_prob: float = 1.0, seed: int = 0, row_key: Optional[torch.Tensor] = None, transpose: bool = False,
-              save_s: bool = False, fused: Optional[bool] = None, img: Optional[torch.Tensor] = None):
+              save_s: bool = False, fused: Optional[bool] = None, img: Optional[torch.Tensor] = None, panel: bool = False):
     """One GCN layer  out = dropout(relu(M x W' + bias))  with M = A_hat, W' = W, or (transpose=True, the backward's
     dx = A_hat^T (dP W^T)) M = A_hat^T, W' = W^T.  -> (out, S = M x if save_s else None).
     Fused single launch for hidden sizes 32 / 64 / 100 (ggnn_gcn_layer_f32); otherwise (or fused=False) the composition
-    ggnn_weighted_segment_sum_f32 -> ggnn_gemm_f32 -> ggnn_gcn_epilogue_f32.  The dropout mask is ggnn_dropout_f32's for
-    (seed, row key, column)."""
+    ggnn_weighted_segment_sum_f32 -> ggnn_gemm_f32 -> ggnn_gcn_epilogue_f32.  panel=True (opt-in): hidden sizes 128 / 192 / 256 take
+    ONE ggnn_gcn_panel_layer_f32 launch instead of the composition (img: gcn_panel_pack's images; packed here when None); at any
+    other size the argument changes nothing.  The dropout mask is ggnn_dropout_f32's for (seed, row key, column)."""
     lib = _lib.load()
     _req(x, torch.float32, "x")
     V, D = x.shape
@@ -1942,6 +1967,13 @@ def gcn_layer(x: torch.Tensor, graph: GCNGraph, W: torch.Tensor, bias: Optional[
     out = torch.empty_like(x)
     S = torch.empty_like(x) if save_s else None
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if panel and gcn_panel_supported(D):
+        if img is None:
+            img = gcn_panel_pack(W.contiguous(), transpose)
+        _launch("gcn_panel_layer[D=%d]" % D, lambda: lib.ggnn_gcn_panel_layer_f32(
+            _ptr(x), _ptr(rp), _ptr(col), _ptr(val), graph.nnz, _ptr(img), _ptr(bias), 1 if relu else 0, _ptr(row_key), 0, seed,
+            float(keep_prob), _ptr(out), _ptr(S), V, D, _stream()))
+        return out, S
     if fused is None:
         fused = gcn_fused_supported(D)
     if fused:
@@ -2009,21 +2041,35 @@ def gcn_train_pack(weights: Sequence[torch.Tensor]) -> torch.Tensor:
     return images
 
 
-def gcn_propagate(h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
-                  biases: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-    """Inference forward of all layers (ReLU on all but the last) in one native call, ggnn_gcn_propagate_f32 (fused sizes only)."""
-    lib = _lib.load()
+def _gcn_propagate(name: str, workspace_bytes, entry, h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
+                   biases: Optional[Sequence[torch.Tensor]]) -> torch.Tensor:
+    """One whole-stack inference call: `entry` is ggnn_gcn_propagate_f32 or its panel form, `workspace_bytes` its size query."""
     _req(h0, torch.float32, "h0")
     V, D = h0.shape
     L = len(weights)
-    ws_bytes = lib.ggnn_gcn_workspace_bytes(V, D, L)
+    ws_bytes = workspace_bytes(V, D, L)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=h0.device)
     out = torch.empty_like(h0)
     Ws = [_req(w, torch.float32, "W") for w in weights]
     bs = None if biases is None else [_req(b, torch.float32, "bias") for b in biases]
     w_arr = _ptr_array(Ws)
     b_arr = None if bs is None else _ptr_array(bs)
-    _launch("gcn_propagate[D=%d,L=%d]" % (D, L), lambda: lib.ggnn_gcn_propagate_f32(
+    _launch("%s[D=%d,L=%d]" % (name, D, L), lambda: entry(
         _ptr(h0), V, D, L, _ptr(graph.row_ptr), _ptr(graph.col), _ptr(graph.val), graph.nnz, w_arr, b_arr, _ptr(out), _ptr(ws),
         ws_bytes, _stream()))
     return out
+
+
+def gcn_propagate(h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
+                  biases: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """Inference forward of all layers (ReLU on all but the last) in one native call, ggnn_gcn_propagate_f32 (fused sizes only)."""
+    lib = _lib.load()
+    return _gcn_propagate("gcn_propagate", lib.ggnn_gcn_workspace_bytes, lib.ggnn_gcn_propagate_f32, h0, graph, weights, biases)
+
+
+def gcn_panel_propagate(h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
+                        biases: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """gcn_propagate at hidden sizes 128 / 192 / 256: all layers on the panel kernel in one native call (ggnn_gcn_panel_propagate_f32)."""
+    lib = _lib.load()
+    return _gcn_propagate("gcn_panel_propagate", lib.ggnn_gcn_panel_workspace_bytes, lib.ggnn_gcn_panel_propagate_f32, h0, graph,
+                          weights, biases)

@@ -857,6 +857,28 @@ int ggnn_gcn_propagate_f32(const float* h0, int V, int D, int num_layers, const 
                            int64_t nnz, const float* const* W, const float* const* bias, float* out, void* ws, size_t ws_bytes,
                            ggnn_stream_t stream);
 
+/* ---- sparse GCN at hidden sizes 128 / 192 / 256: the same layer in one launch on column panels of W (ggnn_gcn_panel.hip) ---------
+ * A workgroup aggregates 8 x 16 rows of S = A_hat x in registers and walks the D / 64 column panels of W, whose images stream
+ * through an LDS ring; products in the exact bf16x3 split form.  Opt-in: ggnn_gcn_fused_supported and its siblings keep their values.
+ * ggnn_gcn_panel_supported: 1 for D = 128, 192, 256; every entry point below returns GGNN_E_UNSUPPORTED for any other D.
+ * ggnn_gcn_panel_pack_weights_f32: the D / 64 panel images (ggnn_gcn_panel_image_bytes(D) bytes in all, 16-byte aligned) of W [D,D],
+ *   or of W^T (transpose != 0: the backward's dx = A_hat^T (dP W^T) is the same layer call on the transposed CSR).
+ * ggnn_gcn_panel_layer_f32: the arguments, validation and results of ggnn_gcn_layer_f32 (img: the panel images).
+ * ggnn_gcn_panel_propagate_f32: ggnn_gcn_propagate_f32 on this kernel; ws: ggnn_gcn_panel_workspace_bytes(V, D, num_layers) bytes.
+ * ggnn_gcn_panel_launch_geometry: rows a workgroup takes per pass and the launcher's cap on workgroups (a launch wraps beyond
+ *   their product); either pointer may be NULL. */
+int ggnn_gcn_panel_supported(int D);
+size_t ggnn_gcn_panel_image_bytes(int D);
+void ggnn_gcn_panel_launch_geometry(int* rows_per_workgroup, int* max_workgroups);
+int ggnn_gcn_panel_pack_weights_f32(const float* W, int D, int transpose, float* img, ggnn_stream_t stream);
+int ggnn_gcn_panel_layer_f32(const float* x, const int32_t* row_ptr, const int32_t* col, const float* val, int64_t nnz,
+                             const float* img, const float* bias, int relu, const int64_t* row_key, int64_t row_key_base,
+                             uint64_t seed, float keep_prob, float* out, float* s_out, int V, int D, ggnn_stream_t stream);
+size_t ggnn_gcn_panel_workspace_bytes(int V, int D, int num_layers);
+int ggnn_gcn_panel_propagate_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col,
+                                 const float* val, int64_t nnz, const float* const* W, const float* const* bias, float* out,
+                                 void* ws, size_t ws_bytes, ggnn_stream_t stream);
+
 /* ---- sparse GCN: the optimisation step as native launch sequences (ggnn_gcn.hip, ggnn_gcn_train.hip) -----------------------------
  * ggnn_gcn_layer_bwd_f32: the backward of one layer with the gate of the layer BELOW in its epilogue, one launch:
  *     out = [gate_out > 0] * dropout(A_hat^T (dP W^T))      = the dP of the layer below

@@ -21,6 +21,13 @@ rounds of `--step-iters` steps each:
   step_ms        per arm: median and min .. max over the rounds of the device-event time per step
   enqueue_ms     per arm: median host time per step to enqueue it (no synchronisation inside the timed loop)
   native_faster  True only if the native arm's whole range lies below the autograd arm's
+--hidden 128 / 192 / 256 (the column-panel kernel, csrc/ggnn_gcn_panel.hip; opt-in params['gcn_panel_layers']): both legs compare the
+panel route with the composed route (weighted segment sum -> GEMM -> epilogue, what these sizes run without the key) in one
+process, `--rounds` interleaved rounds:
+  --leg layer    one ReLU layer (images pre-packed), its transposed form (the backward's dx launch) and the inference forward of all
+                 layers, per arm median and min .. max over the rounds of the device-event time of `--iters` launches
+  --leg step     one training step through GCNLayerFn on either route
+  panel_faster   True only if the panel arm's whole range lies below the composed arm's
 --out FILE also writes the JSON there.
 """
 import argparse
@@ -137,7 +144,95 @@ def _step_round(model, feed, iters):
     return s.elapsed_time(e) / iters, host * 1e3 / iters
 
 
+def _spread(values, digits=2):
+    return {"median": round(float(np.median(values)), digits), "min": round(min(values), digits), "max": round(max(values), digits),
+            "rounds": [round(v, digits) for v in values]}
+
+
+def _emit(a, out):
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+def _panel_models(a, ms):
+    cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
+    return {name: ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms,
+                                               "--config": dict(cfg, **extra)})
+            for name, extra in (("composed", {}), ("panel", {"gcn_panel_layers": True}))}
+
+
+def panel_layer_leg(a):
+    """One layer, its transposed form and the inference forward at a panel size: panel route against composed route, interleaved."""
+    ops = ggnn_amd.ops
+    ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
+    models = _panel_models(a, ms)
+    assert models["panel"].gcn_panel_route() and not models["composed"].gcn_panel_route()
+    feed = next(iter(models["panel"].make_minibatch_iterator(models["panel"].valid_data, is_training=False)))
+    g, h0 = feed['gcn_graph'], feed['initial_node_representation']
+    V, D = h0.shape
+    x = torch.randn((V, D), device=h0.device)
+    W = models["panel"].weights['edge_weights'][0]
+    img, img_t = ops.gcn_panel_pack(W), ops.gcn_panel_pack(W, True)
+    for m in models.values():
+        m.feed(feed)
+    work = {
+        "layer_us": {"panel": lambda: ops.gcn_layer(x, g, W, relu=True, img=img, panel=True),
+                     "composed": lambda: ops.gcn_layer(x, g, W, relu=True)},
+        "layer_transposed_us": {"panel": lambda: ops.gcn_layer(x, g, W, transpose=True, img=img_t, panel=True),
+                                "composed": lambda: ops.gcn_layer(x, g, W, transpose=True)},
+        "forward_us": {name: m.compute_final_node_representations for name, m in models.items()},
+    }
+    csr = (V + 1) * 4 + g.nnz * 8
+    out = {"metric": "sparse GCN layer on column panels, synthetic QM9", "V": V, "nnz": g.nnz, "D": D, "layers": 4, "rounds": a.rounds,
+           "launches_per_round": a.iters, "bytes_panel": 2 * V * D * 4 + csr, "bytes_composed": 6 * V * D * 4 + csr + g.nnz * 4}
+    with torch.no_grad():
+        for what, arms in work.items():
+            iters = max(a.iters // 4, 1) if what == "forward_us" else a.iters
+            times = {name: [] for name in arms}
+            for _ in range(a.rounds):                       # interleaved: both arms see the same clocks and the same neighbours
+                for name, fn in arms.items():
+                    times[name].append(timed(fn, iters) * 1e3)
+            out[what] = {name: _spread(t) for name, t in times.items()}
+            out[what]["panel_faster"] = bool(max(times["panel"]) < min(times["composed"]))
+            out[what]["speedup_median"] = round(float(np.median(times["composed"]) / np.median(times["panel"])), 3)
+    out["roof_fraction_panel"] = round(out["bytes_panel"] / HBM_ROOF / (out["layer_us"]["panel"]["median"] * 1e-6), 3)
+    out["roof_fraction_composed"] = round(out["bytes_composed"] / HBM_ROOF / (out["layer_us"]["composed"]["median"] * 1e-6), 3)
+    _emit(a, out)
+
+
+def panel_step_leg(a):
+    """One training step through GCNLayerFn at a panel size: panel route against composed route, interleaved."""
+    ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
+    arms = {}
+    for name, model in _panel_models(a, ms).items():
+        np.random.seed(0)
+        feed = dict(next(iter(model.make_minibatch_iterator(model.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
+        assert model.gcn_panel_route() == (name == "panel"), name
+        arms[name] = (model, feed)
+    V, D = arms["panel"][1]["initial_node_representation"].shape
+    for model, feed in arms.values():                       # warm-up: workspaces, caching allocator, LDS attributes
+        _step_round(model, feed, 5)
+    dev = {n: [] for n in arms}
+    host = {n: [] for n in arms}
+    for _ in range(a.rounds):
+        for name, (model, feed) in arms.items():
+            d, h = _step_round(model, feed, a.step_iters)
+            dev[name].append(d); host[name].append(h)
+    out = {"metric": "sparse GCN training step on column panels, synthetic QM9", "V": int(V), "nnz": arms["panel"][1]["gcn_graph"].nnz,
+           "D": int(D), "layers": 4, "rounds": a.rounds, "steps_per_round": a.step_iters}
+    for name in arms:
+        out[name] = {"step_ms": _spread(dev[name], 4), "enqueue_ms_median": round(float(np.median(host[name])), 4)}
+    out["panel_faster"] = bool(max(dev["panel"]) < min(dev["composed"]))
+    out["speedup_median"] = round(float(np.median(dev["composed"]) / np.median(dev["panel"])), 3)
+    _emit(a, out)
+
+
 def step_leg(a):
+    if ggnn_amd.ops.gcn_panel_supported(a.hidden):
+        return panel_step_leg(a)
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
     cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
     arms = {}
@@ -188,6 +283,8 @@ def main():
         return step_leg(a)
     if a.leg != "layer":
         return (epoch_leg if a.leg == "epoch" else pack_leg)(a)
+    if ggnn_amd.ops.gcn_panel_supported(a.hidden):
+        return panel_layer_leg(a)
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
     cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
     model = ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms, "--config": cfg})
