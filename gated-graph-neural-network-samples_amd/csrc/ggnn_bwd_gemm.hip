@@ -5,10 +5,10 @@
 //                     column segments (the [x | incoming | h] concat is never materialised), optionally row-gathered
 //                     (edge-weight gradients: X rows = h[pair_node[r]]), optionally batched over row ranges (one output per
 //                     edge type).  Rows are split over the whole GPU; partial products are added in a FIXED order.
+//                     Three product kernels (xty_kernel: f32 MFMA; xty_split_kernel, xty_planes_kernel: bf16x3) over one shared
+//                     layer -- row range, slab loader, 8-wave tile groups, accumulator store, six products, selection ladder.
 //   ggnn_colsum_f32   db = 1^T dY       deterministic two-phase column sum
-//   ggnn_gru_bwd_dx_cand_f32 / _gates_f32
-//                     dX = dY W^T on the FP32-MFMA GEMM core (ggnn_gemm.hpp) with the GRU gate algebra in the epilogue, so
-//                     that neither the [V,K] product nor r*h / dpr round-trip through HBM as separate passes.
+// (The dX = dY W^T products with the GRU gate algebra in the epilogue, ggnn_gru_bwd_dx_*, live in ggnn_gemm.hip.)
 //
 // ggnn_xty_f32 design (FP32 MFMA 16x16x4, 157 TF peak):  the contraction runs over ROWS, so both operands are needed as
 // "4 consecutive rows x 16 consecutive columns" fragments.  Row slabs (32 or 64 rows) of X and dY are brought into LDS by LDS-DMA
@@ -27,8 +27,13 @@ namespace ggnn {
 constexpr int kXtyMaxBatch = 64;
 constexpr int kXtyWaves = 16;
 constexpr int kXtyMaxI = 4;                    // decoded DMA instructions per wave, operand and slab
+constexpr int kXtySplitWaves = 8;              // the two bf16x3 kernels: 8 waves of 256 registers
+constexpr int kXtySplitMaxI = 8;
 #ifndef GGNN_XTY_TIMELINE
 #define GGNN_XTY_TIMELINE 0
+#endif
+#ifndef GGNN_XTY_INTER_MAX
+#define GGNN_XTY_INTER_MAX 24
 #endif
 
 // 16-byte DMA sources that are not operand data: the chunk of X that holds the "ones" column K (Kout == K + 1: row K of the
@@ -64,9 +69,204 @@ __host__ __device__ inline void xty_group(int n, int g, int& off, int& cnt) {
     off = g * base + (g < rem ? g : rem);
 }
 
-// Slab loader: a slab is a linear run of 16-byte chunks (row-major, `cpr` chunks per row); DMA instruction j of a wave moves
-// chunks [64*(j*16 + wave), +64).  chunk -> (row in slab, segment, column in segment) is fixed per lane, so it is decoded once
-// and kept packed: bits 0-15 column within the segment, 16-17 segment, 18-24 row in slab, 31 = padding chunk.
+// ---- the layer the three product kernels share ----------------------------------------------------------------------------------
+
+// Row range: workgroup row wg_row (blockIdx.y) belongs to one batch and owns the rows [r_beg, r_end) of it -- the batch's rows
+// dealt evenly over its workgroup rows, in whole units of ROWS -- and the partial product `out` [Kout][N].
+struct XtyRange { int batch, r_beg, r_end; float* out; };
+
+template <int ROWS>
+__device__ __forceinline__ XtyRange xty_row_range(const XtyArgs& a, unsigned wg_row) {
+    int batch = 0;
+    while (batch + 1 < a.nbatch && (int)wg_row >= a.wg_off[batch + 1]) ++batch;
+    const int split = (int)wg_row - a.wg_off[batch], splits = a.wg_off[batch + 1] - a.wg_off[batch];
+    const int rb = a.row_off[batch], re = a.row_off[batch + 1];
+    int rows_per = (re - rb + splits - 1) / splits;
+    rows_per = (rows_per + ROWS - 1) / ROWS * ROWS;
+    const int r_beg = rb + split * rows_per;
+    return XtyRange{batch, r_beg, min(re, r_beg + rows_per), a.part + (size_t)wg_row * a.Kout * a.N};
+}
+
+// a pointer as a VALUE in scalar registers (readfirstlane: otherwise the compiler selects the ADDRESS of the kernel argument and
+// loads through it, see the slab loader's issue())
+__device__ __forceinline__ const float* xty_sgpr_ptr(const float* p) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
+}
+
+// One 1-KiB LDS-DMA instruction with per-lane source addresses, in the two flavours of the slab kernels: the builtin (the
+// compiler counts it: xty_kernel), or inline assembly (M0 = the wave's LDS destination), which the compiler does not see in
+// flight and the kernel waits for itself (dma_wait() before the barrier: xty_split_kernel).
+__device__ __forceinline__ void xty_dma_builtin(const float* src, float* dst) {
+    __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+}
+__device__ __forceinline__ void xty_dma_asm(const float* src, float* dst) {
+    const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_void*)dst);
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(l), "v"(src) : "memory");
+}
+
+// Slab loader of the two slab kernels: a slab is a linear run of 16-byte chunks (row-major, `cpr` chunks per row) of X, [2][ROWS]
+// [pitch_x] floats at `slab` (sx), and of dY behind it, [2][ROWS][pitch_y] (sy); DMA instruction j of a wave moves chunks
+// [64*(j*NW + wave), +64).  chunk -> (row in slab, segment, column in segment) is fixed per lane, so it is decoded once and kept
+// packed: bits 0-15 column within the segment, 16-17 segment, 18-24 row in slab, 30 = the chunk [1 0 0 0] of the ones column,
+// 31 = padding chunk (no instruction).  NW waves, <= MAXI instructions per wave, operand and slab; DMA: xty_dma_builtin / _asm.
+// It declares, in the kernel's scope (which provides a, slab, lane, wave, kcol0, r_beg, r_end, GATHER and ROWS):
+//   px, py, sx, sy       pitches and the two slab pairs
+//   fetch_rows(r0)       (GATHER) the X rows of the slab at r0, into rid[]: called one slab ahead of its issue()
+//   issue(buf, r0)       the DMA of the slab at r0 into buffer buf
+// A macro, not a class: with the loader's state in one object the f32 kernels allocate 2-3 registers more, keep LDS addresses in
+// vector registers and measure 1 % slower (profiles/xty_shared_layer_timing.json); as locals of the kernel the code is the same
+// as written out in place.
+// Two measured reasons inside: the segment bases / strides are held as VALUES in scalar registers (xty_sgpr_ptr), and the
+// segment, a per-lane value, selects base and stride with compares -- indexing the kernel-argument arrays with it makes the
+// compiler spill them to memory, and the loads that fetch them back sit in the same in-order queue as the DMA: every slab
+// instruction then waited for the previous one.
+#define GGNN_XTY_SLAB_LOADER(NW, MAXI, DMA)                                                                                     \
+    const int px = a.pitch_x, py = a.pitch_y;                                                                                   \
+    float* sx = slab;                                                                                                           \
+    float* sy = slab + 2 * ROWS * px;                                                                                           \
+    const int cprx = px / 4, cpry = py / 4;                                                                                     \
+    const int nix = ROWS * cprx / 64, niy = ROWS * cpry / 64;      /* 1-KiB instructions per slab */                            \
+    unsigned mx[MAXI], my[MAXI];                                                                                                \
+    _Pragma("unroll") for (int j = 0; j < MAXI; ++j) {                                                                          \
+        const int ix = j * NW + wave;                                                                                           \
+        mx[j] = 0x80000000u; my[j] = 0x80000000u;                                                                               \
+        if (ix < nix) {                                                                                                         \
+            const int c = ix * 64 + lane, row = c / cprx, q = c - row * cprx;                                                   \
+            int col = kcol0 + 4 * q;                                                                                            \
+            const bool ones = a.Kout > a.K && col == a.K && 4 * q < a.kb_tiles * 16;      /* the chunk [1 0 0 0] of the ones column */ \
+            if (!(4 * q < a.kb_tiles * 16 && col < a.K)) col = 0;            /* padding chunk: any valid address */              \
+            const int seg = col / a.Dseg, within = col - seg * a.Dseg;                                                          \
+            mx[j] = (unsigned)within | ((unsigned)seg << 16) | ((unsigned)row << 18) | (ones ? 0x40000000u : 0u);               \
+        }                                                                                                                       \
+        if (ix < niy) {                                                                                                         \
+            const int c = ix * 64 + lane, row = c / cpry, q = c - row * cpry;                                                   \
+            my[j] = (unsigned)(4 * q < a.N ? 4 * q : 0) | ((unsigned)row << 18);                                                \
+        }                                                                                                                       \
+    }                                                                                                                           \
+    /* operand row of slab row r (X: before the row gather of the edge-weight gradients); rows past the range are clamped   */  \
+    /* here and X's are zeroed in issue()                                                                                   */  \
+    auto xrow = [&](int r0, unsigned m) __attribute__((always_inline)) -> int {                                                 \
+        int r = r0 + (int)((m >> 18) & 127u); r = r < r_end ? r : r_end - 1;                                                    \
+        return r;                                                                                                               \
+    };                                                                                                                          \
+    int rid[GATHER ? MAXI : 1];                                     /* (GATHER) X rows of the NEXT slab to be issued */         \
+    auto fetch_rows = [&](int r0) __attribute__((always_inline)) {                                                              \
+        if constexpr (GATHER) {                                                                                                 \
+            _Pragma("unroll") for (int j = 0; j < MAXI; ++j)                                                                    \
+                rid[j] = (mx[j] >> 31) ? 0 : a.x_rows[xrow(r0 < r_end ? r0 : r_beg, mx[j])];                                    \
+        }                                                                                                                       \
+    };                                                                                                                          \
+    const float* X0 = xty_sgpr_ptr(a.X[0]); const float* X1 = xty_sgpr_ptr(a.X[1]);                                             \
+    const float* X2 = xty_sgpr_ptr(a.X[2]); const float* X3 = xty_sgpr_ptr(a.X[3]);                                             \
+    const int L0 = __builtin_amdgcn_readfirstlane(a.ldx[0]), L1 = __builtin_amdgcn_readfirstlane(a.ldx[1]);                     \
+    const int L2 = __builtin_amdgcn_readfirstlane(a.ldx[2]), L3 = __builtin_amdgcn_readfirstlane(a.ldx[3]);                     \
+    const float* Yb = xty_sgpr_ptr(a.Y);                                                                                        \
+    const int ldy = __builtin_amdgcn_readfirstlane(a.ldy);                                                                      \
+    auto issue = [&](int buf, int r0) __attribute__((always_inline)) {          /* uses rid[] (fetched one slab ahead) */       \
+        _Pragma("unroll") for (int j = 0; j < MAXI; ++j) {                                                                      \
+            if (!(mx[j] >> 31)) {                                                                                               \
+                const unsigned m = mx[j];                                                                                       \
+                const int seg = (int)((m >> 16) & 3u);                                                                          \
+                const float* xb = seg == 0 ? X0 : (seg == 1 ? X1 : (seg == 2 ? X2 : X3));                                       \
+                const int xl = seg == 0 ? L0 : (seg == 1 ? L1 : (seg == 2 ? L2 : L3));                                          \
+                const int xr = GATHER ? rid[GATHER ? j : 0] : xrow(r0, m);                                                      \
+                const float* src = xb + (size_t)xr * xl + (m & 0xFFFFu);                                                        \
+                if (m & 0x40000000u) src = kXtyOnesChunk;                                                                       \
+                if (r0 + (int)((m >> 18) & 127u) >= r_end) src = kXtyZeroChunk;                                                 \
+                float* dst = sx + buf * ROWS * px + (size_t)(j * NW + wave) * 256;      /* 1 KiB = 256 floats per instruction */ \
+                DMA(src, dst);                                                                                                  \
+            }                                                                                                                   \
+        }                                                                                                                       \
+        _Pragma("unroll") for (int j = 0; j < MAXI; ++j) {                                                                      \
+            if (!(my[j] >> 31)) {                                                                                               \
+                const unsigned m = my[j];                                                                                       \
+                const float* src = Yb + (size_t)xrow(r0, m) * ldy + (m & 0xFFFFu);                                              \
+                float* dst = sy + buf * ROWS * py + (size_t)(j * NW + wave) * 256;                                              \
+                DMA(src, dst);                                                                                                  \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    }
+
+// Tile groups of a wave of the 8-wave kernels: wave w owns X group w >> 1 (tiles kt0 .. kt0 + my_mt - 1 of the K block) and TWO
+// dY groups, (w >> 1) + 2 (w & 1) and the next one (mod 4): its dY tile t is tile(t), t < nt().
+struct XtyWaveTiles {
+    int kt0, my_mt, nta0, cnta, ntb0, cntb;
+    __device__ __forceinline__ int nt() const { return cnta + cntb; }
+    __device__ __forceinline__ int tile(int t) const { return t < cnta ? nta0 + t : ntb0 + (t - cnta); }
+};
+
+__device__ __forceinline__ XtyWaveTiles xty_wave_tiles(const XtyArgs& a, int wave) {
+    XtyWaveTiles w;
+    xty_group(a.kb_tiles, wave >> 1, w.kt0, w.my_mt);
+    const int ga = ((wave >> 1) + 2 * (wave & 1)) & 3;
+    xty_group(a.n_tiles, ga, w.nta0, w.cnta);
+    xty_group(a.n_tiles, (ga + 1) & 3, w.ntb0, w.cntb);
+    return w;
+}
+
+// The six products of the tile pairs (X tile mt, dY tile nt), mt < MT, smallest terms first, product-major over the X tiles
+// (consecutive MFMAs hit different accumulators).
+template <int MT, int NT>
+__device__ __forceinline__ void xty_six_products(f32x4 (&acc)[MT][NT], int nt, const u32x4 (&xh)[MT], const u32x4 (&xm)[MT],
+                                                 const u32x4 (&xl)[MT], u32x4 yh, u32x4 ym, u32x4 yl) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xl[mt], yh, acc[mt][nt]);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xm[mt], ym, acc[mt][nt]);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xm[mt], yh, acc[mt][nt]);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xh[mt], yl, acc[mt][nt]);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xh[mt], ym, acc[mt][nt]);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(xh[mt], yh, acc[mt][nt]);
+}
+
+// Accumulator store.  Tile (mt, nt): lane (li, kq) holds dW[kcol0 + 16 (kt0 + mt) + 4 kq + e][col(nt) + li], e = 0..3; col(nt) is
+// the first column of the wave's dY tile nt.  (A workgroup without rows still writes its zeros: the reduction adds every workgroup
+// row.)
+template <int MT, int NT, class Col>
+__device__ __forceinline__ void xty_store_acc(const XtyArgs& a, float* out, const f32x4 (&acc)[MT][NT], int kcol0, int kt0, int li,
+                                              int kq, Col col) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int k0 = kcol0 + (kt0 + mt) * 16;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int n = col(nt) + li;
+            if (n < a.N) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int k = k0 + 4 * kq + e;
+                    if (k < a.Kout) out[(size_t)k * a.N + n] = acc[mt][nt][e];
+                }
+            }
+        }
+    }
+}
+
+// Selection ladder of the 8-wave kernels: run(MT, NT) with the wave's tile counts as constants, MTM or MTM-1 X tiles by 2 NTM,
+// 2 NTM - 1 or 2 NTM - 2 dY tiles, or (0, 0) for a wave without tiles (why the whole slab loop is instantiated per count and
+// selected once: see xty_kernel).
+template <int MTM, int NTM, class Run>
+__device__ __forceinline__ void xty_run_selected(int my_mt, int my_nt, Run&& run) {
+    using I0 = std::integral_constant<int, 0>;
+    using IM = std::integral_constant<int, MTM>; using IM1 = std::integral_constant<int, MTM - 1>;
+    using IN = std::integral_constant<int, 2 * NTM>; using IN1 = std::integral_constant<int, 2 * NTM - 1>;
+    using IN2 = std::integral_constant<int, 2 * NTM - 2>;
+    if (my_mt == MTM && my_nt == 2 * NTM) run(IM{}, IN{});
+    else if (my_mt == MTM && my_nt == 2 * NTM - 1) run(IM{}, IN1{});
+    else if (my_mt == MTM && my_nt == 2 * NTM - 2) run(IM{}, IN2{});
+    else if (my_mt == MTM - 1 && my_nt == 2 * NTM) run(IM1{}, IN{});
+    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 1) run(IM1{}, IN1{});
+    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 2) run(IM1{}, IN2{});
+    else run(I0{}, I0{});
+}
+
+// ---- X^T dY on the f32 MFMA ---------------------------------------------------------------------------------------------------
 template <bool GATHER, int ROWS, int MTM, int NTM>   // MTM / NTM: tiles of the largest X / dY group (the others have one less or as many)
 __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float slab[];     // [2][ROWS][pitch_x] | [2][ROWS][pitch_y]
@@ -74,19 +274,9 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
-    int batch = 0;
-    while (batch + 1 < a.nbatch && (int)blockIdx.y >= a.wg_off[batch + 1]) ++batch;
-    const int split = (int)blockIdx.y - a.wg_off[batch], splits = a.wg_off[batch + 1] - a.wg_off[batch];
-    const int rb = a.row_off[batch], re = a.row_off[batch + 1];
-    int rows_per = (re - rb + splits - 1) / splits;
-    rows_per = (rows_per + ROWS - 1) / ROWS * ROWS;
-    const int r_beg = rb + split * rows_per;
-    const int r_end = min(re, r_beg + rows_per);
+    const XtyRange rg = xty_row_range<ROWS>(a, blockIdx.y);
+    const int r_beg = rg.r_beg, r_end = rg.r_end;
     const int kcol0 = blockIdx.x * a.kb_tiles * 16;                  // first X column of this workgroup
-    const int px = a.pitch_x, py = a.pitch_y;
-    float* sx = slab;
-    float* sy = slab + 2 * ROWS * px;
-    float* out = a.part + (size_t)blockIdx.y * a.Kout * a.N;
 
     // this wave's tile groups
     int kt0, my_mt, nt0, my_nt;
@@ -102,84 +292,7 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
 #define GGNN_XT(K)
 #endif
     GGNN_XT(0)
-
-    // ---- per-lane decode of the DMA chunks ---------------------------------------------------------------------------
-    constexpr int MAXI = kXtyMaxI;
-    const int cprx = px / 4, cpry = py / 4;
-    const int nix = ROWS * cprx / 64, niy = ROWS * cpry / 64;      // 1-KiB instructions per slab
-    unsigned mx[MAXI], my[MAXI];
-#pragma unroll
-    for (int j = 0; j < MAXI; ++j) {
-        const int ix = j * nw + wave;
-        mx[j] = 0x80000000u; my[j] = 0x80000000u;
-        if (ix < nix) {
-            const int c = ix * 64 + lane, row = c / cprx, q = c - row * cprx;
-            int col = kcol0 + 4 * q;
-            const bool ones = a.Kout > a.K && col == a.K && 4 * q < a.kb_tiles * 16;      // the chunk [1 0 0 0] of the ones column
-            if (!(4 * q < a.kb_tiles * 16 && col < a.K)) col = 0;            // padding chunk: any valid address
-            const int seg = col / a.Dseg, within = col - seg * a.Dseg;
-            mx[j] = (unsigned)within | ((unsigned)seg << 16) | ((unsigned)row << 18) | (ones ? 0x40000000u : 0u);
-        }
-        if (ix < niy) {
-            const int c = ix * 64 + lane, row = c / cpry, q = c - row * cpry;
-            my[j] = (unsigned)(4 * q < a.N ? 4 * q : 0) | ((unsigned)row << 18);
-        }
-    }
-    // X row of slab row r (row gather for the edge-weight gradients); rows past the range are clamped here and zeroed in issue()
-    auto xrow = [&](int r0, unsigned m) -> int {
-        int r = r0 + (int)((m >> 18) & 127u); r = r < r_end ? r : r_end - 1;
-        return r;
-    };
-    int rid[GATHER ? MAXI : 1];                                     // (GATHER) X rows of the NEXT slab to be issued
-    auto fetch_rows = [&](int r0) {
-        if constexpr (GATHER) {
-#pragma unroll
-            for (int j = 0; j < MAXI; ++j) rid[j] = (mx[j] >> 31) ? 0 : a.x_rows[xrow(r0 < r_end ? r0 : r_beg, mx[j])];
-        }
-    };
-    // segment bases / strides as VALUES in scalar registers (readfirstlane: otherwise the compiler selects the ADDRESS
-    // of the kernel argument and loads through it, see below)
-    auto sgpr_ptr = [](const float* p) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-    };
-    const float* X0 = sgpr_ptr(a.X[0]); const float* X1 = sgpr_ptr(a.X[1]);
-    const float* X2 = sgpr_ptr(a.X[2]); const float* X3 = sgpr_ptr(a.X[3]);
-    const int L0 = __builtin_amdgcn_readfirstlane(a.ldx[0]), L1 = __builtin_amdgcn_readfirstlane(a.ldx[1]);
-    const int L2 = __builtin_amdgcn_readfirstlane(a.ldx[2]), L3 = __builtin_amdgcn_readfirstlane(a.ldx[3]);
-    const float* Yb = sgpr_ptr(a.Y);
-    const int ldy = __builtin_amdgcn_readfirstlane(a.ldy);
-    auto issue = [&](int buf, int r0) {                             // uses rid[] (fetched one slab ahead)
-#pragma unroll
-        for (int j = 0; j < MAXI; ++j) {
-            if (!(mx[j] >> 31)) {
-                const unsigned m = mx[j];
-                // (the segment is a per-lane value: select base and stride with compares -- indexing the kernel-argument
-                //  arrays with it makes the compiler spill them to memory, and the loads that fetch them back sit in the
-                //  same in-order queue as the DMA: every slab instruction then waited for the previous one)
-                const int seg = (int)((m >> 16) & 3u);
-                const float* xb = seg == 0 ? X0 : (seg == 1 ? X1 : (seg == 2 ? X2 : X3));
-                const int xl = seg == 0 ? L0 : (seg == 1 ? L1 : (seg == 2 ? L2 : L3));
-                const int xr = GATHER ? rid[GATHER ? j : 0] : xrow(r0, m);
-                const float* src = xb + (size_t)xr * xl + (m & 0xFFFFu);
-                if (m & 0x40000000u) src = kXtyOnesChunk;
-                if (r0 + (int)((m >> 18) & 127u) >= r_end) src = kXtyZeroChunk;
-                float* dst = sx + buf * ROWS * px + (size_t)(j * nw + wave) * 256;      // 1 KiB = 256 floats per instruction
-                __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < MAXI; ++j) {
-            if (!(my[j] >> 31)) {
-                const unsigned m = my[j];
-                int r = r0 + (int)((m >> 18) & 127u); r = r < r_end ? r : r_end - 1;
-                const float* src = Yb + (size_t)r * ldy + (m & 0xFFFFu);
-                float* dst = sy + buf * ROWS * py + (size_t)(j * nw + wave) * 256;
-                __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
-            }
-        }
-    };
+    GGNN_XTY_SLAB_LOADER(nw, kXtyMaxI, xty_dma_builtin);
 
     // The whole slab loop is instantiated per (tiles of X, tiles of dY) of a wave -- MTM or MTM-1, NTM or NTM-1, or none -- and
     // selected ONCE: with run-time tile counts the compiler cannot count the outstanding LDS reads (s_waitcnt lgkmcnt(0) at every
@@ -246,25 +359,7 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
             }
         }
         GGNN_XT(62)
-        // accumulator tile (mt, nt): lane (li, kq) holds dW[k0 + 4*kq + e][16*(nt0+nt) + li], e = 0..3  (a workgroup without rows
-        // still writes its zeros: the reduction adds every workgroup row)
-        if constexpr (ON) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int k0 = kcol0 + (kt0 + mt) * 16;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int n = 16 * (nt0 + nt) + li;
-                    if (n < a.N) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int k = k0 + 4 * kq + e;
-                            if (k < a.Kout) out[(size_t)k * a.N + n] = acc[mt][nt][e];
-                        }
-                    }
-                }
-            }
-        }
+        if constexpr (ON) xty_store_acc(a, rg.out, acc, kcol0, kt0, li, kq, [&](int nt) { return 16 * (nt0 + nt); });
         GGNN_XT(63)
     };
     using I0 = std::integral_constant<int, 0>;
@@ -293,11 +388,6 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
 //     waves of a SIMD (w, w + 4) carry 46 / 45 / 39 / 39 pairs at 13 x 13 tiles.
 //   * the slab DMA goes out through inline assembly (the compiler does not see an LDS-DMA in flight, see dma_image_asm) and is
 //     waited for explicitly before the barrier that publishes the slab.
-#ifndef GGNN_XTY_INTER_MAX
-#define GGNN_XTY_INTER_MAX 24
-#endif
-constexpr int kXtySplitWaves = 8;
-constexpr int kXtySplitMaxI = 8;
 
 // The three bf16 pieces of two operand values, cut by ROUNDING (v_cvt_pk_bf16_f32): hi = RN(a), mid = RN(a - hi), lo = a - hi - mid
 // (exact: 8 bits are left).  split_pair (ggnn_split.hpp) cuts by truncation; its pieces all carry a's sign, so what the six-product
@@ -319,107 +409,15 @@ __device__ __forceinline__ void xty_split_pair(float a0, float a1, unsigned& h, 
 template <bool GATHER, int ROWS, int MTM, int NTM>
 __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float slab[];     // [2][ROWS][pitch_x] | [2][ROWS][pitch_y]
-    constexpr int nw = kXtySplitWaves;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
-    int batch = 0;
-    while (batch + 1 < a.nbatch && (int)blockIdx.y >= a.wg_off[batch + 1]) ++batch;
-    const int split = (int)blockIdx.y - a.wg_off[batch], splits = a.wg_off[batch + 1] - a.wg_off[batch];
-    const int rb = a.row_off[batch], re = a.row_off[batch + 1];
-    int rows_per = (re - rb + splits - 1) / splits;
-    rows_per = (rows_per + ROWS - 1) / ROWS * ROWS;
-    const int r_beg = rb + split * rows_per;
-    const int r_end = min(re, r_beg + rows_per);
+    const XtyRange rg = xty_row_range<ROWS>(a, blockIdx.y);
+    const int r_beg = rg.r_beg, r_end = rg.r_end;
     const int kcol0 = blockIdx.x * a.kb_tiles * 16;
-    const int px = a.pitch_x, py = a.pitch_y;
-    float* sx = slab;
-    float* sy = slab + 2 * ROWS * px;
-    float* out = a.part + (size_t)blockIdx.y * a.Kout * a.N;
+    const XtyWaveTiles wt = xty_wave_tiles(a, wave);
+    GGNN_XTY_SLAB_LOADER(kXtySplitWaves, kXtySplitMaxI, xty_dma_asm);
 
-    // this wave's tile groups
-    int kt0, my_mt, nta0, cnta, ntb0, cntb;
-    xty_group(a.kb_tiles, wave >> 1, kt0, my_mt);
-    const int ga = ((wave >> 1) + 2 * (wave & 1)) & 3;
-    xty_group(a.n_tiles, ga, nta0, cnta);
-    xty_group(a.n_tiles, (ga + 1) & 3, ntb0, cntb);
-    const int my_nt = cnta + cntb;
-
-    // ---- per-lane decode of the DMA chunks (as xty_kernel, 8 waves) --------------------------------------------------------------
-    constexpr int MAXI = kXtySplitMaxI;
-    const int cprx = px / 4, cpry = py / 4;
-    const int nix = ROWS * cprx / 64, niy = ROWS * cpry / 64;
-    unsigned mx[MAXI], my[MAXI];
-#pragma unroll
-    for (int j = 0; j < MAXI; ++j) {
-        const int ix = j * nw + wave;
-        mx[j] = 0x80000000u; my[j] = 0x80000000u;
-        if (ix < nix) {
-            const int c = ix * 64 + lane, row = c / cprx, q = c - row * cprx;
-            int col = kcol0 + 4 * q;
-            const bool ones = a.Kout > a.K && col == a.K && 4 * q < a.kb_tiles * 16;
-            if (!(4 * q < a.kb_tiles * 16 && col < a.K)) col = 0;
-            const int seg = col / a.Dseg, within = col - seg * a.Dseg;
-            mx[j] = (unsigned)within | ((unsigned)seg << 16) | ((unsigned)row << 18) | (ones ? 0x40000000u : 0u);
-        }
-        if (ix < niy) {
-            const int c = ix * 64 + lane, row = c / cpry, q = c - row * cpry;
-            my[j] = (unsigned)(4 * q < a.N ? 4 * q : 0) | ((unsigned)row << 18);
-        }
-    }
-    auto xrow = [&](int r0, unsigned m) __attribute__((always_inline)) -> int {
-        int r = r0 + (int)((m >> 18) & 127u); r = r < r_end ? r : r_end - 1;
-        return r;
-    };
-    int rid[GATHER ? MAXI : 1];
-    auto fetch_rows = [&](int r0) __attribute__((always_inline)) {
-        if constexpr (GATHER) {
-#pragma unroll
-            for (int j = 0; j < MAXI; ++j) rid[j] = (mx[j] >> 31) ? 0 : a.x_rows[xrow(r0 < r_end ? r0 : r_beg, mx[j])];
-        }
-    };
-    auto sgpr_ptr = [](const float* p) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-    };
-    const float* X0 = sgpr_ptr(a.X[0]); const float* X1 = sgpr_ptr(a.X[1]);
-    const float* X2 = sgpr_ptr(a.X[2]); const float* X3 = sgpr_ptr(a.X[3]);
-    const int L0 = __builtin_amdgcn_readfirstlane(a.ldx[0]), L1 = __builtin_amdgcn_readfirstlane(a.ldx[1]);
-    const int L2 = __builtin_amdgcn_readfirstlane(a.ldx[2]), L3 = __builtin_amdgcn_readfirstlane(a.ldx[3]);
-    const float* Yb = sgpr_ptr(a.Y);
-    const int ldy = __builtin_amdgcn_readfirstlane(a.ldy);
-    // one 1-KiB LDS-DMA instruction with per-lane source addresses, through inline assembly (M0 = the wave's LDS destination)
-    auto dma1 = [&](const float* src, float* dst) __attribute__((always_inline)) {
-        const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_void*)dst);
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(l), "v"(src) : "memory");
-    };
-    auto issue = [&](int buf, int r0) __attribute__((always_inline)) {                             // uses rid[] (fetched one slab ahead)
-#pragma unroll
-        for (int j = 0; j < MAXI; ++j) {
-            if (!(mx[j] >> 31)) {
-                const unsigned m = mx[j];
-                const int seg = (int)((m >> 16) & 3u);
-                const float* xb = seg == 0 ? X0 : (seg == 1 ? X1 : (seg == 2 ? X2 : X3));
-                const int xl = seg == 0 ? L0 : (seg == 1 ? L1 : (seg == 2 ? L2 : L3));
-                const int xr = GATHER ? rid[GATHER ? j : 0] : xrow(r0, m);
-                const float* src = xb + (size_t)xr * xl + (m & 0xFFFFu);
-                if (m & 0x40000000u) src = kXtyOnesChunk;
-                if (r0 + (int)((m >> 18) & 127u) >= r_end) src = kXtyZeroChunk;
-                dma1(src, sx + buf * ROWS * px + (size_t)(j * nw + wave) * 256);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < MAXI; ++j) {
-            if (!(my[j] >> 31)) {
-                const unsigned m = my[j];
-                int r = r0 + (int)((m >> 18) & 127u); r = r < r_end ? r : r_end - 1;
-                dma1(Yb + (size_t)r * ldy + (m & 0xFFFFu), sy + buf * ROWS * py + (size_t)(j * nw + wave) * 256);
-            }
-        }
-    };
-
-    // the slab loop, instantiated per (X tiles, dY tiles) of a wave and selected once (see xty_kernel)
     auto run = [&](auto mt_c, auto nt_c) __attribute__((always_inline)) {
         constexpr int MT = decltype(mt_c)::value, NT = decltype(nt_c)::value;
         constexpr bool ON = MT > 0 && NT > 0;
@@ -429,7 +427,7 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs 
 #pragma unroll
             for (int nt = 0; nt < (ON ? NT : 1); ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // dY tile t of this wave: column offset within the slab row
-        auto ycol = [&](int t) __attribute__((always_inline)) { return (t < cnta ? nta0 + t : ntb0 + (t - cnta)) * 16; };
+        auto ycol = [&](int t) __attribute__((always_inline)) { return wt.tile(t) * 16; };
         if (r_beg < r_end) {
             int buf = 0;
             fetch_rows(r_beg);
@@ -441,7 +439,7 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs 
                 const bool has_next = r0 + ROWS < r_end;
                 if (has_next) { issue(buf ^ 1, r0 + ROWS); fetch_rows(r0 + 2 * ROWS); }
                 if constexpr (ON) {
-                    const float* bx = sx + buf * ROWS * px + kt0 * 16 + li;
+                    const float* bx = sx + buf * ROWS * px + wt.kt0 * 16 + li;
                     const float* by = sy + buf * ROWS * py + li;
                     // 8 values of a tile column (rows 32 s + 4 j + kq) -> planes
                     auto tile_planes = [&](const float* col, int pitch, int s, u32x4& hi, u32x4& mid, u32x4& lo) __attribute__((always_inline)) {
@@ -466,10 +464,7 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs 
                         for (int nt = 0; nt < NT; ++nt) {
                             __builtin_amdgcn_sched_barrier(0);
                             if (nt + 1 < NT) tile_planes(by + ycol(nt + 1), py, s, zh, zm, zl);
-                            // six products per tile pair, product-major over the X tiles (consecutive MFMAs hit different accumulators)
-#define GGNN_XS(XP, YP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(XP[mt], YP, acc[mt][nt]);
-                            GGNN_XS(xl, yh) GGNN_XS(xm, ym) GGNN_XS(xm, yh) GGNN_XS(xh, yl) GGNN_XS(xh, ym) GGNN_XS(xh, yh)
-#undef GGNN_XS
+                            xty_six_products(acc, nt, xh, xm, xl, yh, ym, yl);
                             yh = zh; ym = zm; yl = zl;
                         }
                         __builtin_amdgcn_sched_barrier(0);
@@ -480,36 +475,11 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_split_kernel(XtyArgs 
                 buf ^= 1;
             }
         }
-        if constexpr (ON) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int k0 = kcol0 + (kt0 + mt) * 16;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int n = ycol(nt) + li;
-                    if (n < a.N) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int k = k0 + 4 * kq + e;
-                            if (k < a.Kout) out[(size_t)k * a.N + n] = acc[mt][nt][e];
-                        }
-                    }
-                }
-            }
-        }
+        if constexpr (ON) xty_store_acc(a, rg.out, acc, kcol0, wt.kt0, li, kq, ycol);
     };
-    using I0 = std::integral_constant<int, 0>;
-    using IM = std::integral_constant<int, MTM>; using IM1 = std::integral_constant<int, MTM - 1>;
-    using IN = std::integral_constant<int, 2 * NTM>; using IN1 = std::integral_constant<int, 2 * NTM - 1>;
-    using IN2 = std::integral_constant<int, 2 * NTM - 2>;
-    if (my_mt == MTM && my_nt == 2 * NTM) run(IM{}, IN{});
-    else if (my_mt == MTM && my_nt == 2 * NTM - 1) run(IM{}, IN1{});
-    else if (my_mt == MTM && my_nt == 2 * NTM - 2) run(IM{}, IN2{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM) run(IM1{}, IN{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 1) run(IM1{}, IN1{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 2) run(IM1{}, IN2{});
-    else run(I0{}, I0{});
+    xty_run_selected<MTM, NTM>(wt.my_mt, wt.nt(), run);
 }
+#undef GGNN_XTY_SLAB_LOADER
 
 // ---- X^T dY in split form with the operands split ONCE, into LDS planes (round 4) -------------------------------------------------
 // xty_split_kernel above splits an operand tile in EVERY wave that multiplies it (484 vector instructions and 88 ds_read_b32 per
@@ -536,27 +506,13 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_planes_kernel(XtyArgs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
-    int batch = 0;
-    while (batch + 1 < a.nbatch && (int)blockIdx.y >= a.wg_off[batch + 1]) ++batch;
-    const int split = (int)blockIdx.y - a.wg_off[batch], splits = a.wg_off[batch + 1] - a.wg_off[batch];
-    const int rb = a.row_off[batch], re = a.row_off[batch + 1];
-    int rows_per = (re - rb + splits - 1) / splits;
-    rows_per = (rows_per + ROWS - 1) / ROWS * ROWS;
-    const int r_beg = rb + split * rows_per;
-    const int r_end = min(re, r_beg + rows_per);
+    const XtyRange rg = xty_row_range<ROWS>(a, blockIdx.y);
+    const int r_beg = rg.r_beg, r_end = rg.r_end;
     const int kcol0 = blockIdx.x * a.kb_tiles * 16;
     const int XC = a.kb_tiles * 16, YC = a.n_tiles * 16, CT = XC + YC;      // CT <= NTH (one quad per thread and 8-row group)
     const unsigned plane_b = 4u * (unsigned)CT * 16u;                  // bytes of one plane (4 groups)
     const unsigned buf_b = 3u * plane_b;
-    float* out = a.part + (size_t)blockIdx.y * a.Kout * a.N;
-
-    // this wave's tile groups (xty_split_kernel's)
-    int kt0, my_mt, nta0, cnta, ntb0, cntb;
-    xty_group(a.kb_tiles, wave >> 1, kt0, my_mt);
-    const int ga = ((wave >> 1) + 2 * (wave & 1)) & 3;
-    xty_group(a.n_tiles, ga, nta0, cnta);
-    xty_group(a.n_tiles, (ga + 1) & 3, ntb0, cntb);
-    const int my_nt = cnta + cntb;
+    const XtyWaveTiles wt = xty_wave_tiles(a, wave);
 
     // ---- producer side: thread t < CT owns quad (t % (CT / 4)) of 8-row group t / (CT / 4) ------------------------------------------
     const char* const zero_p = reinterpret_cast<const char*>(kXtyZeroChunk);
@@ -640,7 +596,6 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_planes_kernel(XtyArgs
         for (int mt = 0; mt < (ON ? MT : 1); ++mt)
 #pragma unroll
             for (int nt = 0; nt < (ON ? NT : 1); ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto ytile = [&](int t) __attribute__((always_inline)) { return t < cnta ? nta0 + t : ntb0 + (t - cnta); };
         // the MFMAs of one step over slab[buf]; INTER: the next step's columns cut in (one per PU tiles)
         auto mma_step = [&](int buf, int r0, bool has_next, auto inter_c) __attribute__((always_inline)) {
             constexpr bool INTER = decltype(inter_c)::value;
@@ -654,16 +609,13 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_planes_kernel(XtyArgs
                 };
                 u32x4 xh[MT], xm[MT], xl[MT];
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) planes(0, kt0 + mt, xh[mt], xm[mt], xl[mt]);
+                for (int mt = 0; mt < MT; ++mt) planes(0, wt.kt0 + mt, xh[mt], xm[mt], xl[mt]);
                 u32x4 yh, ym, yl, zh, zm, zl;
-                planes(XC, ytile(0), yh, ym, yl);
+                planes(XC, wt.tile(0), yh, ym, yl);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    if (nt + 1 < NT) planes(XC, ytile(nt + 1), zh, zm, zl);
-                    // six products per tile pair, product-major over the X tiles (consecutive MFMAs hit different accumulators)
-#define GGNN_XS(XP, YP) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = mfma_bf16(XP[mt], YP, acc[mt][nt]);
-                    GGNN_XS(xl, yh) GGNN_XS(xm, ym) GGNN_XS(xm, yh) GGNN_XS(xh, yl) GGNN_XS(xh, ym) GGNN_XS(xh, yh)
-#undef GGNN_XS
+                    if (nt + 1 < NT) planes(XC, wt.tile(nt + 1), zh, zm, zl);
+                    xty_six_products(acc, nt, xh, xm, xl, yh, ym, yl);
                     yh = zh; ym = zm; yl = zl;
                     if constexpr (INTER) {
                         constexpr int PU = NT >= 8 ? 2 : 1;              // tiles per column slice
@@ -699,35 +651,9 @@ __global__ __launch_bounds__(kXtySplitWaves * 64) void xty_planes_kernel(XtyArgs
                 buf ^= 1;
             }
         }
-        if constexpr (ON) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int k0 = kcol0 + (kt0 + mt) * 16;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int n = ytile(nt) * 16 + li;
-                    if (n < a.N) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int k = k0 + 4 * kq + e;
-                            if (k < a.Kout) out[(size_t)k * a.N + n] = acc[mt][nt][e];
-                        }
-                    }
-                }
-            }
-        }
+        if constexpr (ON) xty_store_acc(a, rg.out, acc, kcol0, wt.kt0, li, kq, [&](int nt) { return wt.tile(nt) * 16; });
     };
-    using I0 = std::integral_constant<int, 0>;
-    using IM = std::integral_constant<int, MTM>; using IM1 = std::integral_constant<int, MTM - 1>;
-    using IN = std::integral_constant<int, 2 * NTM>; using IN1 = std::integral_constant<int, 2 * NTM - 1>;
-    using IN2 = std::integral_constant<int, 2 * NTM - 2>;
-    if (my_mt == MTM && my_nt == 2 * NTM) run(IM{}, IN{});
-    else if (my_mt == MTM && my_nt == 2 * NTM - 1) run(IM{}, IN1{});
-    else if (my_mt == MTM && my_nt == 2 * NTM - 2) run(IM{}, IN2{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM) run(IM1{}, IN{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 1) run(IM1{}, IN1{});
-    else if (my_mt == MTM - 1 && my_nt == 2 * NTM - 2) run(IM1{}, IN2{});
-    else run(I0{}, I0{});
+    xty_run_selected<MTM, NTM>(wt.my_mt, wt.nt(), run);
 }
 
 // C[b][i] = sum over the workgroup rows of batch b of part[row][i], in row order.  With a separate bias destination the K weight rows
@@ -817,7 +743,11 @@ static int xty_default_rows() {                                                 
 
 // What a product of Kout x N outputs runs on: the geometry of a workgroup (rows: slab height of the f32 / per-wave split kernels
 // and the unit of the workgroup-row deal) and the table cell.
-struct XtySel { int rows, kb_tiles, n_tiles, kblocks, px, py; size_t lds; XtyCell cell; };
+struct XtySel { int rows, kb_tiles, n_tiles, kblocks, px, py; size_t lds; XtyCell cell; };     // lds: of the selected cell's kernel
+
+constexpr size_t kXtyLdsLimit = (size_t)160 * 1024;                                     // LDS of a CU: one workgroup per CU
+// xty_planes_kernel: [2 buffers][3 planes][4 groups][16 (kb_tiles + n_tiles) column slots] x 16 bytes
+static inline size_t xty_planes_lds(int kb_tiles, int n_tiles) { return (size_t)2 * 192 * 16 * (kb_tiles + n_tiles); }
 
 static inline int xty_dma_per_wave(int rows, int pitch, int waves) { return (rows * pitch / 256 + waves - 1) / waves; }
 
@@ -830,10 +760,10 @@ static int xty_select(int K, int N, int Kout, bool g, bool split_on, bool planes
     s.n_tiles = (N + 15) / 16;
     s.px = xty_pitch(s.kb_tiles * 16); s.py = xty_pitch(s.n_tiles * 16);
     const int mtm = (s.kb_tiles + 3) / 4, ntm = (s.n_tiles + 3) / 4;
-    // 64-row slabs when two of them fit the 160 KiB of LDS (half the barriers, and a slab's MFMA time then covers the latency of the
+    // 64-row slabs when two of them fit kXtyLdsLimit (half the barriers, and a slab's MFMA time then covers the latency of the
     // next slab's DMA also for the narrow edge-weight products) and a wave's share of a slab fits its kXtyMaxI DMA instructions (a
     // 16-tile operand, pitch 272, does not: 68 instructions per 64 rows), else 32
-    const bool fits64 = (size_t)2 * 64 * (s.px + s.py) * sizeof(float) <= (size_t)160 * 1024 && mtm + ntm <= 6 &&
+    const bool fits64 = (size_t)2 * 64 * (s.px + s.py) * sizeof(float) <= kXtyLdsLimit && mtm + ntm <= 6 &&
                         xty_dma_per_wave(64, s.px, kXtyWaves) <= kXtyMaxI && xty_dma_per_wave(64, s.py, kXtyWaves) <= kXtyMaxI;
     s.rows = fits64 ? 64 : 32;
     if (rows_override == 32) s.rows = 32;
@@ -845,11 +775,11 @@ static int xty_select(int K, int N, int Kout, bool g, bool split_on, bool planes
     if (split_on && s.kb_tiles >= 4 && s.n_tiles >= 4 && xty_dma_per_wave(s.rows, s.px, kXtySplitWaves) <= kXtySplitMaxI &&
         xty_dma_per_wave(s.rows, s.py, kXtySplitWaves) <= kXtySplitMaxI) {
         // operands split once into LDS planes (xty_planes_kernel; GGNN_XTY_PLANES=0: the per-wave split below): ungathered X, both
-        // plane buffers within the 160 KiB of LDS, every unit of a step owned by a thread
-        if (planes_on && !g && (size_t)2 * 192 * 16 * (s.kb_tiles + s.n_tiles) <= (size_t)160 * 1024 &&
-            16 * (s.kb_tiles + s.n_tiles) <= kXtySplitWaves * 64) {
+        // plane buffers within the LDS, every unit of a step owned by a thread
+        const size_t planes_lds = xty_planes_lds(s.kb_tiles, s.n_tiles);
+        if (planes_on && !g && planes_lds <= kXtyLdsLimit && 16 * (s.kb_tiles + s.n_tiles) <= kXtySplitWaves * 64) {
             s.cell = XtyCell{2, false, 32, mtm, ntm};
-            if (xty_has_cell(s.cell)) return GGNN_OK;
+            if (xty_has_cell(s.cell)) { s.lds = planes_lds; return GGNN_OK; }
         }
         s.cell = XtyCell{1, g, s.rows, mtm, ntm};
         if (xty_has_cell(s.cell)) return GGNN_OK;
@@ -866,22 +796,22 @@ static int xty_check_sizes(int K, int N) {
     return GGNN_OK;
 }
 
-struct XtyPlan { int rows, kb_tiles, n_tiles, kblocks, px, py, wg_rows; size_t lds; int wg_off[kXtyMaxBatch + 1]; };
+struct XtyPlan { XtySel sel; int wg_rows; int wg_off[kXtyMaxBatch + 1]; };
 
 // Workgroup rows (one 16-wave workgroup per CU and K block) are dealt to the batches in proportion to their row counts, at least
 // one per non-empty batch and at most one per 4 slabs of rows; an empty batch gets none (its product is the empty sum, 0).
 static XtyPlan xty_plan(const int* row_off, int nbatch, const XtySel& s) {
     XtyPlan p{};
-    p.rows = s.rows; p.kb_tiles = s.kb_tiles; p.n_tiles = s.n_tiles; p.kblocks = s.kblocks; p.px = s.px; p.py = s.py; p.lds = s.lds;
+    p.sel = s;
     long long total = 0;
     for (int b = 0; b < nbatch; ++b) total += row_off[b + 1] - row_off[b];
-    int target = num_cus() / p.kblocks;
+    int target = num_cus() / s.kblocks;
     if (target < 1) target = 1;
     p.wg_off[0] = 0;
     for (int b = 0; b < nbatch; ++b) {
         const long long m = row_off[b + 1] - row_off[b];
         long long w = total > 0 ? (long long)target * m / total : 0;
-        const long long cap = (m + 4 * p.rows - 1) / (4 * p.rows);
+        const long long cap = (m + 4 * s.rows - 1) / (4 * s.rows);
         if (w > cap) w = cap;
         if (w < 1 && m > 0) w = 1;
         p.wg_off[b + 1] = p.wg_off[b] + (int)w;
@@ -890,14 +820,8 @@ static XtyPlan xty_plan(const int* row_off, int nbatch, const XtySel& s) {
     return p;
 }
 
-template <bool GATHER, int ROWS, int MTM, int NTM>
-static int launch_xty(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, int accumulate, hipStream_t st) {
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (p.wg_rows > 0) {
-        if (p.lds > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&xty_kernel<GATHER, ROWS, MTM, NTM>, p.lds, lds_ok)));
-        hipLaunchKernelGGL((xty_kernel<GATHER, ROWS, MTM, NTM>), dim3(p.kblocks, p.wg_rows), dim3(kXtyWaves * 64), p.lds, st, a);
-        GGNN_CHECK_HIP(hipGetLastError());
-    }
+// sums the workgroup rows' partial products into the destinations (see xty_reduce_kernel)
+static int launch_xty_reduce(const XtyArgs& a, float* C, float* Cb, int accumulate, hipStream_t st) {
     XtyReduceArgs ra;
     for (int b = 0; b <= kXtyMaxBatch; ++b) ra.wg_off[b] = a.wg_off[b <= a.nbatch ? b : a.nbatch];
     const long long total = (long long)a.Kout * a.N * a.nbatch;
@@ -907,46 +831,27 @@ static int launch_xty(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, i
     return GGNN_OK;
 }
 
-template <int MTM, int NTM>
-static int launch_xty_planes(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, int accumulate, hipStream_t st) {
-    static std::atomic<unsigned long long> lds_ok{0};
-    const size_t lds = (size_t)2 * 192 * (size_t)(16 * (p.kb_tiles + p.n_tiles));
-    if (p.wg_rows > 0) {
-        if (lds > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&xty_planes_kernel<MTM, NTM>, lds, lds_ok)));
-        hipLaunchKernelGGL((xty_planes_kernel<MTM, NTM>), dim3(p.kblocks, p.wg_rows), dim3(kXtySplitWaves * 64), lds, st, a);
-        GGNN_CHECK_HIP(hipGetLastError());
-    }
-    XtyReduceArgs ra;
-    for (int b = 0; b <= kXtyMaxBatch; ++b) ra.wg_off[b] = a.wg_off[b <= a.nbatch ? b : a.nbatch];
-    const long long total = (long long)a.Kout * a.N * a.nbatch;
-    hipLaunchKernelGGL(xty_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const float*)a.part, C, Cb, a.Kout * a.N,
-                       a.K * a.N, a.nbatch, accumulate, ra);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
-}
+using XtyKernel = void (*)(XtyArgs);
 
-template <bool GATHER, int ROWS, int MTM, int NTM>
-static int launch_xty_split(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, int accumulate, hipStream_t st) {
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (p.wg_rows > 0) {
-        if (p.lds > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&xty_split_kernel<GATHER, ROWS, MTM, NTM>, p.lds, lds_ok)));
-        hipLaunchKernelGGL((xty_split_kernel<GATHER, ROWS, MTM, NTM>), dim3(p.kblocks, p.wg_rows), dim3(kXtySplitWaves * 64), p.lds, st, a);
-        GGNN_CHECK_HIP(hipGetLastError());
-    }
-    XtyReduceArgs ra;
-    for (int b = 0; b <= kXtyMaxBatch; ++b) ra.wg_off[b] = a.wg_off[b <= a.nbatch ? b : a.nbatch];
-    const long long total = (long long)a.Kout * a.N * a.nbatch;
-    hipLaunchKernelGGL(xty_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const float*)a.part, C, Cb, a.Kout * a.N,
-                       a.K * a.N, a.nbatch, accumulate, ra);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
-}
-
+// the kernel of a table cell and its workgroup size
 template <int F, bool GATHER, int ROWS, int MTM, int NTM>
-static int launch_xty_cell(const XtyArgs& a, const XtyPlan& p, float* C, float* Cb, int accumulate, hipStream_t st) {
-    if constexpr (F == 2) return launch_xty_planes<MTM, NTM>(a, p, C, Cb, accumulate, st);
-    else if constexpr (F == 1) return launch_xty_split<GATHER, ROWS, MTM, NTM>(a, p, C, Cb, accumulate, st);
-    else return launch_xty<GATHER, ROWS, MTM, NTM>(a, p, C, Cb, accumulate, st);
+constexpr XtyKernel xty_cell_kernel() {
+    if constexpr (F == 2) return &xty_planes_kernel<MTM, NTM>;
+    else if constexpr (F == 1) return &xty_split_kernel<GATHER, ROWS, MTM, NTM>;
+    else return &xty_kernel<GATHER, ROWS, MTM, NTM>;
+}
+constexpr int xty_cell_threads(int family) { return (family == 0 ? kXtyWaves : kXtySplitWaves) * 64; }
+
+// One product: the cell's kernel over (K blocks) x (workgroup rows), then the reduction.  lds_ok: the kernel's own record of
+// the devices on which its dynamic-LDS limit has been raised.
+static int launch_xty_cell(XtyKernel kernel, int threads, std::atomic<unsigned long long>& lds_ok, const XtyArgs& a, const XtyPlan& p,
+                           float* C, float* Cb, int accumulate, hipStream_t st) {
+    if (p.wg_rows > 0) {
+        if (p.sel.lds > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(kernel, p.sel.lds, lds_ok)));
+        hipLaunchKernelGGL(kernel, dim3(p.sel.kblocks, p.wg_rows), dim3(threads), p.sel.lds, st, a);
+        GGNN_CHECK_HIP(hipGetLastError());
+    }
+    return launch_xty_reduce(a, C, Cb, accumulate, st);
 }
 
 // ---- deterministic column sums -----------------------------------------------------------------------------------------
@@ -1037,14 +942,16 @@ extern "C" int ggnn_xty_acc_f32(const float* const* x_segs, int nseg, int Dseg, 
     const XtyPlan p = xty_plan(row_off, nbatch, sel);
     a.Kout = Kout;
     a.nseg = nseg; a.Dseg = Dseg; a.x_rows = x_rows; a.Y = Y; a.ldy = ldy; a.part = static_cast<float*>(ws);
-    a.K = K; a.N = N; a.nbatch = nbatch; a.kb_tiles = p.kb_tiles; a.n_tiles = p.n_tiles;
-    a.pitch_x = p.px; a.pitch_y = p.py;
+    a.K = K; a.N = N; a.nbatch = nbatch; a.kb_tiles = sel.kb_tiles; a.n_tiles = sel.n_tiles;
+    a.pitch_x = sel.px; a.pitch_y = sel.py;
     for (int b = 0; b <= kXtyMaxBatch; ++b) a.wg_off[b] = p.wg_off[b <= nbatch ? b : nbatch];
     { const char* e = getenv("GGNN_XTY_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
     const XtyCell& c = sel.cell;
 #define GGNN_XTY_LAUNCH(F, G, R, M, Nn)                                                                     \
-    if (c.family == F && c.gathered == G && c.rows == R && c.mtm == M && c.ntm == Nn)                        \
-        return launch_xty_cell<F, G, R, M, Nn>(a, p, C, Cb, accumulate, st);
+    if (c.family == F && c.gathered == G && c.rows == R && c.mtm == M && c.ntm == Nn) {                      \
+        static std::atomic<unsigned long long> lds_ok{0};                                                   \
+        return launch_xty_cell(xty_cell_kernel<F, G, R, M, Nn>(), xty_cell_threads(F), lds_ok, a, p, C, Cb, accumulate, st); \
+    }
     GGNN_XTY_TABLE(GGNN_XTY_LAUNCH)
 #undef GGNN_XTY_LAUNCH
     return fail(GGNN_E_UNSUPPORTED, "xty: selected cell is not in the dispatch table (K=%d N=%d)", K, N);

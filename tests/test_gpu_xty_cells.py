@@ -211,14 +211,22 @@ def test_gathered_index_patterns(pkg, cuda, lib, gathered_case):
     _check(pkg, cuda, c, cell, "%s descending triples" % _cell_id(cell))
 
 
-@pytest.mark.parametrize("K,ones,kblocks", [(4 * 132, 1, 3), (4 * 256, 0, 4)])
-def test_three_and_four_k_blocks(pkg, cuda, lib, K, ones, kblocks):
-    """512 < K <= 1024, ungathered, N = 64: the product is cut into 3 / 4 K blocks (blockIdx.x), the last one short of whole tile
-    groups (K = 528 + ones row: 34 tiles in blocks of 12) or exactly full (K = 1024: 4 x 16)."""
-    rc, cell, geom = xc.describe(lib, K, 64, ones, 0)
-    assert rc == 0 and geom[0] == kblocks and geom[2] == 4, (cell, geom)
+@pytest.mark.parametrize("K,ones,N,kblocks,default_cell", [
+    (4 * 132, 1, 64, 3, None), (4 * 256, 0, 64, 4, None),
+    (4 * 132, 1, 128, 3, (2, 0, 32, 3, 2)), (4 * 256, 0, 256, 4, (1, 0, 32, 4, 4))],
+    ids=["528-1-3", "1024-0-4", "528-1-N128-3", "1024-0-N256-4"])              # (the N = 64 cases keep the ids they had)
+def test_three_and_four_k_blocks(pkg, cuda, lib, K, ones, N, kblocks, default_cell):
+    """512 < K <= 1024, ungathered: the product is cut into 3 / 4 K blocks (blockIdx.x), the last one short of whole tile groups
+    (K = 528 + ones row: 34 tiles in blocks of 12, the last one 10) or exactly full (K = 1024: 4 x 16).  N = 64 runs on the f32
+    kernel in every leg; N = 128 / 256 take the workgroups that are not the first K block through the split families too: in the
+    default leg xty_planes_kernel<3, 2> (12 + 8 tiles) and xty_split_kernel<false, 32, 4, 4> (16 + 16 tiles do not fit the planes'
+    LDS)."""
+    rc, cell, geom = xc.describe(lib, K, N, ones, 0)
+    assert rc == 0 and geom[0] == kblocks and geom[2] == (N + 15) // 16, (cell, geom)
+    if default_cell is not None and (LEG == "default" or not (LEG or any(v in os.environ for v in xc.LEG_VARS))):
+        assert cell == default_cell, (cell, default_cell)
     for M in (cell[2] + 1, 4 * cell[2] + 1):
-        _check(pkg, cuda, xc.make_case(M, M, K, 64, ones, 0), cell, "K=%d (%d K blocks, %s) M=%d" % (K, kblocks, _cell_id(cell), M))
+        _check(pkg, cuda, xc.make_case(M, M, K, N, ones, 0), cell, "K=%d N=%d (%d K blocks, %s) M=%d" % (K, N, kblocks, _cell_id(cell), M))
 
 
 def test_other_legs_run_every_remaining_instantiation(pkg, cuda, lib, tmp_path):
