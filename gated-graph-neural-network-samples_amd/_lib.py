@@ -217,6 +217,17 @@ SYMBOLS = {
     "ggnn_gcn_train_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                             POINTER(c_uint64), c_float, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t,
                                             c_void_p, c_void_p]),
+    "ggnn_gcn_panel_layer_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_uint64, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "ggnn_gcn_panel_train_pack_f32": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_gcn_panel_train_supported": (c_int, [c_int]),
+    "ggnn_gcn_panel_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ggnn_gcn_panel_train_forward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_void_p),
+                                                 POINTER(c_void_p), c_void_p, POINTER(c_uint64), c_float, c_void_p, c_size_t,
+                                                 POINTER(c_int64), c_void_p]),
+    "ggnn_gcn_panel_train_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                  POINTER(c_uint64), c_float, POINTER(c_void_p), POINTER(c_void_p), c_void_p,
+                                                  c_size_t, c_void_p, c_void_p]),
     "ggnn_gcn_assemble_batch": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                         c_int, c_int, POINTER(c_void_p), c_void_p]),
     "ggnn_dense_assemble_batch": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,

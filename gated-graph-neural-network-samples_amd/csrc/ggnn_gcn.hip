@@ -56,13 +56,6 @@ __global__ __launch_bounds__(256) void gcn_train_pack_kernel(GcnPackList w, int 
     else pack_split_image<D, kSplitBf16x3>(StageValue<D>{W, 0, 0, D, -1, nullptr, 0, 0, -1}, img, first, stride);
 }
 
-// d v / d P of out = dropout(relu(P)) given out: ggnn_act_bwd_f32's ReLU select, term for term
-__device__ __forceinline__ f32x4 gcn_relu_gate(f32x4 v, f32x4 gate) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = gate[e] > 0.f ? v[e] : 0.f;
-    return v;
-}
-
 // BWD: x = dP of this layer, (row_ptr, col, val) = the transposed CSR, packed = the image of W^T, ep = the dropout of the layer
 // below (no bias, no ReLU), gate_out [V, D] = that layer's forward output; out = its dP.  s_out is not written.
 template <int D, bool BWD = false>

@@ -1,5 +1,6 @@
 // What the GCN layer kernels share (ggnn_gcn.hip: hidden sizes 32 / 64 / 100; ggnn_gcn_panel.hip: 128 / 192 / 256): the weighted
-// accumulation of a gathered row into the aggregate fragment and the epilogue out = dropout(relu(P + b)).
+// accumulation of a gathered row into the aggregate fragment, the epilogue out = dropout(relu(P + b)) and the ReLU gate of the
+// layer-backward forms.
 #pragma once
 #include "ggnn_split.hpp"
 #include "ggnn_philox.hpp"
@@ -39,6 +40,13 @@ __device__ __forceinline__ f32x4 gcn_epilogue(f32x4 v, int row, int col, const G
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] / ep.keep * floorf(ep.keep + (float)(u[e] >> 8) * (1.0f / 16777216.0f));
     }
+    return v;
+}
+
+// d v / d P of out = dropout(relu(P)) given out: ggnn_act_bwd_f32's ReLU select, term for term
+__device__ __forceinline__ f32x4 gcn_relu_gate(f32x4 v, f32x4 gate) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = gate[e] > 0.f ? v[e] : 0.f;
     return v;
 }
 

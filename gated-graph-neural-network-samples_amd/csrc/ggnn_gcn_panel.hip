@@ -23,6 +23,11 @@
 // the workgroup's own round barriers -- neither the gather nor a ring wait is a launch-wide phase.
 //
 // The backward's dx = A_hat^T (dP W^T) is the same launch on the transposed CSR with the panels of W^T (transpose = 1 packs them).
+// The BWD instantiation (ggnn_gcn_panel_layer_bwd_f32, the twin of ggnn_gcn.hip's) writes the dP of the layer BELOW: in the last
+// part of each panel the epilogue applies that layer's dropout mask and the ReLU gate of its forward output gate_out =
+// dropout(relu(P)), read at the lane's own row and column quad -- bit for bit the panel launch followed by ggnn_dropout_f32 and
+// ggnn_act_bwd_f32, without their [V, D] round trips.  BWD is a template parameter: the forward instantiations keep their code
+// and registers.  ggnn_gcn_panel_train_pack_f32 builds every panel image of a training step (W_l and W_l^T) in one launch.
 #include "ggnn_gcn.hpp"
 #include "ggnn_panel.hpp"
 
@@ -71,10 +76,32 @@ __device__ __forceinline__ void gcn_panel_gather(Frag<D>& a, const float* __rest
     for (int i = 0; i < N; ++i) frag_fma<D>(a, w[i], t[i]);
 }
 
+// Every panel image of a training step in ONE launch: blockIdx.z = slot j of `images`, slot j < L the D / 64 panel images of W_j,
+// slot L + (l - 1) those of W_l^T for l >= 1 (layer 0 forms no dx); blockIdx.y = the panel.  pack_panel_gru_split_image writes word
+// i as a function of (i, W) alone: the images are gcn_panel_pack_kernel's bit for bit whatever the grid.
+constexpr int kGcnPanelTrainMaxLayers = 64;
+struct GcnPanelPackList { const float* W[kGcnPanelTrainMaxLayers]; };
+
 template <int D>
+__global__ __launch_bounds__(256) void gcn_panel_train_pack_kernel(GcnPanelPackList w, int L, float* __restrict__ images,
+                                                                   unsigned slot_floats) {
+    using C = PanelCfg<D>;
+    const int j = blockIdx.z, p = blockIdx.y;
+    const bool transpose = j >= L;
+    const float* W = w.W[transpose ? j - L + 1 : j];
+    float* dst = images + (size_t)j * slot_floats + (size_t)p * GcnPanelImg<D>::IMG;
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    if (transpose) pack_panel_gru_split_image<D, kSplitBf16x3, true>(W, 0, p * C::BN, D, dst, first, stride);
+    else pack_panel_gru_split_image<D, kSplitBf16x3, false>(W, 0, p * C::BN, D, dst, first, stride);
+}
+
+// BWD: x = dP of this layer, (row_ptr, col, val) = the transposed CSR, packed = the panel images of W^T, ep = the dropout of the
+// layer below (no bias, no ReLU), gate_out [V, D] = that layer's forward output; out = its dP.  s_out is not written.
+template <int D, bool BWD = false>
 __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
         const float* __restrict__ x, const int* __restrict__ row_ptr, const int* __restrict__ col, const float* __restrict__ val,
-        int nnz, const float* __restrict__ packed, GcnEpilogue ep, float* __restrict__ out, float* __restrict__ s_out, int V) {
+        int nnz, const float* __restrict__ packed, GcnEpilogue ep, float* __restrict__ out, float* __restrict__ s_out, int V,
+        const float* __restrict__ gate_out) {
     using C = PanelCfg<D>;
     using SC = GcnPanelImg<D>;
     constexpr int NW = kGcnPanelNW, NP = C::NP, NC = C::NC, PARTS = SC::PARTS, SLOTF = SC::PART, IMGF = SC::IMG;
@@ -118,7 +145,7 @@ __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
                 if (k + 2 <= end) { gcn_panel_gather<D, 2>(a, x, col, val, k, V, kq); k += 2; }
             }
             if (k < end) gcn_panel_gather<D, 1>(a, x, col, val, k, V, kq);
-            if (s_out && r < V) {
+            if (!BWD && s_out && r < V) {
                 const unsigned ob = ((unsigned)r * (unsigned)D + 4u * (unsigned)kq) * 4u;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) st4_b(s_out, ob + 64u * c, a.v[c]);
@@ -135,6 +162,20 @@ __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
                                                      : packed + (size_t)(p + 1 < NP ? p + 1 : 0) * IMGF;
                 // every wave issues its pieces of the next part FIRST: a part issued behind a burst would not land before the barrier
                 if (more) dma(nsrc, ring + (cur ^ 1) * SLOTF);
+                // BWD: the lane's four gate quads of this panel, issued BEHIND the round's DMA pieces and in front of the burst that
+                // hides them.  publish_keep(4) below still proves the pieces landed, by construction: every st4_b's value is a select
+                // on one of these loads (and on ep.row_key[r], where given), so hipcc's own waits have retired all of them -- and, the
+                // counter being in order, the DMA pieces issued before them -- when the last store is issued; no vector-memory
+                // instruction follows the stores, so "at most 4 outstanding" can only leave the four stores, as in the forward.
+                // A row r >= V loads nothing (and stores nothing); a wave without a tile (ACT = false) issues neither.
+                f32x4 gate[4];
+                if constexpr (BWD && ACT && part == PARTS - 1) {
+                    if (r < V) {
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt)
+                            gate[nt] = ld4_b(gate_out, ((unsigned)r * (unsigned)D + (unsigned)(p * 64 + nt * 16 + 4 * kq)) * 4u);
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (ACT) panel_part_mma_split<D, part == 0, false, part, kSplitBf16x3>(acc, a, ring + cur * SLOTF, li, kq);
                 __builtin_amdgcn_sched_barrier(0);
@@ -148,7 +189,9 @@ __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
 #pragma unroll
                         for (int nt = 0; nt < 4; ++nt) {
                             const int c0 = p * 64 + nt * 16 + 4 * kqe;
-                            st4_b(out, ((unsigned)r * (unsigned)D + (unsigned)c0) * 4u, gcn_epilogue(acc[nt], r, c0, ep));
+                            f32x4 v = gcn_epilogue(acc[nt], r, c0, ep);
+                            if constexpr (BWD) v = gcn_relu_gate(v, gate[nt]);
+                            st4_b(out, ((unsigned)r * (unsigned)D + (unsigned)c0) * 4u, v);
                         }
                     }
                     publish_keep(std::integral_constant<int, 4>{});
@@ -182,14 +225,25 @@ long long gcn_panel_blocks(int V) {
     return std::min<long long>((n_tiles + kGcnPanelNW - 1) / kGcnPanelNW, (long long)num_cus());
 }
 
-template <int D>
+template <int D, bool BWD = false>
 int gcn_panel_launch(const float* x, const int* row_ptr, const int* col, const float* val, int nnz, const float* img,
-                     const GcnEpilogue& ep, float* out, float* s_out, int V, hipStream_t st) {
+                     const GcnEpilogue& ep, float* out, float* s_out, int V, hipStream_t st, const float* gate_out = nullptr) {
     constexpr size_t lds = (size_t)2 * GcnPanelImg<D>::PART_BYTES;
     static std::atomic<unsigned long long> lds_ok{0};
-    if (lds > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gcn_panel_layer_kernel<D>, lds, lds_ok));
-    hipLaunchKernelGGL((gcn_panel_layer_kernel<D>), dim3((unsigned)gcn_panel_blocks(V)), dim3(kGcnPanelNW * 64), lds, st, x, row_ptr, col,
-                       val, nnz, img, ep, out, s_out, V);
+    if (lds > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gcn_panel_layer_kernel<D, BWD>, lds, lds_ok));
+    hipLaunchKernelGGL((gcn_panel_layer_kernel<D, BWD>), dim3((unsigned)gcn_panel_blocks(V)), dim3(kGcnPanelNW * 64), lds, st, x, row_ptr,
+                       col, val, nnz, img, ep, out, s_out, V, gate_out);
+    GGNN_CHECK_HIP(hipGetLastError());
+    return GGNN_OK;
+}
+
+template <int D>
+int gcn_panel_train_pack(const float* const* W, int L, float* images, hipStream_t st) {
+    GcnPanelPackList w{};
+    for (int l = 0; l < L; ++l) w.W[l] = W[l];
+    const unsigned slot_floats = (unsigned)(align256g(gcn_panel_layer_image_bytes<D>()) / sizeof(float));
+    hipLaunchKernelGGL((gcn_panel_train_pack_kernel<D>), dim3(8, PanelCfg<D>::NP, (unsigned)(2 * L - 1)), dim3(256), 0, st, w, L, images,
+                       slot_floats);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
@@ -200,6 +254,16 @@ int gcn_panel_dispatch(const float* x, const int* row_ptr, const int* col, const
         case 256: return gcn_panel_launch<256>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
         case 192: return gcn_panel_launch<192>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
         default: return gcn_panel_launch<128>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
+    }
+}
+
+// the layer backward: out = relu_gate(dropout(A_hat^T (dP W^T)), gate_out)
+int gcn_panel_dispatch_bwd(const float* dP, const int* row_ptr_t, const int* col_t, const float* val_t, int nnz, const float* img_T,
+                           const GcnEpilogue& ep, const float* gate_out, float* out, int V, int D, hipStream_t st) {
+    switch (D) {
+        case 256: return gcn_panel_launch<256, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
+        case 192: return gcn_panel_launch<192, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
+        default: return gcn_panel_launch<128, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
     }
 }
 
@@ -252,6 +316,36 @@ extern "C" int ggnn_gcn_panel_layer_f32(const float* x, const int32_t* row_ptr, 
     if ((unsigned long long)V * D >= (1ULL << 30)) return fail(GGNN_E_UNSUPPORTED, "V*D must be < 2^30 (32-bit byte offsets)");
     const GcnEpilogue ep{bias, relu ? 1 : 0, row_key, row_key_base, (uint32_t)seed, (uint32_t)(seed >> 32), keep_prob};
     return gcn_panel_dispatch(x, row_ptr, col, val, (int)nnz, img, ep, out, s_out, V, D, (hipStream_t)stream);
+}
+
+extern "C" int ggnn_gcn_panel_layer_bwd_f32(const float* dP, const int32_t* row_ptr_t, const int32_t* col_t, const float* val_t,
+                                            int64_t nnz, const float* img_T, const float* gate_out, const int64_t* row_key,
+                                            int64_t row_key_base, uint64_t seed, float keep_prob, float* out, int V, int D,
+                                            ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(V >= 0 && nnz >= 0 && nnz < (1LL << 31), "bad sizes V=%d nnz=%lld", V, (long long)nnz);
+    if (!ggnn_gcn_panel_supported(D)) return gcn_panel_unsupported(D);
+    GGNN_CHECK_ARG(gcn_epilogue_args(nullptr, keep_prob), "keep_prob %g outside (0, 1]", (double)keep_prob);
+    if (V == 0) return GGNN_OK;
+    GGNN_CHECK_ARG(dP && row_ptr_t && img_T && out && gate_out && (nnz == 0 || (col_t && val_t)), "null pointer");
+    GGNN_CHECK_ARG(aligned16(dP) && aligned16(img_T) && aligned16(out) && aligned16(gate_out), "pointers must be 16-byte aligned");
+    GGNN_CHECK_ARG(dP != out && gate_out != out, "out must not alias dP or gate_out");
+    if ((unsigned long long)V * D >= (1ULL << 30)) return fail(GGNN_E_UNSUPPORTED, "V*D must be < 2^30 (32-bit byte offsets)");
+    const GcnEpilogue ep{nullptr, 0, row_key, row_key_base, (uint32_t)seed, (uint32_t)(seed >> 32), keep_prob};
+    return gcn_panel_dispatch_bwd(dP, row_ptr_t, col_t, val_t, (int)nnz, img_T, ep, gate_out, out, V, D, (hipStream_t)stream);
+}
+
+extern "C" int ggnn_gcn_panel_train_pack_f32(const float* const* W, int num_layers, int D, float* images, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(num_layers > 0 && num_layers <= kGcnPanelTrainMaxLayers, "layers=%d outside [1, %d]", num_layers,
+                   kGcnPanelTrainMaxLayers);
+    if (!ggnn_gcn_panel_supported(D)) return gcn_panel_unsupported(D);
+    GGNN_CHECK_ARG(W && images && aligned16(images), "null or misaligned pointer");
+    for (int l = 0; l < num_layers; ++l) GGNN_CHECK_ARG(W[l] != nullptr, "null weight pointer of layer %d", l);
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 256: return gcn_panel_train_pack<256>(W, num_layers, images, st);
+        case 192: return gcn_panel_train_pack<192>(W, num_layers, images, st);
+        default: return gcn_panel_train_pack<128>(W, num_layers, images, st);
+    }
 }
 
 extern "C" size_t ggnn_gcn_panel_workspace_bytes(int V, int D, int num_layers) {

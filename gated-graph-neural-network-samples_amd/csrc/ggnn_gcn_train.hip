@@ -27,6 +27,10 @@
 // workspace with its [D] result, added into g_b[l] by a one-block launch behind it).  The call ends with
 // the main stream waiting for the side stream's last product: the caller's next launches (optimizer, next forward, which rewrites
 // the workspace) see every gradient and overwrite nothing in use.
+//
+// Two routes share these sequences (GcnTrainRoute below: image size, pack-all, layer, layer backward, supported sizes): the fused
+// layer kernels of ggnn_gcn.hip at hidden sizes 32 / 64 / 100 (ggnn_gcn_train_*) and the column-panel kernels of
+// ggnn_gcn_panel.hip at 128 / 192 / 256 (ggnn_gcn_panel_train_*).  Workspace layout, streams, events and products are the same.
 #include "ggnn_common.h"
 
 namespace ggnn {
@@ -36,14 +40,33 @@ constexpr int kGcnTrainMaxLayers = 64;              // ggnn_gcn_train_pack_f32's
 
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
+// what a route brings: the kernels of one family of hidden sizes behind the signatures both families share
+struct GcnTrainRoute {
+    int (*supported)(int D);
+    size_t (*image_bytes)(int D);
+    int (*pack_all)(const float* const* W, int num_layers, int D, float* images, ggnn_stream_t stream);
+    int (*layer)(const float* x, const int32_t* row_ptr, const int32_t* col, const float* val, int64_t nnz, const float* img,
+                 const float* bias, int relu, const int64_t* row_key, int64_t row_key_base, uint64_t seed, float keep_prob, float* out,
+                 float* s_out, int V, int D, ggnn_stream_t stream);
+    int (*layer_bwd)(const float* dP, const int32_t* row_ptr_t, const int32_t* col_t, const float* val_t, int64_t nnz,
+                     const float* img_T, const float* gate_out, const int64_t* row_key, int64_t row_key_base, uint64_t seed,
+                     float keep_prob, float* out, int V, int D, ggnn_stream_t stream);
+    const char* sizes;                                 // for the error message
+};
+
+const GcnTrainRoute kGcnFusedRoute{ggnn_gcn_train_supported, ggnn_gcn_image_bytes, ggnn_gcn_train_pack_f32, ggnn_gcn_layer_f32,
+                                   ggnn_gcn_layer_bwd_f32, "32, 64, 100"};
+const GcnTrainRoute kGcnPanelRoute{ggnn_gcn_panel_train_supported, ggnn_gcn_panel_image_bytes, ggnn_gcn_panel_train_pack_f32,
+                                   ggnn_gcn_panel_layer_f32, ggnn_gcn_panel_layer_bwd_f32, "128, 192, 256"};
+
 struct GcnTrainLayout {
     size_t images, S, H, dP, xty, colsum, db, total;   // byte offsets from the 256-aligned base; S / H / dP: L buffers of `state` bytes each
     size_t slot, state, xty_bytes, colsum_bytes;
 };
 
-GcnTrainLayout gcn_layout(int V, int D, int L) {
+GcnTrainLayout gcn_layout(const GcnTrainRoute& rt, int V, int D, int L) {
     GcnTrainLayout o{};
-    o.slot = al256(ggnn_gcn_image_bytes(D));
+    o.slot = al256(rt.image_bytes(D));
     o.state = al256((size_t)V * D * sizeof(float));
     size_t p = 0;
     auto take = [&](size_t bytes) { const size_t at = p; p += al256(bytes); return at; };
@@ -66,32 +89,25 @@ __global__ __launch_bounds__(256) void gcn_bias_add_kernel(float* __restrict__ g
     if (i < n) g[i] = g[i] + t[i];
 }
 
-int check_shape(int V, int D, int L) {
+int check_shape(const GcnTrainRoute& rt, int V, int D, int L) {
     GGNN_CHECK_ARG(V >= 0 && L >= 1 && L <= kGcnTrainMaxLayers, "bad sizes V=%d layers=%d", V, L);
-    if (!ggnn_gcn_train_supported(D))
-        return fail(GGNN_E_UNSUPPORTED, "native GCN training step: hidden sizes 32, 64, 100 (got %d)", D);
+    if (!rt.supported(D))
+        return fail(GGNN_E_UNSUPPORTED, "native GCN training step: hidden sizes %s on this route (got %d)", rt.sizes, D);
     if ((unsigned long long)V * D >= (1ULL << 30)) return fail(GGNN_E_UNSUPPORTED, "V*D must be < 2^30 (32-bit byte offsets)");
     return GGNN_OK;
 }
 
-}  // namespace
-}  // namespace ggnn
-
-using namespace ggnn;
-
-extern "C" int ggnn_gcn_train_supported(int D) { return D == 32 || D == 64 || D == 100; }
-
-extern "C" size_t ggnn_gcn_train_workspace_bytes(int V, int D, int num_layers) {
-    if (V < 0 || num_layers <= 0 || !ggnn_gcn_train_supported(D)) return 0;
-    return gcn_layout(V, D, num_layers).total;
+size_t gcn_train_workspace_bytes(const GcnTrainRoute& rt, int V, int D, int num_layers) {
+    if (V < 0 || num_layers <= 0 || !rt.supported(D)) return 0;
+    return gcn_layout(rt, V, D, num_layers).total;
 }
 
-extern "C" int ggnn_gcn_train_forward_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col,
-                                          const float* val, int64_t nnz, const float* const* W, const float* const* bias,
-                                          const int64_t* row_key, const uint64_t* seeds, float keep_prob, void* ws, size_t ws_bytes,
-                                          int64_t* final_off, ggnn_stream_t stream) {
+int gcn_train_forward(const GcnTrainRoute& rt, const float* h0, int V, int D, int num_layers, const int32_t* row_ptr,
+                      const int32_t* col, const float* val, int64_t nnz, const float* const* W, const float* const* bias,
+                      const int64_t* row_key, const uint64_t* seeds, float keep_prob, void* ws, size_t ws_bytes, int64_t* final_off,
+                      ggnn_stream_t stream) {
     const int L = num_layers;
-    if (int rc = check_shape(V, D, L)) return rc;
+    if (int rc = check_shape(rt, V, D, L)) return rc;
     GGNN_CHECK_ARG(nnz >= 0 && nnz < (1LL << 31), "bad nnz=%lld", (long long)nnz);
     GGNN_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "keep_prob %g outside (0, 1]", (double)keep_prob);
     if (V == 0) return GGNN_OK;
@@ -101,20 +117,19 @@ extern "C" int ggnn_gcn_train_forward_f32(const float* h0, int V, int D, int num
         GGNN_CHECK_ARG(W[l] != nullptr, "null weight pointer of layer %d", l);
         GGNN_CHECK_ARG(!bias || (bias[l] && aligned16(bias[l])), "null or misaligned bias pointer of layer %d", l);
     }
-    const GcnTrainLayout o = gcn_layout(V, D, L);
+    const GcnTrainLayout o = gcn_layout(rt, V, D, L);
     if (ws_bytes < o.total) return fail(GGNN_E_WORKSPACE, "GCN training workspace too small: %zu < %zu", ws_bytes, o.total);
     char* base = reinterpret_cast<char*>(al256(reinterpret_cast<size_t>(ws)));
     auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
 
-    if (int rc = ggnn_gcn_train_pack_f32(W, L, D, f(o.images), stream)) return rc;
+    if (int rc = rt.pack_all(W, L, D, f(o.images), stream)) return rc;
     const float* cur = h0;
     for (int l = 0; l < L; ++l) {
         const bool last = l == L - 1;                                     // ReLU and dropout on all but the last layer (:75-78)
         const bool drop = !last && keep_prob < 1.0f;
         float* out = f(o.H + (size_t)l * o.state);
-        if (int rc = ggnn_gcn_layer_f32(cur, row_ptr, col, val, nnz, f(o.images + (size_t)l * o.slot), bias ? bias[l] : nullptr,
-                                        last ? 0 : 1, row_key, 0, drop ? seeds[l] : 0, drop ? keep_prob : 1.0f, out,
-                                        f(o.S + (size_t)l * o.state), V, D, stream))
+        if (int rc = rt.layer(cur, row_ptr, col, val, nnz, f(o.images + (size_t)l * o.slot), bias ? bias[l] : nullptr, last ? 0 : 1,
+                              row_key, 0, drop ? seeds[l] : 0, drop ? keep_prob : 1.0f, out, f(o.S + (size_t)l * o.state), V, D, stream))
             return rc;
         cur = out;
     }
@@ -122,12 +137,12 @@ extern "C" int ggnn_gcn_train_forward_f32(const float* h0, int V, int D, int num
     return GGNN_OK;
 }
 
-extern "C" int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t,
-                                           const int32_t* col_t, const float* val_t, int64_t nnz, const int64_t* row_key,
-                                           const uint64_t* seeds, float keep_prob, float* const* g_W, float* const* g_b, void* ws,
-                                           size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+int gcn_train_backward(const GcnTrainRoute& rt, const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t,
+                       const int32_t* col_t, const float* val_t, int64_t nnz, const int64_t* row_key, const uint64_t* seeds,
+                       float keep_prob, float* const* g_W, float* const* g_b, void* ws, size_t ws_bytes, ggnn_stream_t stream,
+                       ggnn_stream_t side_stream) {
     const int L = num_layers;
-    if (int rc = check_shape(V, D, L)) return rc;
+    if (int rc = check_shape(rt, V, D, L)) return rc;
     GGNN_CHECK_ARG(nnz >= 0 && nnz < (1LL << 31), "bad nnz=%lld", (long long)nnz);
     GGNN_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "keep_prob %g outside (0, 1]", (double)keep_prob);
     if (V == 0) return GGNN_OK;
@@ -137,7 +152,7 @@ extern "C" int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, i
         GGNN_CHECK_ARG(g_W[l] != nullptr, "null weight-gradient pointer of layer %d", l);
         GGNN_CHECK_ARG(!g_b || g_b[l] != nullptr, "null bias-gradient pointer of layer %d", l);
     }
-    const GcnTrainLayout o = gcn_layout(V, D, L);
+    const GcnTrainLayout o = gcn_layout(rt, V, D, L);
     if (ws_bytes < o.total) return fail(GGNN_E_WORKSPACE, "GCN training workspace too small: %zu < %zu", ws_bytes, o.total);
     char* base = reinterpret_cast<char*>(al256(reinterpret_cast<size_t>(ws)));
     auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -162,11 +177,61 @@ extern "C" int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, i
         if (l == 0) break;                                                // h0 is data: no dx of layer 0
         // ---- main stream: dP_{l-1} = [out_{l-1} > 0] * mask_{l-1} / keep * A_hat^T (dP_l W_l^T) ----
         float* below = f(o.dP + (size_t)(l - 1) * o.state);
-        if (int rc = ggnn_gcn_layer_bwd_f32(dP, row_ptr_t, col_t, val_t, nnz, f(o.images + (size_t)(L + l - 1) * o.slot),
-                                            f(o.H + (size_t)(l - 1) * o.state), row_key, 0, drop ? seeds[l - 1] : 0,
-                                            drop ? keep_prob : 1.0f, below, V, D, stream))
+        if (int rc = rt.layer_bwd(dP, row_ptr_t, col_t, val_t, nnz, f(o.images + (size_t)(L + l - 1) * o.slot),
+                                  f(o.H + (size_t)(l - 1) * o.state), row_key, 0, drop ? seeds[l - 1] : 0, drop ? keep_prob : 1.0f,
+                                  below, V, D, stream))
             return rc;
         dP = below;
     }
     return stream_order_after(st, side);          // the caller's next launches (optimizer, next forward) see every product
+}
+
+}  // namespace
+}  // namespace ggnn
+
+using namespace ggnn;
+
+extern "C" int ggnn_gcn_train_supported(int D) { return D == 32 || D == 64 || D == 100; }
+
+extern "C" size_t ggnn_gcn_train_workspace_bytes(int V, int D, int num_layers) {
+    return gcn_train_workspace_bytes(kGcnFusedRoute, V, D, num_layers);
+}
+
+extern "C" int ggnn_gcn_train_forward_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col,
+                                          const float* val, int64_t nnz, const float* const* W, const float* const* bias,
+                                          const int64_t* row_key, const uint64_t* seeds, float keep_prob, void* ws, size_t ws_bytes,
+                                          int64_t* final_off, ggnn_stream_t stream) {
+    return gcn_train_forward(kGcnFusedRoute, h0, V, D, num_layers, row_ptr, col, val, nnz, W, bias, row_key, seeds, keep_prob, ws,
+                             ws_bytes, final_off, stream);
+}
+
+extern "C" int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t,
+                                           const int32_t* col_t, const float* val_t, int64_t nnz, const int64_t* row_key,
+                                           const uint64_t* seeds, float keep_prob, float* const* g_W, float* const* g_b, void* ws,
+                                           size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    return gcn_train_backward(kGcnFusedRoute, d_final, V, D, num_layers, row_ptr_t, col_t, val_t, nnz, row_key, seeds, keep_prob, g_W,
+                              g_b, ws, ws_bytes, stream, side_stream);
+}
+
+// ---- the same sequences on the column-panel kernels (hidden sizes 128 / 192 / 256) ------------------------------------------------
+extern "C" int ggnn_gcn_panel_train_supported(int D) { return D == 128 || D == 192 || D == 256; }
+
+extern "C" size_t ggnn_gcn_panel_train_workspace_bytes(int V, int D, int num_layers) {
+    return gcn_train_workspace_bytes(kGcnPanelRoute, V, D, num_layers);
+}
+
+extern "C" int ggnn_gcn_panel_train_forward_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr,
+                                                const int32_t* col, const float* val, int64_t nnz, const float* const* W,
+                                                const float* const* bias, const int64_t* row_key, const uint64_t* seeds,
+                                                float keep_prob, void* ws, size_t ws_bytes, int64_t* final_off, ggnn_stream_t stream) {
+    return gcn_train_forward(kGcnPanelRoute, h0, V, D, num_layers, row_ptr, col, val, nnz, W, bias, row_key, seeds, keep_prob, ws,
+                             ws_bytes, final_off, stream);
+}
+
+extern "C" int ggnn_gcn_panel_train_backward_f32(const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t,
+                                                 const int32_t* col_t, const float* val_t, int64_t nnz, const int64_t* row_key,
+                                                 const uint64_t* seeds, float keep_prob, float* const* g_W, float* const* g_b, void* ws,
+                                                 size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    return gcn_train_backward(kGcnPanelRoute, d_final, V, D, num_layers, row_ptr_t, col_t, val_t, nnz, row_key, seeds, keep_prob, g_W,
+                              g_b, ws, ws_bytes, stream, side_stream);
 }

@@ -2041,6 +2041,47 @@ def gcn_train_pack(weights: Sequence[torch.Tensor]) -> torch.Tensor:
     return images
 
 
+def gcn_panel_layer_bwd(dP: torch.Tensor, graph: GCNGraph, W: torch.Tensor, gate_out: torch.Tensor, keep_prob: float = 1.0,
+                        seed: int = 0, row_key: Optional[torch.Tensor] = None, img: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gcn_layer_bwd at hidden sizes 128 / 192 / 256, one launch of the panel kernel (ggnn_gcn_panel_layer_bwd_f32):
+    -> [gate_out > 0] * dropout(A_hat^T (dP W^T)).  Bit-identical to act_bwd(dropout(gcn_layer(dP, graph, W, transpose=True,
+    panel=True)[0], ...), gate_out, "relu").  img: the panel images of W^T (gcn_panel_pack(W, True)) when the caller has them."""
+    lib = _lib.load()
+    _req(dP, torch.float32, "dP")
+    _req(gate_out, torch.float32, "gate_out")
+    V, D = dP.shape
+    if V != graph.num_nodes:
+        raise ValueError("dP has %d rows, the graph %d nodes" % (V, graph.num_nodes))
+    if tuple(W.shape) != (D, D) or tuple(gate_out.shape) != (V, D):
+        raise ValueError("W must be [%d, %d], gate_out [%d, %d]" % (D, D, V, D))
+    if row_key is not None:
+        _req(row_key, torch.int64, "row_key")
+    if not gcn_panel_supported(D):
+        raise ValueError("gcn_panel_layer_bwd: hidden size %d has no panel GCN kernel" % D)
+    if img is None:
+        img = gcn_panel_pack(W.contiguous(), True)
+    out = torch.empty_like(dP)
+    _launch("gcn_panel_layer_bwd[D=%d]" % D, lambda: lib.ggnn_gcn_panel_layer_bwd_f32(
+        _ptr(dP), _ptr(graph.row_ptr_t), _ptr(graph.col_t), _ptr(graph.val_t), graph.nnz, _ptr(img), _ptr(gate_out), _ptr(row_key), 0,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, float(keep_prob), _ptr(out), V, D, _stream()))
+    return out
+
+
+def gcn_panel_train_pack(weights: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Every panel image of a GCN training step in one launch (ggnn_gcn_panel_train_pack_f32) -> float32 [2L - 1, slot]: row l the
+    images of W_l, row L + l - 1 those of W_l^T for l >= 1; a row's first ggnn_gcn_panel_image_bytes(D) / 4 floats are gcn_panel_pack's."""
+    lib = _lib.load()
+    Ws = [_req(w, torch.float32, "W") for w in weights]
+    L, D = len(Ws), Ws[0].shape[0]
+    if not gcn_panel_supported(D) or any(tuple(w.shape) != (D, D) for w in Ws):
+        raise ValueError("gcn_panel_train_pack: every W must be [D, D] with D in 128 / 192 / 256")
+    slot = (lib.ggnn_gcn_panel_image_bytes(D) + 255) // 256 * 256 // 4
+    images = torch.empty((2 * L - 1, slot), dtype=torch.float32, device=Ws[0].device)
+    w_arr = _ptr_array(Ws)
+    _launch("gcn_panel_train_pack[D=%d,L=%d]" % (D, L), lambda: lib.ggnn_gcn_panel_train_pack_f32(w_arr, L, D, _ptr(images), _stream()))
+    return images
+
+
 def _gcn_propagate(name: str, workspace_bytes, entry, h0: torch.Tensor, graph: GCNGraph, weights: Sequence[torch.Tensor],
                    biases: Optional[Sequence[torch.Tensor]]) -> torch.Tensor:
     """One whole-stack inference call: `entry` is ggnn_gcn_propagate_f32 or its panel form, `workspace_bytes` its size query."""

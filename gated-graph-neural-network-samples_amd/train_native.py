@@ -14,8 +14,9 @@ handful of launches for the weight images and masks, and the optimizer's two lau
 The dense model (chem_tensorflow_dense.py:93-117) has the same step on csrc/ggnn_dense_train.hip (ggnn_dense_train_forward_f32 /
 ggnn_dense_train_backward_f32) when its config asks for it with graph_resident_training = 'native': dense_eligible /
 native_dense_train_step below.  The sparse GCN (chem_tensorflow_gcn.py:62-82) has it on csrc/ggnn_gcn_train.hip
-(ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32) under native_training = True: gcn_eligible / native_gcn_train_step at
-the end of this file.
+(ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32; at hidden sizes 128 / 192 / 256 with gcn_panel_layers = True their panel
+twins ggnn_gcn_panel_train_forward_f32 / ggnn_gcn_panel_train_backward_f32) under native_training = True: gcn_eligible /
+native_gcn_train_step at the end of this file.
 
 The sparse model with propagation attention on the compacted route (chem_tensorflow_sparse.py:147-149, 170-196;
 SparseGGNNChemModel.attention_route) has it on ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32 when its
@@ -525,18 +526,34 @@ def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
 
 
 # ---- the sparse GCN (chem_tensorflow_gcn.py:62-82) on ggnn_gcn_train_forward_f32 / ggnn_gcn_train_backward_f32 ------------------------
+def _gcn_native_entries(model):
+    """The entry points of the model's native step, chosen once: (launch-name stem, workspace query, forward call, backward call), or
+    None when its hidden size has none.  A model on the panel route (params['gcn_panel_layers'] at 128 / 192 / 256 on a GPU,
+    gcn_model.gcn_panel_route) takes the ggnn_gcn_panel_train_* family; every other model the ggnn_gcn_train_* family (32 / 64 / 100)."""
+    lib = _lib.load()
+    D = int(model.params['hidden_size'])
+    if model.gcn_panel_route():
+        if not lib.ggnn_gcn_panel_train_supported(D):
+            return None
+        return ("gcn_panel_train", lib.ggnn_gcn_panel_train_workspace_bytes, lib.ggnn_gcn_panel_train_forward_f32,
+                lib.ggnn_gcn_panel_train_backward_f32)
+    if not lib.ggnn_gcn_train_supported(D):
+        return None
+    return "gcn_train", lib.ggnn_gcn_train_workspace_bytes, lib.ggnn_gcn_train_forward_f32, lib.ggnn_gcn_train_backward_f32
+
+
 def gcn_model_eligible(model) -> bool:
     """The part of `gcn_eligible` that depends on the model only: a GCN model that asks for the native step
     (params['native_training'], read with .get: not a key of default_params, whose keys a reference checkpoint must match) on a GPU,
-    a hidden size with the fused layer kernels, the fused optimizer over exactly the trainable variables, nothing frozen, one-layer
-    readout MLPs, no active data-parallel context."""
+    a hidden size with the fused layer kernels (or, with params['gcn_panel_layers'] too, with the panel kernels: _gcn_native_entries),
+    the fused optimizer over exactly the trainable variables, nothing frozen, one-layer readout MLPs, no active data-parallel context."""
     p = getattr(model, "params", None)
     if p is None or not p.get('native_training') or not hasattr(model, "_graph") or 'gcn_use_bias' not in p:
         return False
     if not torch.cuda.is_available() or torch.device(model.device).type != 'cuda' or not backward.USE_NATIVE_STEP or not p['use_graph']:
         return False
     L = int(p['num_timesteps'])
-    if not _lib.load().ggnn_gcn_train_supported(int(p['hidden_size'])) or L < 1 or L > 64:
+    if L < 1 or L > 64 or _gcn_native_entries(model) is None:
         return False
     dist = getattr(model, "dist", None)
     if dist is not None and dist.active:
@@ -576,11 +593,11 @@ def gcn_eligible(model, batch_data: Dict[str, Any]) -> bool:
 
 
 def native_gcn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
-    """native_train_step for the sparse GCN: two C calls for the layers and every graph-model gradient, the readout + loss per task
-    between them, clip + Adam.  No torch.autograd; the dropout masks are the autograd route's (the same seeds and row keys)."""
-    lib = _lib.load()
+    """native_train_step for the sparse GCN: two C calls for the layers and every graph-model gradient (the ggnn_gcn_train_* pair, or
+    on the panel route the ggnn_gcn_panel_train_* pair: _gcn_native_entries), the readout + loss per task between them, clip + Adam.  No torch.autograd; the dropout masks are the autograd route's (the same seeds and row keys)."""
     p = model.params
     opt = model.optimizer
+    stem, workspace_bytes, train_forward, train_backward = _gcn_native_entries(model)
     model.feed(batch_data)
     ph = model.placeholders
     h0 = ph['initial_node_representation'].contiguous()
@@ -603,10 +620,10 @@ def native_gcn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         # ---- forward: every weight image in one launch, then the L saving layer launches ---------------------------------------
         if getattr(model, "_native_ws", None) is None:
             model._native_ws = _DenseWorkspace()
-        ws = model._native_ws.get(lib.ggnn_gcn_train_workspace_bytes(V, D, L), dev)
+        ws = model._native_ws.get(workspace_bytes(V, D, L), dev)
         final_off = ctypes.c_int64(0)
         w_arr, b_arr = _ptrs(Ws), (None if bs is None else _ptrs(bs))
-        ops._launch("gcn_train_forward[L=%d]" % L, lambda: lib.ggnn_gcn_train_forward_f32(
+        ops._launch("%s_forward[L=%d]" % (stem, L), lambda: train_forward(
             h0.data_ptr(), V, D, L, graph.row_ptr.data_ptr(), ops._ptr(graph.col), ops._ptr(graph.val), graph.nnz, w_arr, b_arr,
             ops._ptr(uid), seeds, keep, ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
         off = int(final_off.value)
@@ -625,7 +642,7 @@ def native_gcn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         d_final = (_readout_multi_backward if multi else _readout_per_task_backward)(model, saved, dens, gviews)
         gW_arr = _ptrs([gviews[w.data_ptr()] for w in Ws])
         gb_arr = None if bs is None else _ptrs([gviews[b.data_ptr()] for b in bs])
-        ops._launch("gcn_train_backward[L=%d]" % L, lambda: lib.ggnn_gcn_train_backward_f32(
+        ops._launch("%s_backward[L=%d]" % (stem, L), lambda: train_backward(
             d_final.data_ptr(), V, D, L, graph.row_ptr_t.data_ptr(), ops._ptr(graph.col_t), ops._ptr(graph.val_t), graph.nnz,
             ops._ptr(uid), seeds, keep, gW_arr, gb_arr, ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
 

@@ -913,6 +913,36 @@ int ggnn_gcn_train_backward_f32(const float* d_final, int V, int D, int num_laye
                                 float* const* g_W, float* const* g_b, void* ws, size_t ws_bytes, ggnn_stream_t stream,
                                 ggnn_stream_t side_stream);
 
+/* ---- sparse GCN: the same native step at hidden sizes 128 / 192 / 256 on the column-panel kernels (ggnn_gcn_panel.hip) -----------
+ * The optimisation step of chem_tensorflow.py:183-191 over the layers of chem_tensorflow_gcn.py:62-82 at the wide sizes.
+ * The twins of the six entry points above, with their arguments, validation, workspace layout, streams and results; in place of
+ * gcn_model.GCNLayerFn's per-layer backward on the panel route -- a transposed ggnn_gcn_panel_layer_f32, ggnn_dropout_f32 and
+ * ggnn_act_bwd_f32 over [V,D], two ggnn_gcn_panel_pack_weights_f32, a ggnn_gemm_tn_f32 and a ggnn_colsum_f32, enqueued from Python.
+ * ggnn_gcn_panel_layer_bwd_f32: ggnn_gcn_layer_bwd_f32 on the panel kernel, img_T = the panel images of W^T: bit-identical to
+ *   ggnn_gcn_panel_layer_f32 (transposed CSR, img_T) + ggnn_dropout_f32 + ggnn_act_bwd_f32.
+ * ggnn_gcn_panel_train_pack_f32: ggnn_gcn_train_pack_f32 in the panel format: slots of ggnn_gcn_panel_image_bytes(D) rounded up to
+ *   256 bytes, each the D / 64 panel images of W_l (slot l) or W_l^T (slot num_layers + l - 1, l >= 1) --
+ *   ggnn_gcn_panel_pack_weights_f32's images bit for bit.
+ * ggnn_gcn_panel_train_supported: 1 for the hidden sizes with this step (128, 192, 256); ggnn_gcn_train_supported and the
+ *   ggnn_gcn_train_* calls keep their values and return codes at these sizes.
+ * ggnn_gcn_panel_train_forward_f32 / _backward_f32: ggnn_gcn_train_forward_f32 / _backward_f32 over ggnn_gcn_panel_train_pack_f32,
+ *   ggnn_gcn_panel_layer_f32 and ggnn_gcn_panel_layer_bwd_f32; ws: ggnn_gcn_panel_train_workspace_bytes(V, D, num_layers) bytes
+ *   (0 for an unsupported D). */
+int ggnn_gcn_panel_layer_bwd_f32(const float* dP, const int32_t* row_ptr_t, const int32_t* col_t, const float* val_t, int64_t nnz,
+                                 const float* img_T, const float* gate_out, const int64_t* row_key, int64_t row_key_base,
+                                 uint64_t seed, float keep_prob, float* out, int V, int D, ggnn_stream_t stream);
+int ggnn_gcn_panel_train_pack_f32(const float* const* W, int num_layers, int D, float* images, ggnn_stream_t stream);
+int ggnn_gcn_panel_train_supported(int D);
+size_t ggnn_gcn_panel_train_workspace_bytes(int V, int D, int num_layers);
+int ggnn_gcn_panel_train_forward_f32(const float* h0, int V, int D, int num_layers, const int32_t* row_ptr, const int32_t* col,
+                                     const float* val, int64_t nnz, const float* const* W, const float* const* bias,
+                                     const int64_t* row_key, const uint64_t* seeds, float keep_prob, void* ws, size_t ws_bytes,
+                                     int64_t* final_off, ggnn_stream_t stream);
+int ggnn_gcn_panel_train_backward_f32(const float* d_final, int V, int D, int num_layers, const int32_t* row_ptr_t,
+                                      const int32_t* col_t, const float* val_t, int64_t nnz, const int64_t* row_key,
+                                      const uint64_t* seeds, float keep_prob, float* const* g_W, float* const* g_b, void* ws,
+                                      size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
+
 /* ---- measurement aid (bench.py's roofline leg; not on the product path) --------------------------------------------------------
  * The dense bf16 MFMA rate the chip SUSTAINS: `launches` back-to-back launches (~16 ms each) of v_mfma_f32_16x16x32_bf16 on
  * register operands, 8 waves per CU; mode 0 all-zero operands, 1 random operands, 2 the operand pattern and planes of the 3-way

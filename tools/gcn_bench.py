@@ -26,8 +26,11 @@ panel route with the composed route (weighted segment sum -> GEMM -> epilogue, w
 process, `--rounds` interleaved rounds:
   --leg layer    one ReLU layer (images pre-packed), its transposed form (the backward's dx launch) and the inference forward of all
                  layers, per arm median and min .. max over the rounds of the device-event time of `--iters` launches
-  --leg step     one training step through GCNLayerFn on either route
+  --leg step     one training step through GCNLayerFn on either route, and a third arm panel_native: the panel route with
+                 params['native_training'] too (ggnn_gcn_panel_train_forward_f32 / _backward_f32, no torch.autograd)
   panel_faster   True only if the panel arm's whole range lies below the composed arm's
+  native_faster  (step leg) True only if the panel_native arm's whole range lies below the panel arm's -- the autograd step on the
+                 panel route is the fastest route these sizes had; native_speedup_median is against that arm
 --out FILE also writes the JSON there.
 """
 import argparse
@@ -157,11 +160,14 @@ def _emit(a, out):
             f.write(line + "\n")
 
 
-def _panel_models(a, ms):
+def _panel_models(a, ms, native=False):
     cfg = {"hidden_size": a.hidden, "num_timesteps": 4, "batch_size": 100000, "random_seed": 0}
+    arms = (("composed", {}), ("panel", {"gcn_panel_layers": True}))
+    if native:
+        arms += (("panel_native", {"gcn_panel_layers": True, "native_training": True}),)
     return {name: ggnn_amd.SparseGCNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms,
                                                "--config": dict(cfg, **extra)})
-            for name, extra in (("composed", {}), ("panel", {"gcn_panel_layers": True}))}
+            for name, extra in arms}
 
 
 def panel_layer_leg(a):
@@ -204,13 +210,15 @@ def panel_layer_leg(a):
 
 
 def panel_step_leg(a):
-    """One training step through GCNLayerFn at a panel size: panel route against composed route, interleaved."""
+    """One training step at a panel size: composed route and panel route through GCNLayerFn, and the panel route on the native
+    sequences, interleaved."""
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
     arms = {}
-    for name, model in _panel_models(a, ms).items():
+    for name, model in _panel_models(a, ms, native=True).items():
         np.random.seed(0)
         feed = dict(next(iter(model.make_minibatch_iterator(model.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
-        assert model.gcn_panel_route() == (name == "panel"), name
+        assert model.gcn_panel_route() == (name != "composed"), name
+        assert ggnn_amd.train_native.gcn_eligible(model, feed) == (name == "panel_native"), name
         arms[name] = (model, feed)
     V, D = arms["panel"][1]["initial_node_representation"].shape
     for model, feed in arms.values():                       # warm-up: workspaces, caching allocator, LDS attributes
@@ -227,6 +235,8 @@ def panel_step_leg(a):
         out[name] = {"step_ms": _spread(dev[name], 4), "enqueue_ms_median": round(float(np.median(host[name])), 4)}
     out["panel_faster"] = bool(max(dev["panel"]) < min(dev["composed"]))
     out["speedup_median"] = round(float(np.median(dev["composed"]) / np.median(dev["panel"])), 3)
+    out["native_faster"] = bool(max(dev["panel_native"]) < min(dev["panel"]))
+    out["native_speedup_median"] = round(float(np.median(dev["panel"]) / np.median(dev["panel_native"])), 3)
     _emit(a, out)
 
 
