@@ -21,6 +21,8 @@ SYMBOLS = {
     "ggnn_matrix_path_is_split": (c_int, []),
     "ggnn_gru_forward_format": (c_int, []),
     "ggnn_gru_form_set": (c_int, [c_int]),
+    "ggnn_gru_describe": (c_int, [c_int] * 11 + [POINTER(c_int32)]),
+    "ggnn_gru_cells": (c_int, [POINTER(c_int32), c_int]),
     "ggnn_absmax_f32": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p]),
     "ggnn_last_error": (c_char_p, []),
     "ggnn_csr_workspace_bytes": (c_size_t, [c_int64, c_int]),

@@ -26,6 +26,7 @@
 // segment (or of the next pass's first segment) is fetched while the current one is being multiplied.
 // All accumulation orders are those of the plain [x|h] / [x|r*h] products (segments in order, h last).
 #include "ggnn_split.hpp"
+#include "ggnn_gru_cells.hpp"
 #include <type_traits>
 
 #ifndef GGNN_COOP_DEPTH
@@ -63,18 +64,16 @@ static int gru_ablate_bits() { static const int v = [] { const char* e = getenv(
 
 namespace ggnn {
 
-// ticket source of a fused GRU instantiation (the kernel's TK)
-constexpr int kTkRuntime = -1, kTkStatic = 0, kTkCounter = 1;
-
 // large hidden sizes (multiples of 64 from 128): column-panel kernels, ggnn_panel.hip
 int gru_panel_supported(int D);
 int gru_panel_pack_floats(int D, int nx);
-int gru_panel_dispatch(const GruFusedArgs& a, int D, float* packed, hipStream_t st);
+int gru_panel_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st);
+int gru_wide_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st);   // ggnn_gru_wide.hip
 
 // This source is compiled TWICE: as itself (the f32-MFMA instantiations, the dispatch, the C entry points) and, through
 // ggnn_gru_fused_split.hip (GGNN_GRU_TU_SPLIT), for the SPLIT instantiations -- that translation unit is built without
 // packed-f32 vector instructions (build.py: a v_pk_* instruction beside the partner wave's bf16 MFMAs stalls the SIMD).
-int gru_split_launch(int D, int nx, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st);
+int gru_split_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st);
 
 #ifndef GGNN_GRU_TU_SPLIT
 int gru_pack_floats(int D, int nx) {
@@ -838,8 +837,7 @@ static int launch_gru_fused_m(const GruFusedArgs& a_in, float* packed, hipStream
     // Few tiles (the dense model's b = 256 x v = 29: 464): one tile per workgroup, worked cooperatively by its 8 waves (25 MFMAs
     // per stage and wave, weights straight from L2), the workgroups beyond the CU count following as the first ones retire --
     // instead of two-tile tickets on which two waves of a workgroup run the full 175-MFMA stages while six idle.
-    static const int coop_small = [] { const char* e = getenv("GGNN_GRU_COOP_SMALL"); return e ? atoi(e) : 1; }();
-    if (FORM == 0 && coop_small && wt_total > nb && wt_total <= 2 * nb && StageCfg<D>::NT <= NW) nb = wt_total;
+    if (FORM == 0 && gru_coop_small() && wt_total > nb && wt_total <= 2 * nb && StageCfg<D>::NT <= NW) nb = wt_total;
     static std::atomic<unsigned long long> lds_ok{0};        // (one per template instantiation)
     if (lds > 64 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT, TK, G4AVG>, lds, lds_ok));
     hipLaunchKernelGGL((ggnn_gru_fused_kernel<D, NX, NW, SAVE, GATHER, SPLIT, SAVEX, FORM, FMT, TK, G4AVG>), dim3(nb), dim3(NW * 64), lds, st, a, (const float*)packed GGNN_ABL_ARG);
@@ -848,90 +846,11 @@ static int launch_gru_fused_m(const GruFusedArgs& a_in, float* packed, hipStream
 }
 
 #ifdef GGNN_GRU_TU_SPLIT
+// The split-form instantiations (families ring and hot of ggnn_gru_cells.hpp), launched by cell: gru_select() has chosen it.
 // Gather-fused launches: SAVE / SAVEX follow the call -- with save buffers the training instantiation, without them the inference
 // instantiation.  (The plain launches, off the timed path, keep the one instantiation whose stores are skipped at run time.)
-// GGNN_GRU_FORM: ring form of the gather-fused launches (the kernel's FORM): 0 whole images / 8 waves (the form before round 4),
-// 1 two 4-wave workgroups per CU on half-image rings, 2 8 waves on a 3-slot half-image ring with partial waits
-// Default (-1): form 1, except the single-input launch in the exact bf16x3 format.  Round 5, two-piece f16 format
-// (profiles/r05_experiments/gru_forms_f16x2.txt): without a tail round every form takes 63-64 us at R = 0; the reference's
-// 100,000-node batches leave 106 of 6250 tiles for a fourth round, which costs 7.6 us as form 0's cooperative pass and 3.8 us as
-// form 1's single-wave tickets on 512 independent workgroups (R = 0 launch 71.2 -> 66.9 us); with residual inputs form 1 is also
-// the one the register allocator leaves without scratch (88 / 109 us against 99 / 121).  In the exact bf16x3 format form 0 was 3 %
-// ahead of form 1 at R = 0 (round 4).
-std::atomic<int>& gru_form_override();     // ggnn_api.hip: GGNN_GRU_FORM / ggnn_gru_form_set()
-int gru_wide_launch(int D, int nx, int ntw_req, const GruFusedArgs& a, float* packed, hipStream_t st);   // ggnn_gru_wide.hip
-int gru_wide_supported(int D, int nx, const GruFusedArgs& a);
-static int gru_form(int nx, int fmt) {
-    const int v = gru_form_override().load(std::memory_order_relaxed);
-    return v >= 0 ? v : ((nx >= 2 || fmt == kSplitF16x2) ? 1 : 0);
-}
-
-// gather-fused launch of one (NX, NW, FORM): training or inference instantiation by the save buffers
-template <int D, int NX, int NW, int FORM, int FMT>
-static int split_launch_gather(bool save, const GruFusedArgs& a, float* packed, hipStream_t st) {
-    return save ? launch_gru_fused_m<D, NX, NW, true, true, true, true, FORM, FMT>(a, packed, st)
-                : launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT>(a, packed, st);
-}
-// the hot inference launches: ticket source and gather parameters fixed at compile time (the kernel's TK / G4AVG)
-template <int D, int NX, int NW, int FORM, int FMT>
-static int split_launch_hot(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    return a.tickets ? launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT, kTkCounter, true>(a, packed, st)
-                     : launch_gru_fused_m<D, NX, NW, false, true, true, false, FORM, FMT, kTkStatic, true>(a, packed, st);
-}
-
-template <int D, int FMT>
-static int split_launch_d(int nx, bool save, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
-    if constexpr (SplitCfg<D>::OK) {
-        const int f = gru_form(nx, FMT);
-        // form 6: the wide kernel (one wave per SIMD, several tiles per wave; ggnn_gru_wide.hip)
-        // (60 + NTW: the same with NTW tiles per wave where the instantiation exists -- experiments)
-        if (gather && (f == 6 || (f >= 60 && f < 70)) && gru_wide_supported(D, nx, a))
-            return gru_wide_launch(D, nx, f >= 60 ? f - 60 : 0, a, packed, st);
-        if constexpr (D == 100) {
-            // inference at the reference's hidden size, T = 4, mean aggregation, in the forms the default policy picks
-            if (gather && !save && a.g_use_avg && a.g_T == 4) {
-                if (f == 1) {
-                    switch (nx) {
-                        case 1: return split_launch_hot<D, 1, 4, 1, FMT>(a, packed, st);
-                        case 2: return split_launch_hot<D, 2, 4, 1, FMT>(a, packed, st);
-                        case 3: return split_launch_hot<D, 3, 4, 1, FMT>(a, packed, st);
-                    }
-                }
-                if constexpr (FMT == kSplitBf16x3) { if (f == 0 && nx == 1) return split_launch_hot<D, 1, 8, 0, FMT>(a, packed, st); }
-            }
-        }
-        if (gather && f == 2) {
-            switch (nx) {
-                case 1: return split_launch_gather<D, 1, 8, 2, FMT>(save, a, packed, st);
-                case 2: return split_launch_gather<D, 2, 8, 2, FMT>(save, a, packed, st);
-                case 3: return split_launch_gather<D, 3, 8, 2, FMT>(save, a, packed, st);
-            }
-        }
-        if (gather && f == 1) {
-            switch (nx) {
-                case 1: return split_launch_gather<D, 1, 4, 1, FMT>(save, a, packed, st);
-                case 2: return split_launch_gather<D, 2, 4, 1, FMT>(save, a, packed, st);
-                case 3: return split_launch_gather<D, 3, 4, 1, FMT>(save, a, packed, st);
-            }
-        }
-        if (gather) {
-            switch (nx) {
-                case 1: return split_launch_gather<D, 1, 8, 0, FMT>(save, a, packed, st);
-                case 2: return split_launch_gather<D, 2, 8, 0, FMT>(save, a, packed, st);
-                case 3: return split_launch_gather<D, 3, 8, 0, FMT>(save, a, packed, st);
-            }
-        } else {
-            switch (nx) {
-                case 1: return launch_gru_fused_m<D, 1, 8, true, false, true, true, 0, FMT>(a, packed, st);
-                case 2: return launch_gru_fused_m<D, 2, 8, true, false, true, true, 0, FMT>(a, packed, st);
-                case 3: return launch_gru_fused_m<D, 3, 8, true, false, true, true, 0, FMT>(a, packed, st);
-            }
-        }
-    }
-    return fail(GGNN_E_INVALID, "nx %d outside 1..3", nx);
-}
-int gru_split_launch(int D, int nx, bool gather, const GruFusedArgs& a, float* packed, hipStream_t st) {
-    const bool save = a.save_r != nullptr;      // (save_r / save_u / save_c come together: dispatch_nx)
+// The hot inference launches have the ticket source and the gather parameters fixed at compile time (the kernel's TK / G4AVG).
+int gru_split_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st) {
 #ifdef GGNN_PROBE_NX   // register-allocation probe (tools/kernel_regs.sh .../ggnn_gru_fused_split.hip . -DGGNN_PROBE_NX=2): one instantiation
 #ifndef GGNN_PROBE_SAVE
 #define GGNN_PROBE_SAVE true
@@ -954,65 +873,164 @@ int gru_split_launch(int D, int nx, bool gather, const GruFusedArgs& a, float* p
 #ifndef GGNN_PROBE_G4AVG
 #define GGNN_PROBE_G4AVG false
 #endif
+    (void)c;
     return launch_gru_fused_m<100, GGNN_PROBE_NX, GGNN_PROBE_NW, GGNN_PROBE_SAVE, true, true, GGNN_PROBE_SAVEX, GGNN_PROBE_FORM, GGNN_PROBE_FMT,
                               GGNN_PROBE_TK, GGNN_PROBE_G4AVG>(a, packed, st);
 #else
-    const bool f2 = gru_launch_fmt(a.fmt) == kSplitF16x2;            // (per launch: GruFusedArgs::fmt)
-    switch (D) {
-        case 100: return f2 ? split_launch_d<100, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<100, kSplitBf16x3>(nx, save, gather, a, packed, st);
-        case 64: return f2 ? split_launch_d<64, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<64, kSplitBf16x3>(nx, save, gather, a, packed, st);
-        case 32: return f2 ? split_launch_d<32, kSplitF16x2>(nx, save, gather, a, packed, st) : split_launch_d<32, kSplitBf16x3>(nx, save, gather, a, packed, st);
-        default: return fail(GGNN_E_UNSUPPORTED, "no split-form fused GRU for hidden size %d", D);
+    switch (gru_cell_key(c)) {
+#define GGNN_GRU_RING_LAUNCH(D, NX, NW, SAVE, GATHER, SAVEX, FORM, FMT)                                                        \
+        case gru_cell_key(GGNN_GRU_RING_CELL(D, NX, NW, SAVE, GATHER, SAVEX, FORM, FMT)):                                     \
+            return launch_gru_fused_m<D, NX, NW, SAVE, GATHER, true, SAVEX, FORM, FMT>(a, packed, st);
+#define GGNN_GRU_HOT_LAUNCH(NX, NW, FORM, FMT, TK)                                                                           \
+        case gru_cell_key(GGNN_GRU_HOT_CELL(NX, NW, FORM, FMT, TK)):                                                         \
+            return launch_gru_fused_m<100, NX, NW, false, true, true, false, FORM, FMT, TK, true>(a, packed, st);
+        GGNN_GRU_RING_TABLE(GGNN_GRU_RING_LAUNCH)
+        GGNN_GRU_HOT_TABLE(GGNN_GRU_HOT_LAUNCH)
+#undef GGNN_GRU_RING_LAUNCH
+#undef GGNN_GRU_HOT_LAUNCH
+        default: return fail(GGNN_E_UNSUPPORTED, "fused GRU: the selected cell is not in the split-form table (D=%d nx=%d form=%d)", c.D, c.NX, c.FORM);
     }
 #endif
 }
 #else
-template <int D, int NX, int NW, bool SAVE, bool GATHER>
-static int launch_gru_fused(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    if (SplitCfg<D>::OK && split_matrix_path()) return gru_split_launch(D, NX, GATHER, a, packed, st);
-    return launch_gru_fused_m<D, NX, NW, SAVE, GATHER, false>(a, packed, st);
+// ---- selection: which instantiation a launch runs -------------------------------------------------------------------------
+#define GGNN_GRU_ENTRY_RING(...) {GGNN_GRU_RING_CELL(__VA_ARGS__)},
+#define GGNN_GRU_ENTRY_HOT(...) {GGNN_GRU_HOT_CELL(__VA_ARGS__)},
+#define GGNN_GRU_ENTRY_WIDE(...) {GGNN_GRU_WIDE_CELL(__VA_ARGS__)},
+#define GGNN_GRU_ENTRY_PANEL(...) {GGNN_GRU_PANEL_CELL(__VA_ARGS__)},
+#define GGNN_GRU_ENTRY_F32(...) {GGNN_GRU_F32_CELL(__VA_ARGS__)},
+static const GruCell kGruCells[] = {GGNN_GRU_RING_TABLE(GGNN_GRU_ENTRY_RING) GGNN_GRU_HOT_TABLE(GGNN_GRU_ENTRY_HOT)
+                                    GGNN_GRU_WIDE_TABLE(GGNN_GRU_ENTRY_WIDE) GGNN_GRU_PANEL_TABLE(GGNN_GRU_ENTRY_PANEL)
+                                    GGNN_GRU_F32_TABLE(GGNN_GRU_ENTRY_F32)};
+#undef GGNN_GRU_ENTRY_RING
+#undef GGNN_GRU_ENTRY_HOT
+#undef GGNN_GRU_ENTRY_WIDE
+#undef GGNN_GRU_ENTRY_PANEL
+#undef GGNN_GRU_ENTRY_F32
+constexpr int kGruNumCells = (int)(sizeof(kGruCells) / sizeof(kGruCells[0]));
+
+bool gru_has_cell(const GruCell& c) {
+    const uint64_t k = gru_cell_key(c);
+    for (const GruCell& t : kGruCells)
+        if (gru_cell_key(t) == k) return true;
+    return false;
 }
+
+static GruCell gru_wide_cell(int nx, int fmt, int form) {
+    // 6 / 60 / 62: two tiles per wave (bf16x3 with three inputs: one); 61: 8 waves x one tile; 64: the half-image form
+    // (61 / 64 exist for the single-input launch; elsewhere they are 6 by another name)
+    GruCell c{kGruWide, 100, nx, 4, 6, fmt, 0, 0, 1, kTkRuntime, 0, 2, 0};
+    if (form == 61 && nx == 1 && (fmt == kGruFmtF16x2 || (GGNN_WIDE_BF16 && GGNN_WIDE_SET < 3))) { c.NW = 8; c.FORM = 61; c.NTW = 1; }
+    else if (form == 64 && nx == 1 && fmt == kGruFmtF16x2) { c.FORM = 64; c.NTW = 1; c.HALF = 1; }
+    else if (fmt == kGruFmtBf16x3 && nx == 3) c.NTW = 1;
+    return c;
+}
+
+// What the wide form is instantiated for (GGNN_GRU_WIDE_TABLE): the inference launch (no r / u / c / incoming stores) of the tanh
+// cell at hidden size 100 -- the benchmark's launches; training launches, ReLU cells and the other fused sizes stay on the ring
+// forms.
+bool gru_wide_supported(int D, int nx, const GruLaunchDesc& d) {
+    if (D != 100 || !d.gather || d.save || d.save_x || d.act != GGNN_ACT_TANH || nx < 1 || nx > 3) return false;
+    const int f = d.form >= 60 ? d.form : 6;
+    return gru_has_cell(gru_wide_cell(nx, gru_launch_fmt(d.fmt), f));
+}
+
+// GGNN_GRU_FORM: ring form of the gather-fused launches (the kernel's FORM): 0 whole images / 8 waves (the form before round 4),
+// 1 two 4-wave workgroups per CU on half-image rings, 2 8 waves on a 3-slot half-image ring with partial waits
+// Default (-1): form 1, except the single-input launch in the exact bf16x3 format.  Round 5, two-piece f16 format
+// (profiles/r05_experiments/gru_forms_f16x2.txt): without a tail round every form takes 63-64 us at R = 0; the reference's
+// 100,000-node batches leave 106 of 6250 tiles for a fourth round, which costs 7.6 us as form 0's cooperative pass and 3.8 us as
+// form 1's single-wave tickets on 512 independent workgroups (R = 0 launch 71.2 -> 66.9 us); with residual inputs form 1 is also
+// the one the register allocator leaves without scratch (88 / 109 us against 99 / 121).  In the exact bf16x3 format form 0 was 3 %
+// ahead of form 1 at R = 0 (round 4).
+std::atomic<int>& gru_form_override();     // ggnn_api.hip: GGNN_GRU_FORM / ggnn_gru_form_set()
 
 static bool nosave_kernel() {
     static const bool v = [] { const char* e = getenv("GGNN_GRU_NOSAVE_KERNEL"); return e && atoi(e) != 0; }();
     return v;
 }
 
-template <int D>
-static int dispatch_nx(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    const bool save = a.save_r || a.save_u || a.save_c;
-    if (save && !(a.save_r && a.save_u && a.save_c))
-        return fail(GGNN_E_INVALID, "save_r / save_u / save_c must be given together");
-    if (a.g_H) {
-        if (save && !a.save_x) return fail(GGNN_E_INVALID, "the gather-fused GRU saves r/u/c together with the gathered segment (save_x)");
-        switch (a.nx) {
-            case 1: return save ? launch_gru_fused<D, 1, 8, true, true>(a, packed, st) : launch_gru_fused<D, 1, 8, false, true>(a, packed, st);
-            // With residual inputs the inference kernels (SAVE = false) come out of the register allocator with 36-40 B of scratch per
-            // lane, the training instantiations (SAVE = true: the same code plus stores) with none -- so those run both, the
-            // stores skipped at run time when no save buffers are given (a uniform branch).  GGNN_GRU_NOSAVE_KERNEL=1: the others.
-            case 2: return (save || !nosave_kernel()) ? launch_gru_fused<D, 2, 8, true, true>(a, packed, st) : launch_gru_fused<D, 2, 8, false, true>(a, packed, st);
-            case 3: return (save || !nosave_kernel()) ? launch_gru_fused<D, 3, 8, true, true>(a, packed, st) : launch_gru_fused<D, 3, 8, false, true>(a, packed, st);
-            default: return fail(GGNN_E_INVALID, "nx %d outside 1..3", a.nx);
+// THE selection function: gru_fused_dispatch launches what it returns and ggnn_gru_describe reports it.  Host arithmetic only.
+int gru_select(const GruLaunchDesc& d, GruCell& c, GruGeometry& g) {
+    c = GruCell{};
+    g = GruGeometry{};
+    const int D = d.D, nx = d.nx;
+    const bool panel = gru_panel_supported(D);
+    if (!panel && D != 100 && D != 64 && D != 32) return fail(GGNN_E_UNSUPPORTED, "no fused GRU for hidden size %d", D);
+    if (panel && d.gather)
+        return fail(GGNN_E_UNSUPPORTED, "hidden size %d has no gather-fused GRU (use ggnn_gather_segment_sum_f32 + ggnn_gru_packed_f32)", D);
+    if (d.gather && d.save && !d.save_x)
+        return fail(GGNN_E_INVALID, "the gather-fused GRU saves r/u/c together with the gathered segment (save_x)");
+    if (nx < 1 || nx > 3) return fail(GGNN_E_INVALID, "nx %d outside 1..3", nx);
+    const int fmt = gru_launch_fmt(d.fmt);                                   // (per launch: GruFusedArgs::fmt)
+    if (panel) {
+        c = GruCell{GGNN_GRU_PANEL_CELL(D, nx, d.save, d.matrix_split ? fmt : kGruFmtF32)};
+    } else if (!d.matrix_split) {
+        // With residual inputs the gather-fused inference kernels (SAVE = false) come out of the register allocator with 36-40 B of
+        // scratch per lane, the training instantiations (SAVE = true: the same code plus stores) with none -- so those run both, the
+        // stores skipped at run time when no save buffers are given (a uniform branch).  GGNN_GRU_NOSAVE_KERNEL=1: the others.
+        const bool save = d.save || (d.gather && nx >= 2 && !d.nosave_kernel);
+        c = GruCell{GGNN_GRU_F32_CELL(D, nx, save, d.gather)};
+    } else if (!d.gather) {
+        c = GruCell{GGNN_GRU_RING_CELL(D, nx, 8, true, false, true, 0, fmt)};
+    } else {
+        const int f = d.form >= 0 ? d.form : ((nx >= 2 || fmt == kGruFmtF16x2) ? 1 : 0);
+        // form 6: the wide kernel (one wave per SIMD, several tiles per wave; ggnn_gru_wide.hip); 61 / 64: its 8-wave and half-image
+        // forms, 60 / 62: 6 by its other names.  The other values from 60 have no instantiation of their own.
+        if (f == 63 || (f >= 65 && f < 70)) return fail(GGNN_E_UNSUPPORTED, "fused GRU: form %d has no instantiation", f);
+        if ((f == 6 || (f >= 60 && f < 70)) && gru_wide_supported(D, nx, d)) {
+            c = gru_wide_cell(nx, fmt, f);
+        } else if (D == 100 && !d.save && d.use_avg && d.T == 4 && (f == 1 || (f == 0 && nx == 1 && fmt == kGruFmtBf16x3))) {
+            // inference at the reference's hidden size, T = 4, mean aggregation, in the forms the default policy picks
+            c = GruCell{GGNN_GRU_HOT_CELL(nx, f == 1 ? 4 : 8, f, fmt, d.tickets ? kTkCounter : kTkStatic)};
+        } else {
+            const int form = (f == 1 || f == 2) ? f : 0;                     // (a launch the wide kernel does not take: form 0)
+            c = GruCell{GGNN_GRU_RING_CELL(D, nx, form == 1 ? 4 : 8, d.save, true, d.save, form, fmt)};
         }
     }
-    switch (a.nx) {
-        case 1: return save ? launch_gru_fused<D, 1, 8, true, false>(a, packed, st) : launch_gru_fused<D, 1, 8, false, false>(a, packed, st);
-        case 2: return save ? launch_gru_fused<D, 2, 8, true, false>(a, packed, st) : launch_gru_fused<D, 2, 8, false, false>(a, packed, st);
-        case 3: return save ? launch_gru_fused<D, 3, 8, true, false>(a, packed, st) : launch_gru_fused<D, 3, 8, false, false>(a, packed, st);
-        default: return fail(GGNN_E_INVALID, "nx %d outside 1..3", a.nx);
+    if (!gru_has_cell(c)) return fail(GGNN_E_UNSUPPORTED, "fused GRU: no instantiation for this launch (D=%d nx=%d)", D, nx);
+    g.waves = c.NW;
+    g.rows_per_pass = 16 * c.NW * c.NTW;
+    g.wg_per_cu = (c.family == kGruWide ? c.HALF != 0 : c.FORM == 1) ? 2 : 1;
+    g.coop_small = (c.family != kGruWide && c.family != kGruPanel && c.FORM == 0 && gru_coop_small()) ? 1 : 0;
+    return GGNN_OK;
+}
+
+static int gru_f32_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st) {
+    switch (gru_cell_key(c)) {
+#define GGNN_GRU_F32_LAUNCH(D, NX, SAVE, GATHER)                                                                             \
+        case gru_cell_key(GGNN_GRU_F32_CELL(D, NX, SAVE, GATHER)): return launch_gru_fused_m<D, NX, 8, SAVE, GATHER, false>(a, packed, st);
+        GGNN_GRU_F32_TABLE(GGNN_GRU_F32_LAUNCH)
+#undef GGNN_GRU_F32_LAUNCH
+        default: return fail(GGNN_E_UNSUPPORTED, "fused GRU: the selected cell is not in the f32 table (D=%d nx=%d)", c.D, c.NX);
     }
 }
 
 // 1: whole-block stage images, with a gather-fused variant; 2: column-panel kernel (no gather-fused variant); 0: none
 int gru_fused_supported(int D) { return (D == 100 || D == 64 || D == 32) ? 1 : (gru_panel_supported(D) ? 2 : 0); }
 
+static GruLaunchDesc gru_describe_launch(const GruFusedArgs& a, int D) {
+    GruLaunchDesc d{};
+    d.D = D; d.nx = a.nx; d.fmt = a.fmt;
+    d.gather = a.g_H != nullptr; d.save = a.save_r != nullptr; d.save_x = a.save_x != nullptr;
+    d.act = a.act; d.use_avg = a.g_use_avg; d.T = a.g_T; d.tickets = a.tickets != nullptr;
+    d.form = gru_form_override().load(std::memory_order_relaxed);
+    d.matrix_split = split_matrix_path(); d.nosave_kernel = nosave_kernel();
+    return d;
+}
+
 int gru_fused_dispatch(const GruFusedArgs& a, int D, float* packed, hipStream_t st) {
-    if (gru_panel_supported(D)) return gru_panel_dispatch(a, D, packed, st);
-    switch (D) {
-        case 100: return dispatch_nx<100>(a, packed, st);
-        case 64: return dispatch_nx<64>(a, packed, st);
-        case 32: return dispatch_nx<32>(a, packed, st);
-        default: return fail(GGNN_E_UNSUPPORTED, "no fused GRU for hidden size %d", D);
+    const bool save = a.save_r || a.save_u || a.save_c;
+    if (save && !(a.save_r && a.save_u && a.save_c))
+        return fail(GGNN_E_INVALID, "save_r / save_u / save_c must be given together");
+    GruCell c;
+    GruGeometry g;
+    if (int rc = gru_select(gru_describe_launch(a, D), c, g)) return rc;
+    switch (c.family) {
+        case kGruRing: case kGruHot: return gru_split_launch_cell(c, a, packed, st);
+        case kGruWide: return gru_wide_launch_cell(c, a, packed, st);
+        case kGruPanel: return gru_panel_launch_cell(c, a, packed, st);
+        default: return gru_f32_launch_cell(c, a, packed, st);
     }
 }
 #endif   // !GGNN_GRU_TU_SPLIT
@@ -1021,4 +1039,37 @@ int gru_fused_dispatch(const GruFusedArgs& a, int D, float* packed, hipStream_t 
 
 #ifndef GGNN_GRU_TU_SPLIT
 extern "C" int ggnn_gru_is_fused(int D) { return ggnn::gru_fused_supported(D); }
+
+extern "C" int ggnn_gru_describe(int D, int nx, int fmt, int gather, int save, int act, int use_avg, int T, int tickets, int form,
+                                 int matrix_split, int32_t out[17]) {
+    using namespace ggnn;
+    GGNN_CHECK_ARG(out, "null output");
+    GGNN_CHECK_ARG(fmt == 0 || fmt == GGNN_GRU_FMT_F16X2 || fmt == GGNN_GRU_FMT_BF16X3, "gru_fmt %d is not a GGNN_GRU_FMT_* value", fmt);
+    GGNN_CHECK_ARG(act == GGNN_ACT_TANH || act == GGNN_ACT_RELU, "unknown activation %d", act);
+    GGNN_CHECK_ARG(!gather || T > 0, "a gather-fused launch has T > 0 edge types");
+    GruLaunchDesc d{};
+    d.D = D; d.nx = nx; d.fmt = fmt;
+    d.gather = gather != 0; d.save = save != 0; d.save_x = d.gather && d.save;
+    d.act = act; d.use_avg = d.gather ? use_avg : 0; d.T = d.gather ? T : 0; d.tickets = tickets != 0;
+    d.form = form < 0 ? gru_form_override().load(std::memory_order_relaxed) : form;
+    d.matrix_split = matrix_split < 0 ? split_matrix_path() : matrix_split != 0;
+    d.nosave_kernel = nosave_kernel();
+    GruCell c;
+    GruGeometry g;
+    if (int rc = gru_select(d, c, g)) return rc;
+    const int v[17] = {c.family, c.D, c.NX, c.NW, c.FORM, c.FMT, c.SAVE, c.SAVEX, c.GATHER, c.TK, c.G4AVG, c.NTW, c.HALF,
+                       g.waves, g.rows_per_pass, g.wg_per_cu, g.coop_small};
+    for (int i = 0; i < 17; ++i) out[i] = v[i];
+    return GGNN_OK;
+}
+
+extern "C" int ggnn_gru_cells(int32_t* out, int capacity) {
+    using namespace ggnn;
+    for (int i = 0; out && i < kGruNumCells && i < capacity; ++i) {
+        const GruCell& c = kGruCells[i];
+        const int v[kGruCellFields] = {c.family, c.D, c.NX, c.NW, c.FORM, c.FMT, c.SAVE, c.SAVEX, c.GATHER, c.TK, c.G4AVG, c.NTW, c.HALF};
+        for (int j = 0; j < kGruCellFields; ++j) out[kGruCellFields * i + j] = v[j];
+    }
+    return kGruNumCells;
+}
 #endif

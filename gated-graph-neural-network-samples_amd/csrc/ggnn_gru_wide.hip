@@ -46,12 +46,12 @@
 // is finished (any further slots synchronously), divided (one division per row) and split into the next pass's operand planes;
 // slot order and adds are those of ggnn_gather_segment_sum_f32.
 #include "ggnn_split.hpp"
+#include "ggnn_gru_cells.hpp"
 #include <type_traits>
 
 namespace ggnn {
 
-int gru_wide_launch(int D, int nx, int ntw_req, const GruFusedArgs& a, float* packed, hipStream_t st);
-int gru_wide_supported(int D, int nx, const GruFusedArgs& a);
+int gru_wide_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st);
 
 namespace {
 
@@ -993,28 +993,8 @@ int launch_gru_wide(const GruFusedArgs& f, float* packed, hipStream_t st) {
 
 }  // namespace
 
-// What the wide form is instantiated for: the inference launch (no r / u / c stores) of the tanh cell at hidden size 100 -- the
-// benchmark's launches; training launches, ReLU cells and the other fused sizes stay on the ring forms (each instantiation of
-// this kernel is 2 NTW unrolled pass bodies: minutes of compile time apiece).
-// GGNN_WIDE_SET: 1 = nx 1 in the two-piece f16 format only (kernel experiments), 2 = + the residual fan-ins, 3 = + bf16x3.
-#ifndef GGNN_WIDE_SET
-#define GGNN_WIDE_SET 1
-#endif
-#ifndef GGNN_WIDE_BF16
-#define GGNN_WIDE_BF16 0      // 1: also nx 1 in the exact bf16x3 format (experiments)
-#endif
-int gru_wide_supported(int D, int nx, const GruFusedArgs& a) {
-    if (D != 100 || !a.g_H || a.save_r || a.act != GGNN_ACT_TANH || nx < 1 || nx > 3) return 0;
-    const bool f2 = gru_launch_fmt(a.fmt) == kSplitF16x2;
-    if (GGNN_WIDE_SET < 3 && !f2 && !(GGNN_WIDE_BF16 && nx == 1)) return 0;
-    if (GGNN_WIDE_SET < 2 && nx > 1) return 0;
-    return 1;
-}
-
-// ntw_req (experiments: GGNN_GRU_FORM = 60 + NTW): 0 = the default tiles per wave
-int gru_wide_launch(int D, int nx, int ntw_req, const GruFusedArgs& a, float* packed, hipStream_t st) {
-    if (!gru_wide_supported(D, nx, a)) return fail(GGNN_E_UNSUPPORTED, "no wide fused GRU for this launch");
-    const bool f2 = gru_launch_fmt(a.fmt) == kSplitF16x2;
+// The wide form's instantiations are GGNN_GRU_WIDE_TABLE (ggnn_gru_cells.hpp; gru_select / gru_wide_supported choose among them).
+int gru_wide_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st) {
 #ifdef GGNN_WIDE_PROBE_NTW   // register-allocation probe: one instantiation (-DGGNN_WIDE_PROBE_NTW=3 [-DGGNN_WIDE_PROBE_NX=1] [-DGGNN_WIDE_PROBE_FMT=2])
 #ifndef GGNN_WIDE_PROBE_NX
 #define GGNN_WIDE_PROBE_NX 1
@@ -1022,33 +1002,16 @@ int gru_wide_launch(int D, int nx, int ntw_req, const GruFusedArgs& a, float* pa
 #ifndef GGNN_WIDE_PROBE_FMT
 #define GGNN_WIDE_PROBE_FMT kSplitF16x2
 #endif
-    (void)f2; (void)ntw_req;
+    (void)c;
     return launch_gru_wide<100, GGNN_WIDE_PROBE_NX, GGNN_WIDE_PROBE_NTW, GGNN_WIDE_PROBE_FMT>(a, packed, st);
 #else
-    if (f2) {
-        switch (nx) {
-            case 1: return ntw_req == 1 ? launch_gru_wide<100, 1, 1, kSplitF16x2, 8>(a, packed, st)
-                         : ntw_req == 4 ? launch_gru_wide<100, 1, 1, kSplitF16x2, 4, true>(a, packed, st)      // (form 64: the half-image form)
-                                        : launch_gru_wide<100, 1, 2, kSplitF16x2>(a, packed, st);
-#if GGNN_WIDE_SET >= 2
-            case 2: return launch_gru_wide<100, 2, 2, kSplitF16x2>(a, packed, st);
-            case 3: return launch_gru_wide<100, 3, 2, kSplitF16x2>(a, packed, st);
-#endif
-        }
+    switch (gru_cell_key(c)) {
+#define GGNN_GRU_WIDE_LAUNCH(NX, NTW, FMT, NW, HALF, FORM)                                                                   \
+        case gru_cell_key(GGNN_GRU_WIDE_CELL(NX, NTW, FMT, NW, HALF, FORM)): return launch_gru_wide<100, NX, NTW, FMT, NW, HALF>(a, packed, st);
+        GGNN_GRU_WIDE_TABLE(GGNN_GRU_WIDE_LAUNCH)
+#undef GGNN_GRU_WIDE_LAUNCH
+        default: return fail(GGNN_E_UNSUPPORTED, "no wide fused GRU for this launch");
     }
-#if GGNN_WIDE_BF16 && GGNN_WIDE_SET < 3
-    else if (nx == 1) return ntw_req == 1 ? launch_gru_wide<100, 1, 1, kSplitBf16x3, 8>(a, packed, st) : launch_gru_wide<100, 1, 2, kSplitBf16x3>(a, packed, st);
-#endif
-#if GGNN_WIDE_SET >= 3
-    else {
-        switch (nx) {
-            case 1: return launch_gru_wide<100, 1, 2, kSplitBf16x3>(a, packed, st);
-            case 2: return launch_gru_wide<100, 2, 2, kSplitBf16x3>(a, packed, st);
-            case 3: return launch_gru_wide<100, 3, 1, kSplitBf16x3>(a, packed, st);
-        }
-    }
-#endif
-    return fail(GGNN_E_INVALID, "nx %d outside 1..3", nx);
 #endif
 }
 

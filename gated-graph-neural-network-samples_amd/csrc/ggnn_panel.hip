@@ -22,6 +22,7 @@
 // The transform is the same stage loop without the chain: a persistent workgroup is bound to ONE (edge type, panel),
 // keeps that panel image in LDS and walks 16-row tiles of the type's active (source node, type) pairs.
 #include "ggnn_panel.hpp"
+#include "ggnn_gru_cells.hpp"
 #ifndef GGNN_PANEL_PLANES
 #define GGNN_PANEL_PLANES 1        // the panel GRU keeps a fragment's planes resident over the stages that multiply it in a row
 #endif
@@ -488,27 +489,6 @@ static int launch_gru_panel_m(const GruFusedArgs& a_in, float* packed, hipStream
     return GGNN_OK;
 }
 
-template <int D, int NX, bool SAVE>
-static int launch_gru_panel(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    if (split_matrix_path()) return gru_launch_fmt(a.fmt) == kSplitF16x2 ? launch_gru_panel_m<D, NX, SAVE, true, kSplitF16x2>(a, packed, st)
-                                                                 : launch_gru_panel_m<D, NX, SAVE, true>(a, packed, st);
-    return launch_gru_panel_m<D, NX, SAVE, false>(a, packed, st);
-}
-
-template <int D>
-static int dispatch_panel_nx(const GruFusedArgs& a, float* packed, hipStream_t st) {
-    const bool save = a.save_r || a.save_u || a.save_c;
-    if (save && !(a.save_r && a.save_u && a.save_c))
-        return fail(GGNN_E_INVALID, "save_r / save_u / save_c must be given together");
-    if (a.g_H) return fail(GGNN_E_UNSUPPORTED, "hidden size %d has no gather-fused GRU (use ggnn_gather_segment_sum_f32 + ggnn_gru_packed_f32)", D);
-    switch (a.nx) {
-        case 1: return save ? launch_gru_panel<D, 1, true>(a, packed, st) : launch_gru_panel<D, 1, false>(a, packed, st);
-        case 2: return save ? launch_gru_panel<D, 2, true>(a, packed, st) : launch_gru_panel<D, 2, false>(a, packed, st);
-        case 3: return save ? launch_gru_panel<D, 3, true>(a, packed, st) : launch_gru_panel<D, 3, false>(a, packed, st);
-        default: return fail(GGNN_E_INVALID, "nx %d outside 1..3", a.nx);
-    }
-}
-
 int gru_panel_supported(int D) { return D == 128 || D == 192 || D == 256; }
 
 int gru_panel_pack_floats(int D, int nx) {
@@ -522,12 +502,15 @@ int gru_panel_pack_floats(int D, int nx) {
     return panel_gru_images(D, nx) * img;
 }
 
-int gru_panel_dispatch(const GruFusedArgs& a, int D, float* packed, hipStream_t st) {
-    switch (D) {
-        case 128: return dispatch_panel_nx<128>(a, packed, st);
-        case 192: return dispatch_panel_nx<192>(a, packed, st);
-        case 256: return dispatch_panel_nx<256>(a, packed, st);
-        default: return fail(GGNN_E_UNSUPPORTED, "no panel GRU for hidden size %d", D);
+// The panel GRU's instantiations are GGNN_GRU_PANEL_TABLE (ggnn_gru_cells.hpp); gru_select() has chosen the cell.
+int gru_panel_launch_cell(const GruCell& c, const GruFusedArgs& a, float* packed, hipStream_t st) {
+    switch (gru_cell_key(c)) {
+#define GGNN_GRU_PANEL_LAUNCH(D, NX, SAVE, FMT)                                                                              \
+        case gru_cell_key(GGNN_GRU_PANEL_CELL(D, NX, SAVE, FMT)):                                                             \
+            return launch_gru_panel_m<D, NX, SAVE, (FMT) != 0, (FMT) != 0 ? (FMT) : kSplitBf16x3>(a, packed, st);
+        GGNN_GRU_PANEL_TABLE(GGNN_GRU_PANEL_LAUNCH)
+#undef GGNN_GRU_PANEL_LAUNCH
+        default: return fail(GGNN_E_UNSUPPORTED, "no panel GRU for hidden size %d", c.D);
     }
 }
 

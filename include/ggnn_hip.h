@@ -94,6 +94,22 @@ int ggnn_gru_forward_format(void);
  * pass body as 8 waves x one tile / as two 4-wave workgroups per CU on half-image rings.  Process default: environment GGNN_GRU_FORM.  Returns the previous setting.  (Tests and experiments: compare forms
  * inside one process.) */
 int ggnn_gru_form_set(int form);
+/* Which instantiation of the fused GRU forward a launch runs -- the launchers' own selection function, host arithmetic only (never
+ * touches the GPU).  The launch: hidden size D, nx input segments, gru_fmt, gather (ggnn_gru_packed_gather[_train]_f32) or plain
+ * (ggnn_gru_packed_f32 / ggnn_gru_f32), save (r / u / c buffers given; with gather also the gathered segment), act, and of a gather
+ * launch use_avg, T and whether a tile counter is given.  form / matrix_split: the ring form (ggnn_gru_form_set) and 0 or 1 for
+ * GGNN_MATRIX = f32 / split; negative = this process's setting.  (GGNN_GRU_NOSAVE_KERNEL is always this process's.)
+ * out = the cell {family (0 ring, 1 hot: ticket source and gather parameters fixed at compile time, 2 wide, 3 panel, 4 f32 MFMA), D, NX,
+ * NW (waves), FORM, FMT (0 f32 MFMA, else GGNN_GRU_FMT_*), SAVE, SAVEX, GATHER, TK (-1 tested at run time, 0 static tickets, 1
+ * counter), G4AVG, NTW (tiles per wave and pass), HALF} and the launch geometry {waves per workgroup, rows a workgroup takes per
+ * pass, workgroups per CU -- the grid is min(that x CUs, ceil(V / 16)) --, 1 if the grid grows to ceil(V / 16) when that is at most
+ * twice the CU count (ring form 0)}.  Returns what the launch returns for these arguments (0 / GGNN_E_INVALID /
+ * GGNN_E_UNSUPPORTED): a form value without an instantiation of its own (63, 65..69) is refused, not run as another kernel.
+ * ggnn_gru_cells: the tables of instantiations compiled into this library, 13 cell fields each, into out (up to `capacity` cells; out
+ * may be NULL); returns their number. */
+int ggnn_gru_describe(int D, int nx, int gru_fmt, int gather, int save, int act, int use_avg, int T, int tickets, int form,
+                      int matrix_split, int32_t out[17]);
+int ggnn_gru_cells(int32_t* out, int capacity);
 /* out[i] = max |x| over the numel[i] floats at ptrs[i], i < n, in one launch per 32 tensors -- the operand-range check of
  * GGNN_GRU_FMT_F16X2.  A NaN anywhere in tensor i gives out[i] = NaN, an Inf gives Inf (the maximum is taken over the bit patterns
  * of |x|), so a host test `out[i] <= bound` fails on every non-finite input.  ptrs / numel: HOST arrays of n DEVICE pointers /
@@ -371,7 +387,8 @@ int ggnn_gru_is_fused(int D);
  *                               then call ggnn_msg_transform_compact_f32 with W = NULL and ws = packed.
  * tile_counter (ggnn_gru_packed_f32, ggnn_gru_packed_gather_f32): NULL, or a DEVICE int32 that is 0 when the launch
  * starts (the kernel leaves it non-zero).  With a counter the 16-row tiles are handed to the workgroups dynamically:
- * same results, but the launch no longer stretches when other streams hold part of the GPU while it starts. */
+ * same results, but the launch no longer stretches when other streams hold part of the GPU while it starts.  (Hidden sizes
+ * 128 / 192 / 256, the panel kernel, deal their tiles statically: the counter is accepted and left untouched.) */
 size_t ggnn_gru_packed_bytes(int D, int nx);
 int ggnn_gru_pack_weights_f32(const float* Wg, const float* Wc, int nx, int D, int gru_fmt, float* packed, ggnn_stream_t stream);
 int ggnn_gru_packed_f32(const float* const* x_segs, int nx, const float* h, const float* packed, const float* bg,

@@ -3,6 +3,8 @@
 Tolerances (SURVEY 8c / BASELINE.md 4): per kernel atol 1e-6 / rtol 1e-5 against the fp64 oracle;
 final node states after 8 steps atol 1e-5 / rtol 1e-4.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -685,9 +687,22 @@ def test_gru_with_gathered_segment_sum(pkg, oracle, cuda, V, M, D, T, R, avg, fm
 def test_wide_gru_equals_ring_forms(pkg, cuda, V, M, R, avg, fmt, form):
     """The wide form of the gather-fused GRU launch (csrc/ggnn_gru_wide.hip: one wave per SIMD, several tiles per wave sharing every
     weight-fragment read, gate-sequential stages) == the ring forms of csrc/ggnn_gru_fused.hip, BIT FOR BIT: the same products in the
-    same order per accumulator, the same gather arithmetic, the same epilogues -- inference and training (r, u, c, incoming saved)."""
+    same order per accumulator, the same gather arithmetic, the same epilogues -- inference and training (r, u, c, incoming saved).
+
+    The wide kernel is instantiated for the inference launch of the tanh cell with one input in the two-piece f16 format (fmt = 2,
+    R = 0: GGNN_GRU_WIDE_TABLE): in THOSE cases `got` comes from the wide kernel (forms 6 / 61 / 64: two tiles per wave / 8 waves x
+    one tile / the half-image form), which the query below asserts.  Every other launch here -- fmt = 3, R >= 1, the training and the
+    ReLU launches of every case -- is one the wide kernel does not take: under these form values it runs ring form 0, so those
+    comparisons hold the default ring form (form 1; form 0 itself for fmt = 3 at R = 0) against ring form 0.
+    tests/test_gpu_gru_fwd_cells.py runs every instantiation under its own name."""
     lib = pkg._lib.load()
     D, T = 100, 4
+    out = (ctypes.c_int32 * 17)()
+    assert lib.ggnn_gru_describe(D, R + 1, fmt, 1, 0, 0, int(avg), T, 0, form, -1, out) == 0
+    if lib.ggnn_matrix_path_is_split():
+        wide = fmt == 2 and R == 0
+        assert (out[0] == 2) == wide and (not wide or (out[4], out[3], out[11], out[12]) == {6: (6, 4, 2, 0), 61: (61, 8, 1, 0), 64: (64, 4, 1, 1)}[form])
+        assert wide or (out[0], out[4]) == (0, 0)                                                 # (the generic ring form 0)
     rng = np.random.default_rng(V * 11 + M + R)
     h, adj, nin = random_graph_batch(rng, V, M, T, D, sorted_src=False)
     nx = R + 1
