@@ -162,6 +162,8 @@ SYMBOLS = {
     "ggnn_probe_mfma_rate": (c_int, [c_int, c_int, c_void_p, c_size_t, POINTER(ctypes.c_double), POINTER(ctypes.c_double), c_void_p]),
     "ggnn_gemm_tn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ggnn_gemm_tn_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ggnn_gemm_tn_acc_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
     "ggnn_pack_batch_tables": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "ggnn_sparse_train_prepare_f32": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_void_p), c_float, POINTER(c_uint64),
@@ -177,6 +179,22 @@ SYMBOLS = {
                                                c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the same step at the column-panel hidden sizes 128 / 192 / 256 (params['native_panel_training'])
+    "ggnn_sparse_train_panel_supported": (c_int, [c_int]),
+    "ggnn_sparse_train_panel_prepare_f32": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_void_p), c_float, POINTER(c_uint64),
+                                                    POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_void_p),
+                                                    POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "ggnn_sparse_train_panel_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64, c_int]),
+    "ggnn_sparse_train_panel_forward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                                    c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                                    POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                                    POINTER(c_int32), c_int, c_void_p, c_size_t, POINTER(c_int64), c_void_p]),
+    "ggnn_sparse_train_panel_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int64), c_void_p, c_int, c_int,
+                                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
+                                                     POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                                     POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p,
+                                                     c_void_p]),
     # the same step with propagation attention on the compacted route (params['compact_attention'] == 'native')
     "ggnn_sparse_attn_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64, c_int, c_int64]),
     "ggnn_sparse_attn_train_forward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

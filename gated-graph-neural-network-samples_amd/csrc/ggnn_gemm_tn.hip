@@ -88,13 +88,14 @@ __global__ __launch_bounds__(kTnWaves * 64) void gemm_tn_kernel(const float* __r
     }
 }
 
-// C[i] = sum over the S partials, in order
-__global__ void gemm_tn_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int KN, int S) {
+// C[k][n] (row stride ldc) = sum over the S partials, in order; accumulate: that sum is then added to C's contents, once
+__global__ void gemm_tn_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int KN, int N, int ldc, int S, int accumulate) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= KN) return;
     float s = 0.f;
     for (int p = 0; p < S; ++p) s += part[(size_t)p * KN + i];
-    C[i] = s;
+    float* dst = C + (size_t)(i / N) * ldc + i % N;
+    *dst = accumulate ? *dst + s : s;
 }
 
 static int tn_splits(int M, int K) {
@@ -106,8 +107,8 @@ static int tn_splits(int M, int K) {
 }
 
 template <int NT>
-static int launch_tn(const float* A, int lda, const float* B, int ldb, float* C, float* part, int M, int K, int N, int S,
-                     hipStream_t st) {
+static int launch_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int accumulate, float* part, int M, int K,
+                     int N, int S, hipStream_t st) {
     const int kgroups = (K + 16 * kTnWaves - 1) / (16 * kTnWaves);
     int rows = (M + S - 1) / S;
     rows = (rows + kTnSlab - 1) / kTnSlab * kTnSlab;
@@ -116,7 +117,8 @@ static int launch_tn(const float* A, int lda, const float* B, int ldb, float* C,
     if (lds > 64 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gemm_tn_kernel<NT>, lds, lds_ok));
     hipLaunchKernelGGL((gemm_tn_kernel<NT>), dim3(kgroups, S), dim3(kTnWaves * 64), lds, st, A, lda, B, ldb, part, M, K, N, rows);
     GGNN_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((K * N + 255) / 256), dim3(256), 0, st, (const float*)part, C, K * N, S);
+    hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((K * N + 255) / 256), dim3(256), 0, st, (const float*)part, C, K * N, N, ldc, S,
+                       accumulate);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }
@@ -130,14 +132,18 @@ extern "C" size_t ggnn_gemm_tn_workspace_bytes(int M, int K, int N) {
     return (size_t)tn_splits(M, K) * K * N * sizeof(float) + 256;
 }
 
-extern "C" int ggnn_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, float* C, int M, int K, int N, void* ws,
-                                size_t ws_bytes, ggnn_stream_t stream) {
+// ggnn_gemm_tn_f32 with a destination row stride (ldc >= N: C may be a row block of a wider matrix) and, with accumulate != 0, the
+// product ADDED to C's contents: the same first pass, the partials summed in their fixed order and that sum added to C once.
+extern "C" int ggnn_gemm_tn_acc_f32(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int accumulate, int M, int K,
+                                    int N, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(M >= 0 && K > 0 && N > 0 && N % 4 == 0 && N <= 512, "bad sizes M=%d K=%d N=%d (N a multiple of 4, <= 512)", M, K, N);
     GGNN_CHECK_ARG(lda >= K && ldb >= N && ldb % 4 == 0, "lda %d / ldb %d too small or ldb not a multiple of 4", lda, ldb);
+    GGNN_CHECK_ARG(ldc >= N, "ldc %d smaller than N %d", ldc, N);
     GGNN_CHECK_ARG(C, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (M == 0) {
-        GGNN_CHECK_HIP(hipMemsetAsync(C, 0, (size_t)K * N * sizeof(float), st));
+        if (!accumulate)
+            GGNN_CHECK_HIP(hipMemset2DAsync(C, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)K, st));
         return GGNN_OK;
     }
     GGNN_CHECK_ARG(A && B && ws && aligned16(B) && aligned16(ws), "null or misaligned pointer");
@@ -146,9 +152,15 @@ extern "C" int ggnn_gemm_tn_f32(const float* A, int lda, const float* B, int ldb
     float* part = static_cast<float*>(ws);
     const int S = tn_splits(M, K);
     const int nt = (N + 15) / 16;
-    if (nt <= 7) return launch_tn<7>(A, lda, B, ldb, C, part, M, K, N, S, st);
-    if (nt <= 13) return launch_tn<13>(A, lda, B, ldb, C, part, M, K, N, S, st);
-    if (nt <= 19) return launch_tn<19>(A, lda, B, ldb, C, part, M, K, N, S, st);
-    if (nt <= 25) return launch_tn<25>(A, lda, B, ldb, C, part, M, K, N, S, st);
-    return launch_tn<32>(A, lda, B, ldb, C, part, M, K, N, S, st);
+    const int acc = accumulate ? 1 : 0;
+    if (nt <= 7) return launch_tn<7>(A, lda, B, ldb, C, ldc, acc, part, M, K, N, S, st);
+    if (nt <= 13) return launch_tn<13>(A, lda, B, ldb, C, ldc, acc, part, M, K, N, S, st);
+    if (nt <= 19) return launch_tn<19>(A, lda, B, ldb, C, ldc, acc, part, M, K, N, S, st);
+    if (nt <= 25) return launch_tn<25>(A, lda, B, ldb, C, ldc, acc, part, M, K, N, S, st);
+    return launch_tn<32>(A, lda, B, ldb, C, ldc, acc, part, M, K, N, S, st);
+}
+
+extern "C" int ggnn_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, float* C, int M, int K, int N, void* ws,
+                                size_t ws_bytes, ggnn_stream_t stream) {
+    return ggnn_gemm_tn_acc_f32(A, lda, B, ldb, C, N, 0, M, K, N, ws, ws_bytes, stream);
 }

@@ -28,23 +28,15 @@
 
 namespace ggnn {
 
-__host__ __device__ constexpr int panel_gru_bwd_images(int D, int nx) { return 3 * (nx + 1) * (D / 64); }
-
-// image i = (block b, operand w, panel p), b = 0: the h rows, b = 1 + s: the rows of x segment s;  w = 0: Wc^T, 1: Wg_r^T, 2: Wg_u^T
-// image[k][n] = B(k, 64p + n) with out[:, n] = sum_k A[:, k] B(k, n):  B(k, n) = W[seg D + n][c0 + k]
+// image order: panel_gru_bwd_image_src (ggnn_panel.hpp)
 template <int D, bool SPLIT>
 __global__ void gru_bwd_panel_pack_kernel(const float* __restrict__ Wg, const float* __restrict__ Wc, int nx, float* __restrict__ out) {
     using C = PanelCfg<D>;
-    constexpr int NP = C::NP;
     const int i = blockIdx.y;
-    const int b = i / (3 * NP), w = (i / NP) % 3, p = i % NP;
-    const int seg = b == 0 ? nx : b - 1;
-    const float* W = w == 0 ? Wc : Wg;
-    const int ldw = w == 0 ? D : 2 * D;
-    const int k0 = w == 2 ? D : 0;
+    const PanelSrc<true> src = panel_gru_bwd_image_src<D>(Wg, Wc, nx, i);
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-    if constexpr (SPLIT) pack_panel_gru_split_image<D, kSplitBf16x3, true>(W, k0, seg * D + p * C::BN, ldw, out + (size_t)i * PanelGruSplitCfg<D>::IMG, first, stride);
-    else pack_panel_image<D, true>(W, k0, seg * D + p * C::BN, ldw, out + (size_t)i * C::IMG, first, stride);
+    if constexpr (SPLIT) pack_panel_gru_split_image_fn<D, kSplitBf16x3>(src, out + (size_t)i * PanelGruSplitCfg<D>::IMG, first, stride);
+    else pack_panel_image_fn<D>(src, out + (size_t)i * C::IMG, first, stride);
 }
 
 // fragment of rows of a [V, ld] array at column offset c0 (dpu: the second half of dpg's rows)

@@ -34,31 +34,6 @@
 
 namespace ggnn {
 
-// ---- the transform's panel in 3-way split form (ggnn_split.hpp): image = three bf16 planes [c2][g][n < 64][8 x bf16] -----------
-template <int D>
-struct PanelSplitCfg {
-    static constexpr int NC2 = D / 32;
-    static constexpr int PLANE_BYTES = NC2 * 4 * 64 * 16;          // D * 128
-    static constexpr int IMG_BYTES = 3 * PLANE_BYTES;              // 96 KiB at D = 256: ONE image per workgroup, no ring
-    static constexpr int IMG = IMG_BYTES / 4;
-};
-
-template <int D>
-__device__ __forceinline__ void pack_panel_split_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
-                                                       int first, int stride) {
-    using C = PanelSplitCfg<D>;
-    constexpr int PW = C::PLANE_BYTES / 4;
-    for (int i = first; i < C::IMG; i += stride) {
-        const int plane = i / PW, w = i % PW;
-        const int slot = w >> 2, pr = w & 3;
-        const int n = slot % 64, cg = slot / 64, c2 = cg >> 2, g = cg & 3;
-        const int j0 = 2 * pr;
-        const int k0 = 32 * c2 + 16 * (j0 >> 2) + 4 * g + (j0 & 3);
-        const float v0 = W[(size_t)(r0 + k0) * ldw + c0 + n], v1 = W[(size_t)(r0 + k0 + 1) * ldw + c0 + n];
-        img[i] = __uint_as_float(split_piece_bits(v0, plane) | (split_piece_bits(v1, plane) << 16));
-    }
-}
-
 // acc[0..3] (+)= fragment x split panel image.  The fragment stays f32; the 8 values of a 32-chunk are split right before the
 // chunk's 24 MFMAs (the next chunk's while the current one multiplies); weight planes rotate through 12 registers (stage_mma_split).
 template <int D, bool ZERO>
@@ -140,27 +115,15 @@ __device__ __forceinline__ void panel_mma_global(f32x4 (&acc)[4], const Frag<D>&
     }
 }
 
-// ---- packed GRU weights: one image per stage, in stage order ---------------------------------------------------------------
-//   phase R :  (s, p)            s < NS, p < NP     Wg rows [sD, (s+1)D), columns [64p, 64p+64)
-//   phase UC:  p < NP:  for s < NX: U (Wg rows s, cols D + 64p ..), C (Wc rows s, cols 64p ..);  U (Wg rows h);  C (Wc rows h = r*h)
-__host__ __device__ constexpr int panel_gru_images(int D, int nx) { return 3 * (nx + 1) * (D / 64); }
-
+// ---- packed GRU weights: one image per stage, in stage order (panel_gru_fwd_image_src, ggnn_panel.hpp) -------------------------------
 template <int D, bool SPLIT, int FMT = kSplitBf16x3>
 __global__ void gru_panel_pack_kernel(const float* __restrict__ Wg, const float* __restrict__ Wc, int nx, float* __restrict__ out) {
     using C = PanelCfg<D>;
-    const int ns = nx + 1, NP = C::NP;
     const int i = blockIdx.y;
-    const float* W; int r0, c0, ldw;
-    if (i < ns * NP) { W = Wg; r0 = (i / NP) * D; c0 = (i % NP) * C::BN; ldw = 2 * D; }
-    else {
-        const int j = i - ns * NP, p = j / (2 * ns), q = j % (2 * ns);          // q: U x_0, C x_0, .., U h, C rh
-        const int s = q / 2;
-        if (q % 2 == 0) { W = Wg; r0 = s * D; c0 = D + p * C::BN; ldw = 2 * D; }
-        else { W = Wc; r0 = s * D; c0 = p * C::BN; ldw = D; }
-    }
+    const PanelSrc<false> src = panel_gru_fwd_image_src<D>(Wg, Wc, nx, i);
     const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-    if constexpr (SPLIT) pack_panel_gru_split_image<D, FMT>(W, r0, c0, ldw, out + (size_t)i * PanelGruSplitCfg<D, FMT>::IMG, first, stride);
-    else pack_panel_image<D>(W, r0, c0, ldw, out + (size_t)i * C::IMG, first, stride);
+    if constexpr (SPLIT) pack_panel_gru_split_image_fn<D, FMT>(src, out + (size_t)i * PanelGruSplitCfg<D, FMT>::IMG, first, stride);
+    else pack_panel_image_fn<D>(src, out + (size_t)i * C::IMG, first, stride);
 }
 
 // SPLIT: the products on the bf16 pipe in 3-way split form; an image comes through the ring in PanelGruSplitCfg::PARTS parts.
@@ -695,6 +658,8 @@ static bool transform_ring() {
     static const bool v = [] { const char* e = getenv("GGNN_PANEL_TRANSFORM"); return !e || atoi(e) != 0; }();
     return v && split_matrix_path();
 }
+// (for the training step's one-launch image preparation, ggnn_train_panel.hip, which writes the same images)
+bool transform_panel_ring() { return transform_ring(); }
 
 template <int D, bool SPLIT, int FMT = kSplitBf16x3>
 __global__ void edge_weight_panel_pack_kernel(const float* __restrict__ W, float* __restrict__ out, int ring_format) {

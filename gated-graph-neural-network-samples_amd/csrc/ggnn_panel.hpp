@@ -24,16 +24,31 @@ struct PanelCfg {
     static constexpr int IMG_BYTES = IMG * 4;
 };
 
-// image[c][kq][n][e] = W[r0 + 16c + 4kq + e][c0 + n]   (n < 64): the k-interleaved layout of ggnn_stage.hpp
-// TRANS: image value (k, n) = W[c0 + n][r0 + k] instead of W[r0 + k][c0 + n] -- a panel of a TRANSPOSED block (the GRU backward)
-template <int D, bool TRANS = false>
-__device__ __forceinline__ void pack_panel_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
-                                                 int first, int stride) {
+// image[c][kq][n][e] = value(16c + 4kq + e, n)   (n < 64): the k-interleaved layout of ggnn_stage.hpp.  value(k, n): entry (k, n) of
+// the D x 64 panel -- a functor, so that one image writer serves plain, transposed and masked-on-the-fly sources.
+template <int D, class F>
+__device__ __forceinline__ void pack_panel_image_fn(F value, float* __restrict__ img, int first, int stride) {
     using C = PanelCfg<D>;
     for (int i = first; i < C::IMG; i += stride) {
         const int e = i & 3, n = (i >> 2) % C::BN, ck = (i >> 2) / C::BN;
-        img[i] = TRANS ? W[(size_t)(c0 + n) * ldw + r0 + 4 * ck + e] : W[(size_t)(r0 + 4 * ck + e) * ldw + c0 + n];
+        img[i] = value(4 * ck + e, n);
     }
+}
+
+// the panel of a weight block: value(k, n) = W[r0 + k][c0 + n]
+// TRANS: image value (k, n) = W[c0 + n][r0 + k] instead of W[r0 + k][c0 + n] -- a panel of a TRANSPOSED block (the GRU backward)
+template <bool TRANS>
+struct PanelSrc {
+    const float* W; int r0, c0, ldw;
+    __device__ __forceinline__ float operator()(int k, int n) const {
+        return TRANS ? W[(size_t)(c0 + n) * ldw + r0 + k] : W[(size_t)(r0 + k) * ldw + c0 + n];
+    }
+};
+
+template <int D, bool TRANS = false>
+__device__ __forceinline__ void pack_panel_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
+                                                 int first, int stride) {
+    pack_panel_image_fn<D>(PanelSrc<TRANS>{W, r0, c0, ldw}, img, first, stride);
 }
 
 // ---- the GRU's panels in split form: image [c2][plane][g][n < 64][8 x bf16], CHUNK-major, so that it can be brought in in PARTS --
@@ -56,19 +71,84 @@ struct PanelGruSplitCfg {
     static_assert(NC2 % PARTS == 0 && PART_BYTES % 8192 == 0, "parts are whole chunks and whole KiB per wave of an 8-wave workgroup");
 };
 
-template <int D, int FMT = kSplitBf16x3, bool TRANS = false>
-__device__ __forceinline__ void pack_panel_gru_split_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
-                                                           int first, int stride) {
+template <int D, int FMT, class F>
+__device__ __forceinline__ void pack_panel_gru_split_image_fn(F value, float* __restrict__ img, int first, int stride) {
     using C = PanelGruSplitCfg<D, FMT>;
     for (int i = first; i < C::IMG; i += stride) {
         const int slot = i >> 2, pr = i & 3;                       // 16-byte slot ((c2*NPL + plane)*4 + g)*64 + n
         const int n = slot % 64, g = (slot / 64) % 4, plane = (slot / 256) % C::NPL, c2 = slot / (256 * C::NPL);
         const int j0 = 2 * pr;
         const int k0 = 32 * c2 + 16 * (j0 >> 2) + 4 * g + (j0 & 3);
-        const float v0 = TRANS ? W[(size_t)(c0 + n) * ldw + r0 + k0] : W[(size_t)(r0 + k0) * ldw + c0 + n];
-        const float v1 = TRANS ? W[(size_t)(c0 + n) * ldw + r0 + k0 + 1] : W[(size_t)(r0 + k0 + 1) * ldw + c0 + n];
+        const float v0 = value(k0, n), v1 = value(k0 + 1, n);
         img[i] = __uint_as_float(split_piece_bits<FMT>(v0, plane) | (split_piece_bits<FMT>(v1, plane) << 16));
     }
+}
+
+template <int D, int FMT = kSplitBf16x3, bool TRANS = false>
+__device__ __forceinline__ void pack_panel_gru_split_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
+                                                           int first, int stride) {
+    pack_panel_gru_split_image_fn<D, FMT>(PanelSrc<TRANS>{W, r0, c0, ldw}, img, first, stride);
+}
+
+// ---- the transform's panel in 3-way split form (ggnn_split.hpp): image = three bf16 planes [c2][g][n < 64][8 x bf16] -----------
+// (the stationary-image transform kernel of ggnn_panel.hip; the ring kernel takes pack_panel_gru_split_image's chunk-major format)
+template <int D>
+struct PanelSplitCfg {
+    static constexpr int NC2 = D / 32;
+    static constexpr int PLANE_BYTES = NC2 * 4 * 64 * 16;          // D * 128
+    static constexpr int IMG_BYTES = 3 * PLANE_BYTES;              // 96 KiB at D = 256: ONE image per workgroup, no ring
+    static constexpr int IMG = IMG_BYTES / 4;
+};
+
+template <int D, class F>
+__device__ __forceinline__ void pack_panel_split_image_fn(F value, float* __restrict__ img, int first, int stride) {
+    using C = PanelSplitCfg<D>;
+    constexpr int PW = C::PLANE_BYTES / 4;
+    for (int i = first; i < C::IMG; i += stride) {
+        const int plane = i / PW, w = i % PW;
+        const int slot = w >> 2, pr = w & 3;
+        const int n = slot % 64, cg = slot / 64, c2 = cg >> 2, g = cg & 3;
+        const int j0 = 2 * pr;
+        const int k0 = 32 * c2 + 16 * (j0 >> 2) + 4 * g + (j0 & 3);
+        const float v0 = value(k0, n), v1 = value(k0 + 1, n);
+        img[i] = __uint_as_float(split_piece_bits(v0, plane) | (split_piece_bits(v1, plane) << 16));
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void pack_panel_split_image(const float* __restrict__ W, int r0, int c0, int ldw, float* __restrict__ img,
+                                                       int first, int stride) {
+    pack_panel_split_image_fn<D>(PanelSrc<false>{W, r0, c0, ldw}, img, first, stride);
+}
+
+// ---- which weight panel each image of the panel GRU kernels holds (the pack kernels of ggnn_panel.hip / ggnn_gru_bwd_panel.hip and
+// the training step's one-launch image preparation read the same maps) ---------------------------------------------------------------
+__host__ __device__ constexpr int panel_gru_images(int D, int nx) { return 3 * (nx + 1) * (D / 64); }
+__host__ __device__ constexpr int panel_gru_bwd_images(int D, int nx) { return 3 * (nx + 1) * (D / 64); }
+
+// forward GRU, one image per stage, in stage order:
+//   phase R :  (s, p)            s < NS, p < NP     Wg rows [sD, (s+1)D), columns [64p, 64p+64)
+//   phase UC:  p < NP:  for s < NX: U (Wg rows s, cols D + 64p ..), C (Wc rows s, cols 64p ..);  U (Wg rows h);  C (Wc rows h = r*h)
+template <int D>
+__device__ __forceinline__ PanelSrc<false> panel_gru_fwd_image_src(const float* Wg, const float* Wc, int nx, int i) {
+    using C = PanelCfg<D>;
+    const int ns = nx + 1, NP = C::NP;
+    if (i < ns * NP) return {Wg, (i / NP) * D, (i % NP) * C::BN, 2 * D};
+    const int j = i - ns * NP, p = j / (2 * ns), q = j % (2 * ns);          // q: U x_0, C x_0, .., U h, C rh
+    const int s = q / 2;
+    if (q % 2 == 0) return {Wg, s * D, D + p * C::BN, 2 * D};
+    return {Wc, s * D, p * C::BN, D};
+}
+
+// GRU backward: image i = (block b, operand w, panel p), b = 0: the h rows, b = 1 + s: the rows of x segment s;  w = 0: Wc^T, 1: Wg_r^T,
+// 2: Wg_u^T.  image[k][n] = B(k, 64p + n) with out[:, n] = sum_k A[:, k] B(k, n):  B(k, n) = W[seg D + n][c0 + k]
+template <int D>
+__device__ __forceinline__ PanelSrc<true> panel_gru_bwd_image_src(const float* Wg, const float* Wc, int nx, int i) {
+    using C = PanelCfg<D>;
+    constexpr int NP = C::NP;
+    const int b = i / (3 * NP), w = (i / NP) % 3, p = i % NP;
+    const int seg = b == 0 ? nx : b - 1;
+    return {w == 0 ? Wc : Wg, w == 2 ? D : 0, seg * D + p * C::BN, w == 0 ? D : 2 * D};
 }
 
 template <int FMT = kSplitBf16x3>

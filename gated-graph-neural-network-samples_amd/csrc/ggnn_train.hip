@@ -19,6 +19,17 @@
 // layout, layer plan, merged products, the node sum deferred into the next GRU backward -- is shared: the drivers below take the
 // attention arguments as an optional struct and launch what they always launched without it.
 //
+// At the column-panel hidden sizes (128 / 192 / 256) the default model runs the same two sequences as
+// ggnn_sparse_train_panel_forward_f32 / ggnn_sparse_train_panel_backward_f32 -- a second ROUTE through the drivers below (TrainRoute),
+// not a copy of them.  There is no gather-fused forward GRU at these sizes, so a timestep is what the attention form already
+// launches: transform, a stand-alone segment sum (ggnn_gather_segment_sum_f32 into that timestep's `incoming`), ggnn_gru_packed_f32
+// saving r / u / c in the layer's operand format.  The backward's GRU launches are the panel kernel's (ggnn_gru_bwd_panel.hip); its
+// weight-gradient products are too wide for ggnn_xty_acc_f32 (dpg has 2D = up to 512 columns), so on the side stream they run per X
+// segment on the row-split kernel's accumulate form (ggnn_gemm_tn_acc_f32 straight into the caller's gradient views, the bias
+// gradients as column sums added to theirs; timestep by timestep unless GGNN_TRAIN_MERGE_PRODUCTS is set: merge_products below),
+// and the row-gathered edge-weight product goes through 128-column views of h and dHc whose blocks one small launch adds into the
+// [T, D, D] destination.  The images come from ggnn_sparse_train_panel_prepare_f32 (ggnn_train_panel.hip).
+//
 // Cross-stream hazards: everything a side-stream product reads (dpc, dpg, r*h, incoming, states, dHc) has its own buffer per
 // timestep, so the main stream never waits for the side stream inside a step; the call ends with the main stream waiting for the
 // side stream's last product, which orders the next step's forward (it reuses the workspace) behind them.
@@ -32,18 +43,33 @@ namespace {
 constexpr int kMaxLayers = 62;
 constexpr int kMaxNx = 3;
 
+constexpr int kEdgeBlock = 128;        // columns of each operand the row-gathered ggnn_xty_acc_f32 takes
+
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+// Which kernels the two sequences run on.  panel == false: the whole-block sizes (32 / 64 / 100), the launches they always made.
+// panel == true: the column-panel sizes (128 / 192 / 256), see the header comment.
+struct TrainRoute {
+    bool panel;
+    bool takes(int D) const {
+        return panel ? (D == 128 || D == 192 || D == 256) && ggnn_gru_is_fused(D) == 2 && ggnn_gru_bwd_is_fused(D) && ggnn_msg_transform_compact_supported(D)
+                     : ggnn_gru_is_fused(D) == 1 && ggnn_gru_bwd_is_fused(D) && ggnn_msg_transform_compact_supported(D);
+    }
+};
 
 struct TrainLayout {
     size_t Hc, state, r, u, c, inc, counters;           // forward
     size_t dpc, rh, dh, dpg, dx, dHc, Z, xty;            // backward
     size_t coef, md;                                     // attention: coef_a | coef_s | dfac, md bytes each (one set: main stream only)
+    size_t tn, eblk, colsum, bsum;                       // panel route, side stream only: gemm_tn partials, edge-gradient blocks, column sums
+    size_t tn_bytes, colsum_bytes, xty_bytes;
     size_t vd, rd, total;
     int steps;
 };
 
-// M > 0: the layout of the attention sequences (M messages); M == 0: the default model's, unchanged
-TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 0) {
+// M > 0: the layout of the attention sequences (M messages); M == 0: the default model's, unchanged; panel: the default model's at the
+// column-panel sizes (everything the side stream's products need beyond the per-timestep buffers follows them)
+TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 0, bool panel = false) {
     TrainLayout L{};
     L.steps = steps;
     // per-timestep buffers follow each other WITHOUT padding (V*D*4 is a multiple of 16): the buffers of consecutive timesteps then
@@ -62,7 +88,19 @@ TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 
     L.dHc = take(L.rd * steps); L.Z = take(L.rd);
     L.md = al256((size_t)M * sizeof(float));
     if (M > 0) L.coef = take(3 * L.md);
-    L.xty = take(ggnn_xty_workspace_bytes((V > R ? V : (int)R) * (steps > 1 ? steps : 1), 4 * D, 2 * D, T));
+    if (panel) {
+        // one set each: the side stream runs its products in order.  The widest row-split product is [S*V, D]^T [S*V, 2D]
+        L.tn_bytes = ggnn_gemm_tn_workspace_bytes(V * (steps > 1 ? steps : 1), D, 2 * D);
+        L.tn = take(L.tn_bytes);
+        L.eblk = take((size_t)T * D * D * sizeof(float));
+        L.colsum_bytes = ggnn_colsum_workspace_bytes(2 * D);
+        L.colsum = take(L.colsum_bytes);
+        L.bsum = take((size_t)2 * D * sizeof(float));
+        L.xty_bytes = ggnn_xty_workspace_bytes(V > R ? V : (int)R, kEdgeBlock, kEdgeBlock, T);
+    } else {
+        L.xty_bytes = ggnn_xty_workspace_bytes((V > R ? V : (int)R) * (steps > 1 ? steps : 1), 4 * D, 2 * D, T);
+    }
+    L.xty = take(L.xty_bytes);
     L.total = p + 256;
     (void)T;
     return L;
@@ -116,6 +154,19 @@ int add_inplace(float* dst, const float* src, long long n, hipStream_t st) {
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, dst, src, n4);
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
+}
+
+// dst[t][k][n] += blocks of the panel route's edge-weight gradient: block (bk, bn) holds [T][kw][nw] (kw = min(128, D - 128 bk), nw
+// likewise) and the blocks follow each other in (bk, bn) order -- what ggnn_xty_acc_f32 wrote for the 128-column views of h and dHc
+__global__ void add_edge_blocks_kernel(float* __restrict__ dst, const float* __restrict__ blk, int T, int D) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * D * D) return;
+    const int n = i % D, k = (i / D) % D, t = i / (D * D);
+    const int bk = k / kEdgeBlock, bn = n / kEdgeBlock;
+    const int kw = min(kEdgeBlock, D - bk * kEdgeBlock), nw = min(kEdgeBlock, D - bn * kEdgeBlock);
+    // floats in front of block (bk, bn): whole block rows (T * 128 * D each), then the blocks to its left in its row (T * kw * 128 each)
+    const size_t off = (size_t)T * kEdgeBlock * D * bk + (size_t)T * kw * kEdgeBlock * bn;
+    dst[i] += blk[off + ((size_t)t * kw + (k - bk * kEdgeBlock)) * nw + (n - bn * kEdgeBlock)];
 }
 
 // ---- a step's weight images in ONE launch ------------------------------------------------------------------------------------------
@@ -189,10 +240,15 @@ __global__ __launch_bounds__(256) void train_prepare_kernel(PrepArgs a) {
     }
 }
 
-// GGNN_TRAIN_MERGE_PRODUCTS=0: the GRU weight-gradient products timestep by timestep also for layers without residual inputs
-bool merge_products() {
-    static const bool v = [] { const char* e = getenv("GGNN_TRAIN_MERGE_PRODUCTS"); return !e || atoi(e) != 0; }();
-    return v;
+// GGNN_TRAIN_MERGE_PRODUCTS=0: the GRU weight-gradient products timestep by timestep also for layers without residual inputs.
+// The panel route merges only when the variable is SET (and not 0): timestep by timestep its row-split products are the autograd
+// step's own, in the same order -- the gradients of the two steps then differ by the order of the layer-input sums only -- while
+// one product over S*V rows splits the rows differently.  Measured at h = 192, two merged timesteps: gradients 2.7e-7 of the
+// largest entry apart, which Adam's first steps (d update / d g <= lr / (eps / sqrt(1 - beta2)) = 3162) turn into weights 2.2e-5
+// apart after three steps, beyond the 2e-5 the step is held to against the autograd step.
+bool merge_products(bool panel) {
+    static const int v = [] { const char* e = getenv("GGNN_TRAIN_MERGE_PRODUCTS"); return !e ? -1 : (atoi(e) != 0 ? 1 : 0); }();
+    return panel ? v == 1 : v != 0;
 }
 
 // what the attention form of the two sequences needs beyond the default model's arguments
@@ -294,12 +350,16 @@ static int train_forward(
         const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
         const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* bg,
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
-        int64_t* final_state_offset, const AttnForward* at, ggnn_stream_t stream) {
+        int64_t* final_state_offset, const AttnForward* at, const TrainRoute& route, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(h0 && row_ptr && gather_row_c && pair_node && type_row_off && ws && final_state_offset, "null pointer");
     GGNN_CHECK_ARG(edge_packed && bg && bc && gru_packed, "weights missing");
     GGNN_CHECK_ARG((reinterpret_cast<size_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-    if (ggnn_gru_is_fused(D) != 1 || !ggnn_msg_transform_compact_supported(D))
+    if (route.panel) {
+        if (!route.takes(D)) return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: hidden size %d is not 128 / 192 / 256", D);
+        GGNN_CHECK_ARG(!at, "the panel route has no attention form");
+        GGNN_CHECK_ARG(!use_avg || nin, "nin is required for mean aggregation");
+    } else if (ggnn_gru_is_fused(D) != 1 || !ggnn_msg_transform_compact_supported(D))
         return fail(GGNN_E_UNSUPPORTED, "native training step: hidden size %d has no gather-fused GRU / compacted transform", D);
     LayerPlan plan[kMaxLayers];
     int steps = 0;
@@ -307,7 +367,12 @@ static int train_forward(
     const int64_t R = type_row_off[T];
     GGNN_CHECK_ARG(R > 0, "no messages in the batch");
     GGNN_CHECK_ARG(!at || (at->slot_pair && at->factors && at->M > 0 && at->M < (1LL << 31) && (!use_avg || nin)), "attention arguments missing");
-    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0);
+    if (route.panel) {            // (the limits of the launches below, checked before anything is enqueued)
+        GGNN_CHECK_ARG(T <= 64 && R < (1LL << 31), "bad sizes T=%d, %lld compact rows", T, (long long)R);
+        if ((unsigned long long)V * 2 * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30) || (long long)V * steps >= (1LL << 31))
+            return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: V*2D and rows*D must be < 2^30 (V=%d, D=%d, rows=%lld)", V, D, (long long)R);
+    }
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
     char* base = static_cast<char*>(ws);
     float* Hc = reinterpret_cast<float*>(base + L.Hc);
@@ -341,6 +406,14 @@ static int train_forward(
                 xs[nx - 1] = buf(L.inc, k);
                 if (int rc = ggnn_gru_packed_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, buf(L.r, k), buf(L.u, k), buf(L.c, k), V, D,
                                                  act, GGNN_GRU_FMT_BF16X3, counters + k, stream)) return rc;
+            } else if (route.panel) {
+                // :160-168, 206-209 the stand-alone segment sum (with the mean epilogue) into this timestep's `incoming`, then the panel
+                // GRU on it in the layer's operand format
+                if (int rc = ggnn_gather_segment_sum_f32(Hc, row_ptr, gather_row_c, use_avg ? nin : nullptr, nullptr, use_avg ? 1 : 0,
+                                                         buf(L.inc, k), V, D, T, stream)) return rc;
+                xs[nx - 1] = buf(L.inc, k);
+                if (int rc = ggnn_gru_packed_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, buf(L.r, k), buf(L.u, k), buf(L.c, k), V, D,
+                                                 act, gru_fmt ? gru_fmt[l] : GGNN_GRU_FMT_BF16X3, nullptr, stream)) return rc;
             } else if (int rc = ggnn_gru_packed_gather_train_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, Hc, row_ptr, gather_row_c,
                                                           use_avg ? nin : nullptr, T, use_avg ? 1 : 0, buf(L.r, k), buf(L.u, k),
                                                           buf(L.c, k), buf(L.inc, k), V, D, act,
@@ -360,8 +433,8 @@ static int train_backward(
         const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
         const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
         float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc, float* const* g_bc,
-        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, const AttnBackward* at, ggnn_stream_t stream,
-        ggnn_stream_t side_stream) {
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, const AttnBackward* at, const TrainRoute& route,
+        ggnn_stream_t stream, ggnn_stream_t side_stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0 && T <= 64, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(h0 && pair_node && type_row_off && (at || (rows_rp && rows_gather)) && node_rp && node_order && identity_rows && d_final && ws,
                    "null pointer");
@@ -371,21 +444,28 @@ static int train_backward(
     GGNN_CHECK_ARG(edge_packed_t && gru_bwd_packed && g_edge && g_Wg && g_bg && g_Wc && g_bc && d_state_ws, "weights / gradient buffers missing");
     GGNN_CHECK_ARG(!use_avg || nin, "nin is required for mean aggregation");
     GGNN_CHECK_ARG((reinterpret_cast<size_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-    if (!ggnn_gru_bwd_is_fused(D)) return fail(GGNN_E_UNSUPPORTED, "native training step: no fused GRU backward for hidden size %d", D);
+    if (!route.takes(D))
+        return fail(GGNN_E_UNSUPPORTED, route.panel ? "native training step, panel route: hidden size %d is not 128 / 192 / 256"
+                                                    : "native training step: no whole-block fused GRU backward for hidden size %d", D);
+    GGNN_CHECK_ARG(!route.panel || !at, "the panel route has no attention form");
     LayerPlan plan[kMaxLayers];
     int steps = 0;
     if (int rc = plan_layers(num_layers, layer_timesteps, res_ptr, res_idx, plan, &steps)) return rc;
     const int64_t R64 = type_row_off[T];
     GGNN_CHECK_ARG(R64 > 0 && R64 < (1LL << 31), "bad compact row count");
     const int R = (int)R64;
-    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0);
+    if (route.panel) {            // (the limits of the launches below, checked before anything is enqueued)
+        if ((unsigned long long)V * 2 * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30) || (long long)V * steps >= (1LL << 31))
+            return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: V*2D and rows*D must be < 2^30 (V=%d, D=%d, rows=%d)", V, D, R);
+    }
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
     char* base = static_cast<char*>(ws);
     hipStream_t st = (hipStream_t)stream, side = side_stream ? (hipStream_t)side_stream : (hipStream_t)stream;
     auto buf = [&](size_t off, int step) { return reinterpret_cast<float*>(base + off + (size_t)step * L.vd); };
     float* Z = reinterpret_cast<float*>(base + L.Z);
     void* xty_ws = base + L.xty;
-    const size_t xty_ws_bytes = L.total - 256 - L.xty;
+    const size_t xty_ws_bytes = L.xty_bytes;
     const size_t edge_img_bytes = ggnn_msg_transform_compact_workspace_bytes(D, T);
     const long long nvd = (long long)V * D;
     int32_t row_off_v[2] = {0, V};
@@ -457,8 +537,33 @@ static int train_backward(
             // A layer WITHOUT residual inputs runs them once for all its timesteps: incoming, r*h, dpc, dpg and the input states of
             // consecutive timesteps are consecutive [V,D] ([V,2D]) buffers, i.e. one matrix of S*V rows each -- one product
             // instead of S, and its fixed part (prologue, partial store, reduction launch: ~20 us of ~100) paid once.
-            const bool merged = P.nres == 0 && P.steps > 1 && merge_products();
-            if (merged) {
+            const bool merged = P.nres == 0 && P.steps > 1 && merge_products(route.panel);
+            if (route.panel) {
+                // per X segment on the row-split kernel's accumulate form, straight into the segment's rows of the gradient views;
+                // the bias gradients as column sums added to theirs
+                if (!merged || s == 0) {
+                    if (int rc = order_after(side, st)) return rc;
+                    const int k0 = merged ? P.first_step : k;
+                    const int rows = merged ? V * P.steps : V;
+                    const float* X[kMaxNx + 1];
+                    for (int i = 0; i < P.nres; ++i) X[i] = states[P.res[i]];          // (merged: none)
+                    X[nx - 1] = buf(L.inc, k0);
+                    const float* dpc0 = buf(L.dpc, k0);
+                    const float* dpg0 = reinterpret_cast<const float*>(base + L.dpg + (size_t)k0 * 2 * L.vd);
+                    void* tn_ws = base + L.tn;
+                    float* bsum = reinterpret_cast<float*>(base + L.bsum);
+                    X[nx] = buf(L.rh, k0);
+                    for (int i = 0; i <= nx; ++i)
+                        if (int rc = ggnn_gemm_tn_acc_f32(X[i], D, dpc0, D, g_Wc[l] + (size_t)i * D * D, D, 1, rows, D, D, tn_ws, L.tn_bytes, side)) return rc;
+                    if (int rc = ggnn_colsum_f32(dpc0, D, rows, D, bsum, base + L.colsum, L.colsum_bytes, side)) return rc;
+                    if (int rc = add_inplace(g_bc[l], bsum, D, side)) return rc;
+                    X[nx] = buf(L.state, k0);
+                    for (int i = 0; i <= nx; ++i)
+                        if (int rc = ggnn_gemm_tn_acc_f32(X[i], D, dpg0, 2 * D, g_Wg[l] + (size_t)i * D * 2 * D, 2 * D, 1, rows, D, 2 * D, tn_ws, L.tn_bytes, side)) return rc;
+                    if (int rc = ggnn_colsum_f32(dpg0, 2 * D, rows, 2 * D, bsum, base + L.colsum, L.colsum_bytes, side)) return rc;
+                    if (int rc = add_inplace(g_bg[l], bsum, 2 * D, side)) return rc;
+                }
+            } else if (merged) {
                 if (s == 0) {                               // (the layer's first timestep is the last one processed)
                     if (int rc = order_after(side, st)) return rc;
                     const int k0 = P.first_step;
@@ -521,10 +626,29 @@ static int train_backward(
             }
             // ---- edge-weight gradients, side stream (needs dHc: ordered behind the transform launch above, which also read it)
             if (int rc = order_after(side, st)) return rc;
-            {
+            if (D <= kEdgeBlock) {
                 const float* X[1] = {h_in}; int32_t ldx[1] = {D};
                 if (int rc = ggnn_xty_acc_f32(X, 1, D, ldx, pair_node, dHc, D, g_edge[l], nullptr, 1, D, D, 0, row_off_t, T, xty_ws, xty_ws_bytes,
                                               side)) return rc;
+            } else {
+                // (panel route, D = 192 / 256) the row-gathered kernel takes <= 128 columns of each operand: 128-column views of h
+                // (pointer offset, ldx = D) and of dHc, the blocks into the workspace, one launch adds them into [T, D, D]
+                float* blk = reinterpret_cast<float*>(base + L.eblk);
+                float* out = blk;
+                int32_t ldx[1] = {D};
+                for (int kb = 0; kb < D; kb += kEdgeBlock) {
+                    const int kw = D - kb < kEdgeBlock ? D - kb : kEdgeBlock;
+                    for (int nb = 0; nb < D; nb += kEdgeBlock) {
+                        const int nw = D - nb < kEdgeBlock ? D - nb : kEdgeBlock;
+                        const float* X[1] = {h_in + kb};
+                        if (int rc = ggnn_xty_acc_f32(X, 1, kw, ldx, pair_node, dHc + nb, D, out, nullptr, 0, kw, nw, 0, row_off_t, T, xty_ws,
+                                                      xty_ws_bytes, side)) return rc;
+                        out += (size_t)T * kw * nw;
+                    }
+                }
+                const int n = T * D * D;
+                hipLaunchKernelGGL(add_edge_blocks_kernel, dim3((n + 255) / 256), dim3(256), 0, side, g_edge[l], (const float*)blk, T, D);
+                GGNN_CHECK_HIP(hipGetLastError());
             }
             // ---- accumulate what went to temporaries
             for (int i = 0; i < P.nres; ++i) {          // (sums into the gradient of h0 are not needed either)
@@ -547,7 +671,8 @@ extern "C" int ggnn_sparse_train_forward_f32(
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
         int64_t* final_state_offset, ggnn_stream_t stream) {
     return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
-                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, stream);
+                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, TrainRoute{false},
+                         stream);
 }
 
 extern "C" int ggnn_sparse_train_backward_f32(
@@ -560,7 +685,38 @@ extern "C" int ggnn_sparse_train_backward_f32(
         float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
     return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
                           rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act,
-                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, stream, side_stream);
+                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, TrainRoute{false}, stream, side_stream);
+}
+
+// ---- the default model's two sequences at the column-panel sizes 128 / 192 / 256 (see the header comment) ---------------------------
+extern "C" size_t ggnn_sparse_train_panel_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps) {
+    if (V <= 0 || T <= 0 || T > 64 || total_steps <= 0 || compact_rows < 0 || compact_rows >= (1LL << 31) || !TrainRoute{true}.takes(D)) return 0;
+    if ((long long)V * total_steps >= (1LL << 31)) return 0;
+    return train_layout(V, D, T, compact_rows, total_steps, 0, true).total;
+}
+
+extern "C" int ggnn_sparse_train_panel_forward_f32(
+        const float* h0, int V, int D, int T, const int32_t* row_ptr, const int32_t* gather_row_c, const int32_t* pair_node,
+        const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+        const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* bg,
+        const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
+        int64_t* final_state_offset, ggnn_stream_t stream) {
+    return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, TrainRoute{true},
+                         stream);
+}
+
+extern "C" int ggnn_sparse_train_panel_backward_f32(
+        const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const int32_t* rows_rp, const int32_t* rows_gather, const int32_t* rows_heads,
+        const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+        const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
+        float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc, float* const* g_bc,
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
+                          rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act,
+                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, TrainRoute{true}, stream, side_stream);
 }
 
 // ---- the same two sequences with propagation attention on the compacted route (see the header comment) -----------------------------
@@ -574,7 +730,7 @@ extern "C" int ggnn_sparse_attn_train_forward_f32(
     GGNN_CHECK_ARG(M > 0 && M < (1LL << 31), "bad message count %lld", (long long)M);
     const AttnForward at{slot_pair, attn_factors, M};
     return train_forward(h0, V, D, T, row_ptr, slot_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
-                         res_idx, edge_packed, bg, bc, gru_packed, nullptr, act, ws, ws_bytes, final_state_offset, &at, stream);
+                         res_idx, edge_packed, bg, bc, gru_packed, nullptr, act, ws, ws_bytes, final_state_offset, &at, TrainRoute{false}, stream);
 }
 
 extern "C" int ggnn_sparse_attn_train_backward_f32(
@@ -596,5 +752,5 @@ extern "C" int ggnn_sparse_attn_train_backward_f32(
                           edge_packed, attn_factors, g_attn, M};
     return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, nullptr,
                           nullptr, nullptr, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act, g_edge,
-                          g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, &at, stream, side_stream);
+                          g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, &at, TrainRoute{false}, stream, side_stream);
 }

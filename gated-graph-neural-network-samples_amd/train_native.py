@@ -22,6 +22,11 @@ The sparse model with propagation attention on the compacted route (chem_tensorf
 SparseGGNNChemModel.attention_route) has it on ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32 when its
 config says compact_attention = 'native' (True keeps variants.CompactAttentionStepFn): attn_eligible / native_attn_train_step, the
 default model's step below with the attention arguments added.
+
+The default sparse model at the column-panel hidden sizes 128 / 192 / 256 has it on ggnn_sparse_train_panel_forward_f32 /
+ggnn_sparse_train_panel_backward_f32 (the same driver on its panel route, csrc/ggnn_train.hip) when its config says
+native_panel_training = True: panel_eligible / native_panel_train_step, again the default model's step below with a route argument.
+Without the key these sizes keep the autograd step (backward.PropagationStepFn on the panel kernels).
 """
 from __future__ import annotations
 
@@ -36,6 +41,9 @@ from .utils import SMALL_NUMBER
 
 
 import os
+
+# the hidden sizes of the column-panel kernels (the native step's panel route: params['native_panel_training'])
+PANEL_SIZES = (128, 192, 256)
 
 # all of a step's weight images in one launch (GGNN_FUSED_PREPARE=0: mask / transpose / pack layer by layer through the caches of ops.py)
 USE_FUSED_PREPARE = os.environ.get("GGNN_FUSED_PREPARE", "1") != "0"
@@ -156,11 +164,21 @@ def attn_model_eligible(model) -> bool:
     return _sparse_model_eligible(model, True)
 
 
-def _sparse_model_eligible(model, attention: bool) -> bool:
+def panel_model_eligible(model) -> bool:
+    """The part of `panel_eligible` that depends on the model only: a sparse model whose config asks for the native step at the
+    column-panel sizes with params['native_panel_training'] (read with .get: not a key of default_params, whose keys a reference
+    checkpoint must match) and whose hidden size is 128 / 192 / 256 unpadded (116, which pads to 128, keeps autograd), under the
+    default model's conditions otherwise -- GRU cell, no attention, no edge bias, no graph-state dropout, at most two residual inputs
+    per layer, the fused optimizer over exactly the trainable variables, nothing frozen, one-layer readout MLPs -- and no active
+    data-parallel context."""
+    return _sparse_model_eligible(model, False, panel=True)
+
+
+def _sparse_model_eligible(model, attention: bool, panel: bool = False) -> bool:
     p = getattr(model, "params", None)
     if p is None or not hasattr(model, "_edge_weight_vars") or not torch.cuda.is_available():
         return False
-    if not backward.USE_NATIVE_STEP or not backward.USE_COMPACT_TRANSFORM or not backward.TRAIN_GATHER_IN_GRU:
+    if not backward.USE_NATIVE_STEP or not backward.USE_COMPACT_TRANSFORM or not (panel or backward.TRAIN_GATHER_IN_GRU):
         return False
     D = p['hidden_size']
     if getattr(model, "cell_type", None) != 'gru' or bool(p['use_propagation_attention']) != attention or p['use_edge_bias'] \
@@ -170,9 +188,17 @@ def _sparse_model_eligible(model, attention: bool) -> bool:
         dist = getattr(model, "dist", None)
         if p.get('compact_attention') != 'native' or not model.attention_route() or (dist is not None and dist.active):
             return False
+    if panel:
+        dist = getattr(model, "dist", None)
+        if not p.get('native_panel_training') or (dist is not None and dist.active):
+            return False
     if torch.device(model.device).type != 'cuda':
         return False
-    if model._kw != D or not ops.gru_gather_fused(D) or not ops.compact_supported(D) or D > 104 or not ops.gru_bwd_is_fused(D):
+    if panel:
+        if model._kw != D or D not in PANEL_SIZES or not _lib.load().ggnn_sparse_train_panel_supported(D) \
+                or not ops.compact_supported(D) or not ops.gru_bwd_is_fused(D):
+            return False
+    elif model._kw != D or not ops.gru_gather_fused(D) or not ops.compact_supported(D) or D > 104 or not ops.gru_bwd_is_fused(D):
         return False
     if float(p.get('graph_state_dropout_keep_prob', 1.0)) < 1.0:
         return False
@@ -205,8 +231,14 @@ def attn_eligible(model, batch_data: Dict[str, Any]) -> bool:
     return _sparse_eligible(model, batch_data, True)
 
 
-def _sparse_eligible(model, batch_data: Dict[str, Any], attention: bool) -> bool:
-    if ops._timing is not None or not _sparse_model_eligible(model, attention):
+def panel_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """True when this step of the default model at hidden size 128 / 192 / 256 can run on the native sequences' panel route:
+    panel_model_eligible, no per-launch timing, and a batch on the GPU, sorted by graph, with at least one message."""
+    return _sparse_eligible(model, batch_data, False, panel=True)
+
+
+def _sparse_eligible(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False) -> bool:
+    if ops._timing is not None or not _sparse_model_eligible(model, attention, panel):
         return False
     D = model.params['hidden_size']
     if float(batch_data.get('graph_state_keep_prob', 1.0)) < 1.0:
@@ -246,9 +278,23 @@ def native_attn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
     return _native_sparse_step(model, batch_data, True)
 
 
-def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> torch.Tensor:
+def native_panel_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    """native_train_step at the column-panel hidden sizes 128 / 192 / 256: the same two C calls on the driver's panel route
+    (ggnn_sparse_train_panel_forward_f32 / ggnn_sparse_train_panel_backward_f32), the images of the step from
+    ggnn_sparse_train_panel_prepare_f32, the same readout, loss, clip and Adam."""
+    return _native_sparse_step(model, batch_data, False, panel=True)
+
+
+def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False) -> torch.Tensor:
     from .autograd import _PACKED
     lib = _lib.load()
+    # the entry points of the route: whole-block sizes (32 / 64 / 100) or column panels (128 / 192 / 256), one argument list
+    if panel:
+        prepare, workspace_bytes = lib.ggnn_sparse_train_panel_prepare_f32, lib.ggnn_sparse_train_panel_workspace_bytes
+        train_forward, train_backward = lib.ggnn_sparse_train_panel_forward_f32, lib.ggnn_sparse_train_panel_backward_f32
+    else:
+        prepare, workspace_bytes = lib.ggnn_sparse_train_prepare_f32, lib.ggnn_sparse_train_workspace_bytes
+        train_forward, train_backward = lib.ggnn_sparse_train_forward_f32, lib.ggnn_sparse_train_backward_f32
     p = model.params
     opt = model.optimizer
     model.feed(batch_data)
@@ -303,7 +349,7 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> t
                     [f32(lib.ggnn_gru_bwd_packed_bytes(D, nxs[l])) for l in range(L)])
             edge_packed, edge_packed_t, gru_packed, gru_bwd_packed = imgs
             seeds = (ctypes.c_uint64 * L)(*[m[1] for m in masks]) if masks else None
-            check(lib.ggnn_sparse_train_prepare_f32(
+            check(prepare(
                 L, T, D, _i32(nxs), _ptrs(model._edge_weight_vars), ew_keep if masks else 1.0, seeds,
                 _ptrs([c.gates_kernel for c in cells]), _ptrs([c.candidate_kernel for c in cells]), fm, _ptrs(edge_packed),
                 _ptrs(edge_packed_t), _ptrs(gru_packed), _ptrs(gru_bwd_packed), st.cuda_stream))
@@ -324,7 +370,9 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> t
             ws_bytes = lib.ggnn_sparse_attn_train_workspace_bytes(V, D, T, R, steps, M)
             factors = _ptrs(model.gnn_weights.edge_type_attention_weights)
         else:
-            ws_bytes = lib.ggnn_sparse_train_workspace_bytes(V, D, T, R, steps)
+            ws_bytes = workspace_bytes(V, D, T, R, steps)
+            if not ws_bytes:
+                raise ValueError("native training step: no workspace for V=%d D=%d T=%d rows=%d steps=%d" % (V, D, T, R, steps))
         ws, dstate = model._native_ws.get(ws_bytes, L, V, D, dev)
         tro = (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
         lt, rp, ri = _i32(p['layer_timesteps']), _i32(res_ptr), _i32(res_idx)
@@ -336,7 +384,7 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> t
                 comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), factors, bg, bc,
                 _ptrs(gru_packed), act, ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
         else:
-            check(lib.ggnn_sparse_train_forward_f32(
+            check(train_forward(
                 h0.data_ptr(), V, D, T, index.row_ptr.data_ptr(), comp.gather_row.data_ptr(), comp.pair_node.data_ptr(), tro,
                 nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), bg, bc, _ptrs(gru_packed), fm, act,
                 ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
@@ -381,7 +429,7 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool) -> t
                 _ptrs([gv(a) for a in model.gnn_weights.edge_type_attention_weights]), *g_cells, d_final.data_ptr(), _ptrs(dstate),
                 ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
         else:
-            check(lib.ggnn_sparse_train_backward_f32(
+            check(train_backward(
                 h0.data_ptr(), V, D, T, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
                 bwd.rows_index.row_ptr.data_ptr(), bwd.rows_index.gather_row.data_ptr(),
                 ops._ptr(ops.slot_heads(bwd.rows_index, bwd.rows_index.row_ptr, bwd.rows_index.gather_row, R)),

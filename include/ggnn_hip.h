@@ -581,6 +581,13 @@ int ggnn_gemm_f32(const float* const* a_segs, int nseg, int D, int lda, const fl
 size_t ggnn_gemm_tn_workspace_bytes(int M, int K, int N);
 int ggnn_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, float* C, int M, int K, int N, void* ws,
                      size_t ws_bytes, ggnn_stream_t stream);
+/* The same product written the way a training step consumes it: C has row stride ldc >= N (a row block of a wider matrix, e.g. one
+ * X segment's rows of a GRU weight gradient), and with accumulate != 0 the product is ADDED to C's contents.  The first pass is
+ * ggnn_gemm_tn_f32's; the partials are added in their fixed order and that sum is added to C once (deterministic).  M == 0: C is
+ * zeroed (accumulate == 0) or left untouched.  Same argument checks and workspace; ggnn_gemm_tn_f32 is this call with ldc = N,
+ * accumulate = 0. */
+int ggnn_gemm_tn_acc_f32(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int accumulate, int M, int K, int N,
+                         void* ws, size_t ws_bytes, ggnn_stream_t stream);
 
 /* ---- (a-B) backward GEMMs of one propagation timestep, hand-written (ggnn_bwd_gemm.hip) ---------------------------------------
  * What TF autodiff derives from chem_tensorflow_sparse.py:160-164, 211-216 through compute_gradients (chem_tensorflow.py:184).
@@ -805,6 +812,48 @@ int ggnn_sparse_train_backward_f32(const float* h0, int V, int D, int T, const i
                                    const float* const* gru_bwd_packed, int act, float* const* g_edge, float* const* g_Wg,
                                    float* const* g_bg, float* const* g_Wc, float* const* g_bc, float* d_final, float* const* d_state_ws,
                                    void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
+
+/* The same step of the default model at the column-panel hidden sizes 128 / 192 / 256 (ggnn_sparse_train_panel_supported: 1 for
+ * these three, else 0; the pair above keeps refusing them with GGNN_E_UNSUPPORTED, and this one refuses every other size): the
+ * conditions, argument lists and conventions of the pair above, one driver with a second route (ggnn_train.hip).
+ *   forward:  per timestep ggnn_msg_transform_compact_f32 on the layer's ring images, ggnn_gather_segment_sum_f32 over (row_ptr,
+ *     gather_row_c) into that timestep's `incoming` (mean epilogue with use_avg; no edge bias), ggnn_gru_packed_f32 on the panel
+ *     images saving r / u / c, in gru_fmt[l].
+ *   backward: per timestep, last to first: the panel GRU backward (ggnn_gru_bwd_fused_f32, or ggnn_gru_bwd_fused_gather_f32 when the
+ *     previous timestep's node sum is pending: T <= 4 and node_heads given), then the transpose segment sum, the transform on the W^T
+ *     images and the node sum as above.  On `side_stream`, ADDED into the caller's gradient views: per X segment
+ *     ggnn_gemm_tn_acc_f32 for dWc = [x.. | incoming | r*h]^T dpc and dWg = [x.. | incoming | h]^T dpg (timestep by timestep, in the autograd
+ *     step's order of summation; with GGNN_TRAIN_MERGE_PRODUCTS=1 the timesteps of a layer without residual inputs as one product
+ *     over S*V rows), ggnn_colsum_f32 of dpc / dpg added to g_bc / g_bg, and the
+ *     row-gathered ggnn_xty_acc_f32 for the edge weights -- D = 128 straight into g_edge[l], D = 192 / 256 through 128-column views
+ *     of h and dHc whose blocks one launch adds into [T, D, D].
+ *   `ws`: ggnn_sparse_train_panel_workspace_bytes (0 on bad arguments or another hidden size), the SAME buffer for both calls; the
+ *     calls allocate nothing and synchronise nothing.  V * 2D, compact_rows * D < 2^30 and V * total_steps < 2^31, checked before
+ *     anything is enqueued (GGNN_E_UNSUPPORTED).
+ *   prepare: per layer the T ring images of the edge weights and of their transposes (masked on the fly as above), the panel GRU's
+ *     images in gru_fmt[l] and its backward's -- each bit for bit what ggnn_edge_weights_pack_f32 (on the masked weights / their
+ *     transposes), ggnn_gru_pack_weights_f32 and ggnn_gru_bwd_fused_f32(g = NULL) write, with the buffer sizes of those calls. */
+int ggnn_sparse_train_panel_supported(int D);
+int ggnn_sparse_train_panel_prepare_f32(int num_layers, int T, int D, const int32_t* nx, const float* const* edge_w, float keep_prob,
+                                        const uint64_t* seeds, const float* const* Wg, const float* const* Wc, const int32_t* gru_fmt,
+                                        float* const* edge_packed, float* const* edge_packed_t, float* const* gru_packed,
+                                        float* const* gru_bwd_packed, ggnn_stream_t stream);
+size_t ggnn_sparse_train_panel_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps);
+int ggnn_sparse_train_panel_forward_f32(const float* h0, int V, int D, int T, const int32_t* row_ptr, const int32_t* gather_row_c,
+                                        const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg,
+                                        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+                                        const float* const* edge_packed, const float* const* bg, const float* const* bc,
+                                        const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
+                                        int64_t* final_state_offset, ggnn_stream_t stream);
+int ggnn_sparse_train_panel_backward_f32(const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off,
+                                         const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+                                         const int32_t* res_ptr, const int32_t* res_idx, const int32_t* rows_rp,
+                                         const int32_t* rows_gather, const int32_t* rows_heads, const int32_t* node_rp,
+                                         const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+                                         const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
+                                         float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc,
+                                         float* const* g_bc, float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes,
+                                         ggnn_stream_t stream, ggnn_stream_t side_stream);
 
 /* The same step with propagation attention (chem_tensorflow_sparse.py:147-149, 170-196) on the compacted route: the conditions and
  * conventions of the pair above (GRU cell, no edge bias, hidden size 32 / 64 / 100, images from ggnn_sparse_train_prepare_f32 with
