@@ -98,6 +98,19 @@ SYMBOLS = {
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_int32), POINTER(c_int32), c_int, c_int, POINTER(c_void_p), c_void_p,
                                                c_size_t, c_void_p, POINTER(c_void_p), c_void_p]),
+    # BasicRNNCell with the segment sum gathered inside (ggnn_rnn_fused.hip) and the RNN form of the one-call driver
+    "ggnn_rnn_fused_supported": (c_int, [c_int, c_int]),
+    "ggnn_rnn_packed_bytes": (c_size_t, [c_int, c_int]),
+    "ggnn_rnn_pack_weights_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_rnn_fused_launch_geometry": (None, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "ggnn_rnn_packed_gather_f32": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                           c_void_p]),
+    "ggnn_sparse_propagate_rnn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64),
+                                              c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                              POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                              POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int,
+                                              POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "ggnn_gru_bwd_stage1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ggnn_gru_bwd_stage2_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -9,6 +9,11 @@
 // inside: ggnn_gru_packed_gather_f32).  With propagation attention (:147-149, 170-196; ggnn_sparse_propagate_attn_f32) the
 // segment sum is ggnn_gather_segment_sum_attn_compact_f32 over the compacted rows: always 3 kernels.  Both entry points run the
 // one driver below; without attention it launches what it always launched.
+//
+// The cell is a parameter of the driver: with an RnnCell (ggnn_sparse_propagate_rnn_f32; graph_rnn_cell = RNN, the R-GCN
+// configuration) the node update is the BasicRNNCell -- ggnn_rnn_packed_gather_f32 (2 kernels per timestep) for a layer with packed
+// images, a supported (D, nx) and no edge bias, ggnn_gather_segment_sum_f32 + ggnn_rnn_f32 (3 kernels) otherwise -- always behind
+// the compacted transform.  Without one the GRU entry points launch exactly what they launched before.
 #include "ggnn_common.h"
 #include <cstring>
 
@@ -30,8 +35,16 @@ static inline char* bump(char*& p, size_t bytes) {
     return r;
 }
 
+// the BasicRNNCell's per-layer weights (HOST arrays of num_layers DEVICE pointers) and the length of gather_row
+struct RnnCell {
+    const float* const* w;
+    const float* const* b;
+    const float* const* packed;
+    int64_t M;
+};
+
 static int propagate(
-        const float* h0, int V, int D, int T,
+        const RnnCell* rnn, const float* h0, int V, int D, int T,
         const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
         const float* nin, int use_avg,
         int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
@@ -43,10 +56,12 @@ static int propagate(
     GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0 && T > 0, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(num_layers > 0 && layer_timesteps && res_ptr && layer_out, "bad layer description");
     GGNN_CHECK_ARG(edge_w || edge_packed, "edge weights missing");
-    GGNN_CHECK_ARG(bg && bc && (gru_packed || (Wg && Wc)), "GRU weights missing");
+    if (rnn) GGNN_CHECK_ARG(rnn->b && (rnn->packed || rnn->w) && rnn->M >= 0, "RNN weights missing");
+    else GGNN_CHECK_ARG(bg && bc && (gru_packed || (Wg && Wc)), "GRU weights missing");
+    const bool compact = pair_node != nullptr && type_row_off != nullptr;
+    GGNN_CHECK_ARG(!rnn || compact, "the RNN cell runs on the compacted transform only (pair_node, type_row_off)");
     if (V == 0) return GGNN_OK;
     GGNN_CHECK_ARG(h0 && row_ptr && ws, "null pointer");
-    const bool compact = pair_node != nullptr && type_row_off != nullptr;
     GGNN_CHECK_ARG(!attn_factors || compact, "propagation attention needs the compacted transform (pair_node, type_row_off)");
     const int64_t rows = compact ? type_row_off[T] : -1;
     if (ws_bytes < ggnn_sparse_propagate_workspace_bytes(V, D, T, rows))
@@ -90,14 +105,18 @@ static int propagate(
         const float* cur = states[l];              // :152
         const int steps = layer_timesteps[l];
         const float* bias_l = edge_bias ? edge_bias[l] : nullptr;
-        const bool packed_gru = gru_packed && gru_packed[l] && ggnn_gru_is_fused(D) && nx <= 3;
+        const bool packed_gru = !rnn && gru_packed && gru_packed[l] && ggnn_gru_is_fused(D) && nx <= 3;
         const int fmt_l = gru_fmt ? gru_fmt[l] : GGNN_GRU_FMT_BF16X3;      // the format gru_packed[l] was packed in
         // fuse_gather = the largest number of concatenated GRU inputs (residuals + messages) for which the segment sum
         // is gathered inside the GRU kernel; 0 = never.
         const float* factors_l = attn_factors ? attn_factors[l] : nullptr;
         GGNN_CHECK_ARG(!attn_factors || factors_l, "attn_factors[%d] is null", l);
-        const bool gather_in_gru = !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
+        const bool gather_in_gru = !rnn && !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
                                    (unsigned long long)V * T * D < (1ULL << 30);      // (its 32-bit byte offsets)
+        const bool gather_in_rnn = rnn && fuse_gather > 0 && nx <= fuse_gather && rnn->packed && rnn->packed[l] &&
+                                   ggnn_rnn_fused_supported(D, nx) && bias_l == nullptr &&
+                                   (unsigned long long)V * D < (1ULL << 30) && (unsigned long long)(rows > 0 ? rows : 1) * D < (1ULL << 30);
+        if (rnn) GGNN_CHECK_ARG(rnn->b[l] && (gather_in_rnn || (rnn->w && rnn->w[l])), "layer %d needs raw RNN weights (no fused cell for it)", l);
         for (int s = 0; s < steps; ++s) {          // :153
             int rc;
             if (compact) {
@@ -115,7 +134,14 @@ static int propagate(
             static const bool dyn_tiles = [] { const char* e = getenv("GGNN_DYN_TILES"); return !e || atoi(e) != 0; }();
             int32_t* counter = (dyn_tiles && step_no < kTileCounters) ? counters + step_no : nullptr;
             ++step_no;
-            if (gather_in_gru) {
+            if (gather_in_rnn) {
+                rc = ggnn_rnn_packed_gather_f32(xs, nx, cur, rnn->packed[l], rnn->b[l], out, H, rows > 0 ? rows : 1, row_ptr, gather_row,
+                                                rnn->M, nin, T, use_avg, nullptr, V, D, act, stream);
+            } else if (rnn) {
+                rc = ggnn_gather_segment_sum_f32(H, row_ptr, gather_row, nin, bias_l, use_avg, incoming, V, D, T, stream);
+                if (rc) return rc;
+                rc = ggnn_rnn_f32(xs, nx, cur, rnn->w[l], rnn->b[l], out, V, D, act, stream);
+            } else if (gather_in_gru) {
                 rc = ggnn_gru_packed_gather_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, H, row_ptr, gather_row, nin, T,
                                                 use_avg, V, D, act, fmt_l, counter, stream);
             } else {
@@ -152,7 +178,7 @@ extern "C" int ggnn_sparse_propagate_f32(
         const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
         const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act, int fuse_gather,
         float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
-    return propagate(h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+    return propagate(nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
                      res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
                      layer_out, ws, ws_bytes, nullptr, nullptr, stream);
 }
@@ -169,7 +195,24 @@ extern "C" int ggnn_sparse_propagate_attn_f32(
         ggnn_stream_t stream) {
     GGNN_CHECK_ARG(attn_factors, "attn_factors is null");
     if (D > 256) return ggnn::fail(GGNN_E_UNSUPPORTED, "propagation attention supports hidden sizes up to 256 (got %d)", D);
-    return propagate(h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+    return propagate(nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
                      res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
                      layer_out, ws, ws_bytes, slot_pair, attn_factors, stream);
+}
+
+extern "C" int ggnn_sparse_propagate_rnn_f32(
+        const float* h0, int V, int D, int T,
+        const int32_t* row_ptr, const int32_t* gather_row, int64_t M, const int32_t* pair_node, const int64_t* type_row_off,
+        const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+        const float* const* rnn_w, const float* const* rnn_b, const float* const* rnn_packed,
+        const int32_t* edge_fmt, int act, int fuse_gather, float* const* layer_out, void* ws, size_t ws_bytes,
+        ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(pair_node && type_row_off, "the RNN cell runs on the compacted transform only (pair_node, type_row_off)");
+    GGNN_CHECK_ARG(act == GGNN_ACT_TANH || act == GGNN_ACT_RELU, "unknown activation %d", act);
+    const RnnCell cell{rnn_w, rnn_b, rnn_packed, M};
+    return propagate(&cell, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                     res_idx, edge_w, edge_packed, edge_bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, edge_fmt, act,
+                     fuse_gather, layer_out, ws, ws_bytes, nullptr, nullptr, stream);
 }

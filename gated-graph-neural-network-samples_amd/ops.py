@@ -1139,6 +1139,17 @@ class PackedWeights:
             hit = self._store(self._gru_bwd, key, (Wg, Wc), packed)
         return hit
 
+    def rnn(self, W: torch.Tensor, nx: int, D: int) -> torch.Tensor:
+        """The nx + 1 exact bf16x3 stage images of the gather-fused BasicRNNCell (ggnn_rnn_pack_weights_f32), once per weight
+        version.  (nx, D) must be in the supported set: rnn_fused_supported."""
+        if not hasattr(self, "_rnn"):
+            self._rnn = {}
+        key = self._key(W) + (int(nx),)
+        hit = self._lookup(self._rnn, key, (W,))
+        if hit is None:
+            hit = self._store(self._rnn, key, (W,), rnn_pack(W, nx))
+        return hit
+
     def edge(self, W: torch.Tensor, fmt: int = GRU_FMT_EXACT) -> torch.Tensor:
         """The compacted transform's stage images of W [T, D, D] in the operand format `fmt` (the launch that consumes them must be
         given the same format)."""
@@ -1213,13 +1224,16 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
                      Wg: Sequence[torch.Tensor], bg: Sequence[torch.Tensor], Wc: Sequence[torch.Tensor], bc: Sequence[torch.Tensor],
                      gru_packed: Optional[Sequence[torch.Tensor]], activation: str,
                      fuse_gather: Optional[bool] = None, gru_fmt: Optional[Sequence[int]] = None,
-                     edge_fmt: Optional[Sequence[int]] = None, attn: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+                     edge_fmt: Optional[Sequence[int]] = None, attn: Optional[Sequence[torch.Tensor]] = None,
+                     rnn: Optional[Sequence[Sequence[Optional[torch.Tensor]]]] = None) -> List[torch.Tensor]:
     """chem_tensorflow_sparse.py:131-218 in ONE native call (ggnn_sparse_propagate_f32): returns
     node_states_per_layer[1:], the last entry being the final node representations.
     gru_fmt / edge_fmt: per layer, the operand format gru_packed[l] / edge_packed[l] was packed in (None: BF16X3 for every layer).
     fuse_gather (default FUSE_GATHER): gather the segment sum inside the GRU kernel where the layer allows it.
     attn: per layer, the [T] edge_type_attention_weights (:94-96): the propagation-attention form of the loop
-    (ggnn_sparse_propagate_attn_f32; needs `comp`)."""
+    (ggnn_sparse_propagate_attn_f32; needs `comp`).
+    rnn: (W per layer, b per layer, packed images per layer | None) of the BasicRNNCell: the RNN form of the loop
+    (ggnn_sparse_propagate_rnn_f32; needs `comp`; Wg / bg / Wc / bc / gru_packed are not read)."""
     if fuse_gather is None:
         fuse_gather = FUSE_GATHER
     lib = _lib.load()
@@ -1241,6 +1255,17 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
     i32 = lambda xs: (ctypes.c_int32 * max(len(xs), 1))(*xs)
     off = None if comp is None else (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
     gather = index.gather_row if comp is None else comp.gather_row
+    if rnn is not None:
+        rnn_w, rnn_b, rnn_packed = rnn
+        if comp is None or attn is not None or len(rnn_w) != L or len(rnn_b) != L:
+            raise ValueError("the RNN cell's one-call form needs the compacted transform, no attention, and one (W, b) per layer")
+        _launch("sparse_propagate_rnn", lambda: lib.ggnn_sparse_propagate_rnn_f32(
+            _ptr(h0), V, D, T, _ptr(index.row_ptr), _ptr(gather), gather.numel(), _ptr(comp.pair_node), off,
+            _ptr(nin), 1 if use_avg else 0, L, i32([int(x) for x in layer_timesteps]), i32(res_ptr), i32(res_idx),
+            _ptr_array(edge_w), _ptr_array(edge_packed), _ptr_array(edge_bias), _ptr_array(rnn_w), _ptr_array(rnn_b),
+            _ptr_array(rnn_packed), None if edge_fmt is None else i32([int(f) for f in edge_fmt]), act, int(fuse_gather),
+            _ptr_array(outs), _ptr(ws), ws_bytes, _stream()))
+        return outs
     if attn is not None:
         if comp is None or len(attn) != L:
             raise ValueError("propagation attention needs the compacted transform and one [T] factor tensor per layer")
@@ -1296,6 +1321,68 @@ def gru_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, pa
         segs, len(residual_segs) + 1, _ptr(h), _ptr(packed), _ptr(bg), _ptr(bc), _ptr(out), _ptr(H), _ptr(index.row_ptr),
         _ptr(gather), None if nin is None else _ptr(nin), index.num_edge_types, 0 if nin is None else 1, V, D, act, int(fmt),
         _ptr(tile_counter), _stream()))
+    return out
+
+
+def rnn_fused_supported(D: int, nx: int) -> bool:
+    """True when the BasicRNNCell with nx concatenated inputs (residuals + messages) has the gather-fused single launch at width D
+    (ggnn_rnn_fused_supported: all nx + 1 weight images resident in LDS -- D = 32 / 64 with nx <= 3, D = 100 with nx = 1)."""
+    return bool(_lib.load().ggnn_rnn_fused_supported(int(D), int(nx)))
+
+
+def rnn_fused_launch_geometry(D: int, nx: int) -> Tuple[int, int]:
+    """(rows a workgroup of the gather-fused RNN cell covers per round of its tile loop, the most workgroups a launch starts)."""
+    rows, wgs = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().ggnn_rnn_fused_launch_geometry(int(D), int(nx), ctypes.byref(rows), ctypes.byref(wgs))
+    return rows.value, wgs.value
+
+
+def rnn_pack(W: torch.Tensor, nx: int) -> torch.Tensor:
+    """W [(nx+1) D, D] -> the nx + 1 stage images of ggnn_rnn_packed_gather_f32 (PackedWeights.rnn caches them per weight version)."""
+    lib = _lib.load()
+    _req(W, torch.float32, "W")
+    if W.dim() != 2 or W.shape[0] != (nx + 1) * W.shape[1]:
+        raise ValueError("W must be [(nx+1)*D, D]")
+    D = W.shape[1]
+    packed = torch.empty(max(lib.ggnn_rnn_packed_bytes(D, nx) // 4, 4), dtype=torch.float32, device=W.device)
+    check(lib.ggnn_rnn_pack_weights_f32(_ptr(W), nx, D, _ptr(packed), _stream()))
+    return packed
+
+
+def rnn_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, packed: torch.Tensor, b: torch.Tensor,
+                      Hc: torch.Tensor, index: MessageIndex, gather_row: Optional[torch.Tensor],
+                      num_incoming_edges_per_type: Optional[torch.Tensor], activation: str = "tanh",
+                      save: Optional[dict] = None) -> torch.Tensor:
+    """chem_tensorflow_sparse.py:198-216 for the BasicRNNCell in one launch (ggnn_rnn_packed_gather_f32): the cell whose last
+    input segment -- the aggregated messages -- is summed from the transformed rows `Hc` inside the kernel (no edge bias; the
+    mean with num_incoming_edges_per_type, the plain sum with None).  gather_row: message slot -> row of Hc (None: the index's
+    own).  save (dict): receives the gathered segment as save["incoming"] (training: an operand of the weight gradient)."""
+    lib = _lib.load()
+    _req(h, torch.float32, "h"); _req(Hc, torch.float32, "Hc"); _req(b, torch.float32, "b")
+    V, D = h.shape
+    if Hc.dim() != 2 or Hc.shape[1] != D:
+        raise ValueError("Hc must be [R, D]")
+    for i, x in enumerate(residual_segs):
+        _req(x, torch.float32, "residual_segs[%d]" % i)
+        if x.shape != (V, D):
+            raise ValueError("residual_segs[%d] must be [V,D]" % i)
+    act = ACT_IDS.get(activation.lower())
+    if act is None:
+        raise Exception("Unknown activation function type '%s'." % activation)
+    nx = len(residual_segs) + 1
+    segs = (ctypes.c_void_p * max(nx - 1, 1))(*[s.data_ptr() for s in residual_segs])
+    out = torch.empty_like(h)
+    nin = num_incoming_edges_per_type
+    if nin is not None:
+        _req(nin, torch.float32, "num_incoming_edges_per_type")
+    gather = index.gather_row if gather_row is None else gather_row
+    inc = None
+    if save is not None:
+        inc = save["incoming"] = torch.empty_like(h)
+    _launch("rnn_fused_gather[nx=%d]" % nx, lambda: lib.ggnn_rnn_packed_gather_f32(
+        segs, nx, _ptr(h), _ptr(packed), _ptr(b), _ptr(out), _ptr(Hc), Hc.shape[0], _ptr(index.row_ptr), _ptr(gather),
+        gather.numel(), None if nin is None else _ptr(nin), index.num_edge_types, 0 if nin is None else 1, _ptr(inc), V, D, act,
+        _stream()))
     return out
 
 

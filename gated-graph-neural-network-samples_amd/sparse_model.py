@@ -282,6 +282,14 @@ class SparseGGNNChemModel(ChemModel):
         return bool(p.get('compact_attention')) and bool(p['use_propagation_attention']) and self.cell_type == 'gru' \
             and torch.device(self.device).type == 'cuda' and self._kw <= 256 and ops.compact_supported(self._kw)
 
+    def rnn_route(self) -> bool:
+        """True when the BasicRNNCell (graph_rnn_cell = RNN, the R-GCN configuration) runs on the compacted fast route: the opt-in
+        key params['compact_rnn'], no propagation attention, a GPU model and a kernel width that has a compacted transform
+        (32 / 64 / 100 / 128 / 192 / 256 and what pads to them).  Anything else keeps the dense-transform variant route."""
+        p = self.params
+        return bool(p.get('compact_rnn')) and self.cell_type == 'rnn' and not p['use_propagation_attention'] \
+            and torch.device(self.device).type == 'cuda' and ops.compact_supported(self._kw)
+
     # ---- the hot path -----------------------------------------------------------------------------------
     def compute_final_node_representations(self) -> torch.Tensor:
         """chem_tensorflow_sparse.py:117-218."""
@@ -306,7 +314,12 @@ class SparseGGNNChemModel(ChemModel):
         variant = self.params['use_propagation_attention'] or self.cell_type != 'gru'
         gru_fmts = self.gru_formats(h0, ew_keep, st_keep, need_grad)
         attn_route = self.attention_route() and h0.is_cuda
+        rnn_route = self.rnn_route() and h0.is_cuda
 
+        if rnn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
+            # inference with the RNN cell on the compacted route: ONE native call, the cell fused with the segment sum where it can be
+            final = self._propagate_native_rnn(h0, index, nin, use_avg, act)
+            return final if Dk == h_dim else final[:, :h_dim].contiguous()
         if attn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
             # inference with attention on the compacted route: the same ONE native call, every product in the exact format
             final = self._propagate_native(h0, index, nin, use_avg, act, gru_fmts, attention=True)
@@ -344,10 +357,10 @@ class SparseGGNNChemModel(ChemModel):
                     # non-default switches, training: HIP forward, autograd-derived backward (variants.py)
                     from .variants import variant_step
                     cur = variant_step(cur, index, nin, edge_weights, edge_biases, attn_w, use_avg, layer_residual_states,
-                                       self.cell_type, tuple(cell), act, compact_attention=attn_route)
+                                       self.cell_type, tuple(cell), act, compact_attention=attn_route, compact_rnn=rnn_route)
                 elif variant:
                     cur = self._variant_step(cur, index, nin, edge_weights.contiguous(), edge_biases, attn_w, use_avg,
-                                             layer_residual_states, cell, act, compact_attention=attn_route)
+                                             layer_residual_states, cell, act, compact_attention=attn_route, compact_rnn=rnn_route)
                 else:
                     cur = propagation_step(cur, index, nin, edge_weights, edge_biases, use_avg,
                                            layer_residual_states, cell, act, need_grad,
@@ -374,10 +387,15 @@ class SparseGGNNChemModel(ChemModel):
         return uid
 
     def _variant_step(self, h, index, nin, edge_weights, edge_biases, attn_w, use_avg, residual_states, cell, act,
-                      compact_attention: bool = False):
+                      compact_attention: bool = False, compact_rnn: bool = False):
         """One timestep with the non-default switches of chem_tensorflow_sparse.py: propagation attention
         (:147-149, 170-196) and/or the BasicRNNCell / CudnnCompatibleGRUCell cells (:105-110).  Dense transform, unless
-        compact_attention (attention_route()): compacted transform, attention sum over the compact rows, packed GRU."""
+        compact_attention (attention_route()): compacted transform, attention sum over the compact rows, packed GRU;
+        or compact_rnn (rnn_route()): compacted transform, then the BasicRNNCell with the segment sum gathered inside
+        (ops.rnn_packed_gather) or, for layers it does not take, the segment sum over the compact rows and ops.rnn."""
+        if compact_rnn:
+            from .variants import compact_rnn_forward
+            return compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, cell[0], cell[1], act)[0]
         if compact_attention:
             from .autograd import _PACKED
             from .variants import compact_sources
@@ -432,6 +450,28 @@ class SparseGGNNChemModel(ChemModel):
                                     [c.candidate_kernel for c in cells], [c.candidate_bias for c in cells],
                                     gru_packed, act, gru_fmt=gru_fmts, edge_fmt=edge_fmts,
                                     attn=[lay[2] for lay in layers] if attention else None)
+        return outs[-1]
+
+    def _propagate_native_rnn(self, h0, index, nin, use_avg, act) -> torch.Tensor:
+        """compute_final_node_representations on rnn_route() through ggnn_sparse_propagate_rnn_f32: compacted transform on packed
+        edge images, then the gather-fused BasicRNNCell on its packed images (layers the kernel does not take: the segment sum over
+        the compact rows and the generic cell on the raw weights).  Every product in the exact format."""
+        from .autograd import _PACKED
+        from .variants import compact_sources
+        D = self._kw
+        L = len(self.params['layer_timesteps'])
+        comp = compact_sources(index)
+        layers = [self._kernel_layer(l, False) for l in range(L)]
+        edge_w = [lay[0].contiguous() for lay in layers]
+        edge_packed = [_PACKED.edge(w) for w in edge_w]
+        edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
+        cells = [lay[3] for lay in layers]
+        residuals = [self.params['residual_connections'].get(str(l)) or [] for l in range(L)]
+        rnn_packed = [_PACKED.rnn(c.kernel, len(residuals[l]) + 1, D)
+                      if edge_bias is None and ops.rnn_fused_supported(D, len(residuals[l]) + 1) else None for l, c in enumerate(cells)]
+        outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals, edge_w, edge_packed,
+                                    edge_bias, None, None, None, None, None, act, edge_fmt=[ops.GRU_FMT_EXACT] * L,
+                                    rnn=([c.kernel for c in cells], [c.bias for c in cells], rnn_packed))
         return outs[-1]
 
     def _graph_nodes_sorted(self) -> bool:

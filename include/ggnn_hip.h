@@ -471,6 +471,47 @@ int ggnn_sparse_propagate_attn_f32(const float* h0, int V, int D, int T,
                                    int fuse_gather, float* const* layer_out, void* ws, size_t ws_bytes,
                                    const int32_t* slot_pair, const float* const* attn_factors, ggnn_stream_t stream);
 
+/* ---- BasicRNNCell with the segment sum fused in (the R-GCN configuration of the sparse GGNN) ----------------------------------
+ * h' = act([x_0 | .. | x_{nx-2} | incoming | h] W + b) in ONE launch, with
+ *   incoming[v] = (sum over the slots row_ptr[v]..row_ptr[v+1] of Hrows[gather_row[slot]]) / (sum_t nin[v,t] + 1e-7)
+ * gathered inside the kernel in the slot order and arithmetic of ggnn_gather_segment_sum_f32 without bias (bit-identical; the
+ * division only with use_avg).  The nx + 1 weight blocks [D, D] of W [(nx+1)D, D] live in LDS as exact bf16x3 images for the whole
+ * launch, so the supported set is what fits 160 KiB:
+ *   ggnn_rnn_fused_supported(D, nx)   1 for D in {32, 64} with nx in 1..3 and for D = 100 with nx = 1; 0 otherwise.  Every entry
+ *                                     point below returns GGNN_E_UNSUPPORTED (ggnn_rnn_packed_bytes: 0) exactly where it is 0.
+ *   ggnn_rnn_packed_bytes / ggnn_rnn_pack_weights_f32   W -> the nx + 1 images, once per weight version
+ *   ggnn_rnn_fused_launch_geometry    {rows a workgroup covers per round of its tile loop, the most workgroups a launch starts}
+ *   ggnn_rnn_packed_gather_f32        the launch.  x_segs: HOST array of the nx - 1 residual segments [V, D] (may be NULL at
+ *                                     nx = 1); Hrows [num_rows, D]; row_ptr [V + 1] (values are clamped to [0, M]); gather_row [M]
+ *                                     (a value outside [0, num_rows) contributes nothing and is never dereferenced); nin [V, T]
+ *                                     (required with use_avg); save_incoming: NULL, or [V, D] that receives the gathered segment
+ *                                     (training; h_out is bit-identical with and without it).  h_out / save_incoming must not alias
+ *                                     an input.  No edge bias.  V == 0 is a no-op; V*D or num_rows*D >= 2^30: GGNN_E_UNSUPPORTED. */
+int ggnn_rnn_fused_supported(int D, int nx);
+size_t ggnn_rnn_packed_bytes(int D, int nx);
+int ggnn_rnn_pack_weights_f32(const float* W, int nx, int D, float* packed, ggnn_stream_t stream);
+void ggnn_rnn_fused_launch_geometry(int D, int nx, int* rows_per_workgroup, int* max_workgroups);
+int ggnn_rnn_packed_gather_f32(const float* const* x_segs, int nx, const float* h, const float* packed, const float* b,
+                               float* h_out, const float* Hrows, int64_t num_rows, const int32_t* row_ptr,
+                               const int32_t* gather_row, int64_t M, const float* nin, int T, int use_avg,
+                               float* save_incoming, int V, int D, int act, ggnn_stream_t stream);
+
+/* ggnn_sparse_propagate_f32 for graph_rnn_cell = RNN on the compacted transform.  The compact form is REQUIRED (pair_node /
+ * type_row_off non-NULL, gather_row = the remapped rows; GGNN_E_INVALID otherwise).  Per timestep: the compacted transform on
+ * edge_packed[l] (or raw edge_w[l]), then -- for a layer with rnn_packed[l], ggnn_rnn_fused_supported(D, nx) and no edge bias --
+ * ggnn_rnn_packed_gather_f32; otherwise ggnn_gather_segment_sum_f32 over the compact rows and ggnn_rnn_f32 on rnn_w[l].
+ *   rnn_w [(nx+1)D, D], rnn_b [D], rnn_packed (ggnn_rnn_pack_weights_f32; the array or single entries may be NULL): HOST arrays of
+ *   num_layers DEVICE pointers.  M: the length of gather_row.  fuse_gather: as in ggnn_sparse_propagate_f32 (the largest nx that
+ *   runs the fused cell; 0: never).  Same workspace as ggnn_sparse_propagate_f32. */
+int ggnn_sparse_propagate_rnn_f32(const float* h0, int V, int D, int T,
+                                  const int32_t* row_ptr, const int32_t* gather_row, int64_t M, const int32_t* pair_node,
+                                  const int64_t* type_row_off, const float* nin, int use_avg,
+                                  int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+                                  const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+                                  const float* const* rnn_w, const float* const* rnn_b, const float* const* rnn_packed,
+                                  const int32_t* edge_fmt, int act, int fuse_gather, float* const* layer_out, void* ws,
+                                  size_t ws_bytes, ggnn_stream_t stream);
+
 /* ---- (a-B) element-wise stages of the GRU backward (TF autodiff of GRUCell, chem_tensorflow.py:184) -------
  * stage 1: dpc = g*(1-u)*act'(c) -> dpc [V,D];  g*(h-c)*u*(1-u) -> dpg[:, D:2D];  g*u -> dh [V,D];
  *          r*h -> a_c[:, col0:col0+D] (row stride lda: the [x | r*h] operand of the dWc product)
