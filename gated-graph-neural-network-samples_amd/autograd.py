@@ -19,10 +19,6 @@ from . import ops
 # supports it; set False to force the dense [V,D]x[D,T*D] form (the form the training path uses).
 USE_COMPACT_TRANSFORM = True
 
-# LDS stage images of the weights, rebuilt only when a weight tensor's version counter changes
-_PACKED = ops.PackedWeights()
-
-
 def propagation_step(h: torch.Tensor, index: "ops.MessageIndex", nin: torch.Tensor, edge_weights: torch.Tensor,
                      edge_biases: Optional[torch.Tensor], use_avg: bool, residual_states: Sequence[torch.Tensor],
                      cell, activation: str, need_grad: bool = False, ew_mask=None, gru_fmt: int = ops.GRU_FMT_EXACT,
@@ -47,7 +43,7 @@ def propagation_step(h: torch.Tensor, index: "ops.MessageIndex", nin: torch.Tens
         if comp is None:
             comp = index._compact = ops.build_compact_sources(index)
         ew = edge_weights.contiguous()
-        Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(ew, edge_fmt), ew.shape[0], comp, fmt=edge_fmt)
+        Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(ew, edge_fmt), ew.shape[0], comp, fmt=edge_fmt)
         if gather_in_gru:
             Hrows, gather_row = Hc, comp.gather_row
         else:
@@ -59,12 +55,12 @@ def propagation_step(h: torch.Tensor, index: "ops.MessageIndex", nin: torch.Tens
         else:
             incoming = ops.gather_segment_sum(H, index, nin, edge_biases, use_avg)
     if gather_in_gru:
-        packed = _PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(residual_states) + 1, D, gru_fmt)
+        packed = ops.PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(residual_states) + 1, D, gru_fmt)
         return ops.gru_packed_gather(list(residual_states), h, packed, cell.gates_bias, cell.candidate_bias, Hrows, index,
                                      gather_row, nin if use_avg else None, activation, fmt=gru_fmt)
     xs = list(residual_states) + [incoming]
     if ops.gru_is_fused(D) and nx <= ops.GRU_FUSED_MAX_INPUTS:     # (more inputs: the generic two-launch GRU below)
-        packed = _PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(xs), D, gru_fmt)
+        packed = ops.PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(xs), D, gru_fmt)
         return ops.gru_packed(xs, h, packed, cell.gates_bias, cell.candidate_bias, activation, fmt=gru_fmt)
     return ops.gru(xs, h, cell.gates_kernel, cell.gates_bias, cell.candidate_kernel, cell.candidate_bias, activation)
 

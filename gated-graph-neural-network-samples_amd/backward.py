@@ -23,11 +23,10 @@ from __future__ import annotations
 
 import contextlib
 import os
-import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, derived, ops
 from ._lib import check
 from .utils import SMALL_NUMBER
 
@@ -200,49 +199,25 @@ def _source_index(index: "ops.MessageIndex", num_nodes: int) -> "ops.MessageInde
     return src_index
 
 
-class _TransposeCache:
-    """W^T (contiguous) per weight tensor version: the backward of every timestep of a layer multiplies by the same
+# transposed and dropped-out weights, one entry per (weight view, kind) and replaced when the weight's version moves (derived.py)
+_DERIVED = derived.Cache(256)
+
+
+def transposed(W: torch.Tensor, dims=(0, 1)) -> torch.Tensor:
+    """W.transpose(*dims).contiguous(), once per weight version: the backward of every timestep of a layer multiplies by the same
     transposed weights, so the transpose copy is made once per layer and optimisation step."""
-
-    def __init__(self):
-        self._t = {}
-
-    def get(self, W: torch.Tensor, dims=(0, 1)) -> torch.Tensor:
-        key = (id(W), W._version, dims)
-        hit = self._t.get(key)
-        if hit is not None and hit[0]() is W:
-            return hit[1]
-        if len(self._t) > 256:
-            self._t.clear()
-        Wt = W.transpose(*dims).contiguous()
-        self._t[key] = (weakref.ref(W), Wt)
-        return Wt
+    return _DERIVED.get((W,), ("transposed", dims), lambda: W.transpose(*dims).contiguous())
 
 
-_TRANSPOSED = _TransposeCache()
-
-
-class _MaskedWeights:
+def masked(W: torch.Tensor, keep: float, seed: int) -> torch.Tensor:
     """The dropped-out edge weights of a layer (chem_tensorflow_sparse.py:91), formed once per (variable version, mask) and shared
-    by the layer's timesteps."""
-
-    def __init__(self):
-        self._t = {}
-
-    def get(self, W: torch.Tensor, keep: float, seed: int) -> torch.Tensor:
-        base = W._base if W._base is not None else W
-        key = (id(base), W.data_ptr(), tuple(W.shape))
-        hit = self._t.get(key)
-        if hit is not None and hit[0]() is base and hit[1] == (base._version, keep, seed):
-            return hit[2]
-        if len(self._t) > 64:
-            self._t.clear()
-        Wm = ops.dropout(W.detach().contiguous(), keep, seed)
-        self._t[key] = (weakref.ref(base), (base._version, keep, seed), Wm)
-        return Wm
-
-
-_MASKED = _MaskedWeights()
+    by the layer's timesteps.  One entry per variable: the mask of this step replaces the mask of the last one."""
+    Wm = _DERIVED.lookup((W,), "masked")
+    # (keep, seed) rides on the stored tensor object, not in the key: a key per seed would pile up while the variable lives
+    if getattr(Wm, "_mask", None) != (keep, seed):
+        Wm = _DERIVED.store((W,), "masked", ops.dropout(W.detach().contiguous(), keep, seed))
+        Wm._mask = (keep, seed)
+    return Wm
 
 
 class PropagationStepFn(torch.autograd.Function):
@@ -257,22 +232,21 @@ class PropagationStepFn(torch.autograd.Function):
         ctx.var_shapes = tuple(None if t is None else tuple(t.shape) for t in (edge_weights, edge_biases, Wg, bg, Wc, bc))
         if ew_mask is not None:
             # `edge_weights` is the variable: multiply by its masked copy; backward() sends the gradient back through the mask
-            edge_weights = _MASKED.get(edge_weights, float(ew_mask[0]), int(ew_mask[1]))
+            edge_weights = masked(edge_weights, float(ew_mask[0]), int(ew_mask[1]))
         if compact_training(D):
             # transform only the (node, type) pairs that emit a message (~1.2 V rows instead of T V)
-            from .autograd import _PACKED
             comp = getattr(index, "_compact", None)
             if comp is None:
                 comp = index._compact = ops.build_compact_sources(index)
             ctx.comp = comp
             ew = edge_weights if edge_weights.is_contiguous() else edge_weights.contiguous()
-            H = ops.msg_transform_compact_packed(h, _PACKED.edge(ew), ew.shape[0], comp)
+            H = ops.msg_transform_compact_packed(h, ops.PACKED.edge(ew), ew.shape[0], comp)
             edge_weights = ew
             if TRAIN_GATHER_IN_GRU and edge_biases is None and ops.gru_gather_fused(D) and len(residuals) + 1 <= ops.GRU_FUSED_MAX_INPUTS:
                 # the segment sum gathered inside the GRU launch, as on the inference path; the kernel also writes r, u, c and the
                 # gathered segment, which the backward pass needs (one launch and one pass over `incoming` less per timestep)
                 save = {}
-                h_new = ops.gru_packed_gather(list(residuals), h, _PACKED.gru(Wg, Wc, len(residuals) + 1, D, gru_fmt), bg, bc, H, index,
+                h_new = ops.gru_packed_gather(list(residuals), h, ops.PACKED.gru(Wg, Wc, len(residuals) + 1, D, gru_fmt), bg, bc, H, index,
                                               comp.gather_row, nin if use_avg else None, activation, save=save, fmt=gru_fmt)
                 del H
                 ctx.index, ctx.use_avg, ctx.activation, ctx.has_bias = index, use_avg, activation.lower(), False
@@ -308,8 +282,7 @@ class PropagationStepFn(torch.autograd.Function):
 
         if ops.gru_bwd_is_fused(D) and nx <= ops.GRU_FUSED_MAX_INPUTS:
             # ---- 1.-5. in ONE launch: gate algebra, dX products, mean aggregation; dpc / dpg / r*h written for the dW products
-            from .autograd import _PACKED
-            dpc, dpg, rh, dh, dxs = ops.gru_bwd_fused(g, h, r, u, c, _PACKED.gru_bwd(Wg, Wc, nx, D), nin, ctx.use_avg, nx, ctx.activation)
+            dpc, dpg, rh, dh, dxs = ops.gru_bwd_fused(g, h, r, u, c, ops.PACKED.gru_bwd(Wg, Wc, nx, D), nin, ctx.use_avg, nx, ctx.activation)
             dinc = dxs[-1]
             d_res = dxs[:-1]
             Kx = (nx + 1) * D
@@ -369,9 +342,8 @@ class DensePropagateFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h0, A, nin, W, bias, Wg, bg, Wc, bc, steps, fmt):
-        from .autograd import _PACKED
         D = h0.shape[2]
-        out, saved = ops.dense_propagate_save(h0, A, _PACKED.dense_edge(W), _PACKED.dense_gru(Wg, Wc, D), bias, bg, bc, steps, fmt)
+        out, saved = ops.dense_propagate_save(h0, A, ops.PACKED.dense_edge(W), ops.PACKED.dense_gru(Wg, Wc, D), bias, bg, bc, steps, fmt)
         ctx.var_ptrs = tuple(None if t is None else t.data_ptr() for t in (W, bias, Wg, bg, Wc, bc))
         ctx.var_shapes = tuple(None if t is None else tuple(t.shape) for t in (W, bias, Wg, bg, Wc, bc))
         ctx.save_for_backward(A, nin, W, Wg, Wc, saved)
@@ -379,12 +351,11 @@ class DensePropagateFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .autograd import _PACKED
         A, nin, W, Wg, Wc, saved = ctx.saved_tensors
         steps, N, D = saved.shape[1], saved.shape[1] * saved.shape[2], saved.shape[3]
         E = W.shape[0]
         need = ctx.needs_input_grad
-        d_h0, dpc, dpg, dx, dM = ops.dense_propagate_bwd(g.contiguous(), A, _PACKED.dense_bwd(W, Wg, Wc), saved, need_d_h0=need[0])
+        d_h0, dpc, dpg, dx, dM = ops.dense_propagate_bwd(g.contiguous(), A, ops.PACKED.dense_bwd(W, Wg, Wc), saved, need_d_h0=need[0])
         h, x, rh = (saved[k].view(N, D) for k in (0, 1, 5))            # stacked over the timesteps
         dpc, dpg, dx, dM = dpc.view(N, D), dpg.view(N, 2 * D), dx.view(N, D), dM.view(N, E * D)
         pW, pb, pWg, pbg, pWc, pbc = ctx.var_ptrs
@@ -430,7 +401,6 @@ def transform_backward(index, comp, h, W, dinc, dh, message_weights=None, sink=N
     message_weights: per-message weights w (by message id; the attention coefficients) or None.
     sink: (variable address, buffer) of the active weight-gradient sink: dW is then added to the buffer on the side stream and
     None is returned."""
-    from .autograd import _PACKED
     T = W.shape[0]
     bwd = ops.compact_backward(index, comp)
     R = comp.num_rows
@@ -445,11 +415,11 @@ def transform_backward(index, comp, h, W, dinc, dh, message_weights=None, sink=N
         dHc = ops.weighted_segment_sum(dinc, bwd.rows_index, bwd.rows_index.msg, message_weights)
     D_ = h.shape[1]
     if ops.compact_supported(D_):
-        Z = ops.msg_transform_compact_packed(dHc, _PACKED.edge(_TRANSPOSED.get(W, (1, 2))), T, bwd.identity)   # dHc W_t^T
+        Z = ops.msg_transform_compact_packed(dHc, ops.PACKED.edge_t(W), T, bwd.identity)   # dHc W_t^T
     else:
         # hidden sizes without a compacted transform kernel (96, 160, 200, 224, 288, 300 ...: the reference accepts any,
         # chem_tensorflow_sparse.py:46-50): the rows of a type are one contiguous range -> one generic GEMM per type
-        WT = _TRANSPOSED.get(W, (1, 2))
+        WT = transposed(W, (1, 2))
         Z = torch.empty((max(R, 1), D_), dtype=torch.float32, device=h.device)
         for t in range(T):
             lo, hi = int(comp.type_row_off[t]), int(comp.type_row_off[t + 1])
@@ -495,14 +465,14 @@ def _gru_backward_unfused(lib, g, h, r, u, c, Wg, Wc, nin, xs, nx, T, act, use_a
     # ---- 3. dpc Wc^T; gates pre-activation gradients ([r|u] = sigmoid([x | h] Wg + bg))
     dx = torch.empty((V, nx * D), dtype=torch.float32, device=dev)
     ops._launch("gru_bwd_dx_cand[nx=%d]" % nx, lambda: lib.ggnn_gru_bwd_dx_cand_f32(
-        dpc.data_ptr(), _TRANSPOSED.get(Wc).data_ptr(), h.data_ptr(), r.data_ptr(), dx.data_ptr(), dh.data_ptr(), dpg.data_ptr(),
+        dpc.data_ptr(), transposed(Wc).data_ptr(), h.data_ptr(), r.data_ptr(), dx.data_ptr(), dh.data_ptr(), dpg.data_ptr(),
         nx, V, D, st))
     # ---- 4. gate weights
     dWg, dbg = weight_grad(xs + [h], dpg)
     # ---- 5. dpg Wg^T; mean aggregation (chem_tensorflow_sparse.py:206-209)
     dinc = torch.empty_like(h)
     ops._launch("gru_bwd_dx_gates[nx=%d]" % nx, lambda: lib.ggnn_gru_bwd_dx_gates_f32(
-        dpg.data_ptr(), _TRANSPOSED.get(Wg).data_ptr(), dx.data_ptr(), dinc.data_ptr(), nin.data_ptr(), T, 1 if use_avg else 0,
+        dpg.data_ptr(), transposed(Wg).data_ptr(), dx.data_ptr(), dinc.data_ptr(), nin.data_ptr(), T, 1 if use_avg else 0,
         dh.data_ptr(), nx, V, D, st))
     d_res = [dx[:, i * D:(i + 1) * D] for i in range(nx - 1)]
     return dpc, dpg, dh, dinc, d_res, dWc, dbc, dWg, dbg
@@ -531,13 +501,13 @@ def _backward_dense_form(ctx, g):
                                       dpc.data_ptr(), dpg.data_ptr(), dh.data_ptr(), a_c.data_ptr(), K, nx * D, V, D, st))
     dWc = _tn(a_c, dpc)
     dbc = ops.colsum(dpc)
-    dxrh = ops.gemm([dpc], _TRANSPOSED.get(Wc))                            # [V, (nx+1)D] = dpc Wc^T
+    dxrh = ops.gemm([dpc], transposed(Wc))                            # [V, (nx+1)D] = dpc Wc^T
     drh = dxrh[:, nx * D:]
     check(lib.ggnn_gru_bwd_stage2_f32(drh.data_ptr(), K, h.data_ptr(), r.data_ptr(), dh.data_ptr(), dpg.data_ptr(), V, D, st))
     a_c[:, nx * D:] = h                                                    # reuse the buffer as [x | h]
     dWg = _tn(a_c, dpg)
     dbg = ops.colsum(dpg)
-    dxh = ops.gemm([dpg[:, :D], dpg[:, D:]], _TRANSPOSED.get(Wg))          # [V, (nx+1)D] = dpg Wg^T
+    dxh = ops.gemm([dpg[:, :D], dpg[:, D:]], transposed(Wg))          # [V, (nx+1)D] = dpg Wg^T
     dh += dxh[:, nx * D:]
     dx = dxrh[:, :nx * D] + dxh[:, :nx * D]
     d_res = [dx[:, i * D:(i + 1) * D] for i in range(nx - 1)]

@@ -147,16 +147,15 @@ class DenseGGNNChemModel(ChemModel):
         bias = self.weights['edge_biases'].reshape(self.num_edge_types, h_dim) if self.params['use_edge_bias'] else None
         cell = self.weights['node_gru']
         # the GRU's LDS weight images are packed once per weight version (the one cell is shared by all timesteps, :101-102)
-        from .autograd import _PACKED
         if USE_GRAPH_RESIDENT_KERNEL and keep_w >= 1.0 and keep_s >= 1.0 and h.is_cuda \
                 and ops.dense_propagate_supported(int(v), self.num_edge_types, h_dim):
             # all timesteps in ONE launch: a graph's states stay on its CU (ggnn_dense_propagate_f32)
             W = self.weights['edge_weights'].contiguous()
-            return ops.dense_propagate(h.reshape(b, int(v), h_dim), A.contiguous(), _PACKED.dense_edge(W),
-                                       _PACKED.dense_gru(cell.gates_kernel, cell.candidate_kernel, h_dim), bias,
+            return ops.dense_propagate(h.reshape(b, int(v), h_dim), A.contiguous(), ops.PACKED.dense_edge(W),
+                                       ops.PACKED.dense_gru(cell.gates_kernel, cell.candidate_kernel, h_dim), bias,
                                        cell.gates_bias, cell.candidate_bias, self.params['num_timesteps'],
                                        fmt=self.propagate_format(int(v)))
-        packed = _PACKED.gru(cell.gates_kernel, cell.candidate_kernel, 1, h_dim) if ops.gru_is_fused(h_dim) else None
+        packed = ops.PACKED.gru(cell.gates_kernel, cell.candidate_kernel, 1, h_dim) if ops.gru_is_fused(h_dim) else None
         for i in range(self.params['num_timesteps']):                  # :100
             # :104 a fresh weight-dropout mask per (timestep, edge type)
             W = tf_dropout(self.weights['edge_weights'], keep_w, self.dropout_seed('edge_weights', i)).contiguous()

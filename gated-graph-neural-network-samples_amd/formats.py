@@ -36,12 +36,11 @@ import functools
 import math
 import os
 import threading
-import weakref
 from typing import Any, Dict, List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, derived
 from ._lib import check
 
 F16X2, BF16X3 = 2, 3
@@ -110,44 +109,25 @@ def absmax(tensors: Sequence[torch.Tensor]) -> List[float]:
     return [float(v) for v in out.tolist()]
 
 
-class _MaxCache:
-    """max|x| per tensor, valid while the same tensor object sits at the same version (the key of ops.PackedWeights)."""
-
-    def __init__(self):
-        self._t: Dict[Any, Any] = {}
-
-    @staticmethod
-    def _base(t):
-        return t._base if t._base is not None else t
-
-    def get(self, tensors: Sequence[torch.Tensor]) -> List[float]:
-        out: List[Optional[float]] = []
-        miss = []
-        for i, t in enumerate(tensors):
-            key = (id(self._base(t)), t.data_ptr(), tuple(t.shape))
-            hit = self._t.get(key)
-            if hit is not None and hit[0]() is self._base(t) and hit[1] == t._version:
-                out.append(hit[2])
-            else:
-                out.append(None)
-                miss.append((i, key, t))
-        if miss:
-            vals = absmax([t for _, _, t in miss])
-            if len(self._t) > 4096:
-                self._t.clear()
-            for (i, key, t), v in zip(miss, vals):
-                self._t[key] = (weakref.ref(self._base(t)), t._version, v)
-                out[i] = v
-        return out  # type: ignore[return-value]
+def _cached_absmax(cache: derived.Cache, tensors: Sequence[torch.Tensor]) -> List[float]:
+    """max|x| per tensor, measured once per tensor and version: ONE absmax call (one launch, one read-back) for all misses."""
+    out = [cache.lookup((t,), "absmax") for t in tensors]
+    miss = [i for i, v in enumerate(out) if v is None]
+    if miss:
+        for i, v in zip(miss, absmax([tensors[i] for i in miss])):
+            out[i] = cache.store((tensors[i],), "absmax", v)
+    return out
 
 
-_WEIGHT_MAX = _MaxCache()
-_H0_MAX = _MaxCache()
+_WEIGHT_MAX = derived.Cache(4096)
+_H0_MAX = derived.Cache(4096)
+_ADJ_MAX = derived.Cache(4096)
+_NIN_OK = derived.Cache(1024)
 
 
 def weight_absmax(tensors: Sequence[torch.Tensor]) -> List[float]:
     """Cached per weight version (one measurement per tensor and version; every in-place update bumps the version)."""
-    return _WEIGHT_MAX.get(tensors)
+    return _cached_absmax(_WEIGHT_MAX, tensors)
 
 
 def declare_h0_absmax(feed: Dict[str, Any], value: float) -> Dict[str, Any]:
@@ -156,16 +136,13 @@ def declare_h0_absmax(feed: Dict[str, Any], value: float) -> Dict[str, Any]:
     replaced or overwritten afterwards is measured instead of trusted."""
     h0 = feed['initial_node_representation']
     feed['h0_absmax'] = float(value)
-    feed['_h0_absmax_of'] = (weakref.ref(h0), h0._version)
+    feed['_h0_absmax_of'] = derived.stamp(h0)
     # ... and, with it, the packer's second statement: the in-degree table of this feed was counted from the very adjacency lists its
     # message index was built from (nin_consistent below), tied to the table's identity and version the same way
     nin = feed.get('num_incoming_edges_per_type')
     if isinstance(nin, torch.Tensor):
-        feed['_nin_consistent_of'] = (weakref.ref(nin), nin._version)
+        feed['_nin_consistent_of'] = derived.stamp(nin)
     return feed
-
-
-_NIN_OK: Dict[Any, Any] = {}
 
 
 def nin_consistent(placeholders: Dict[str, Any], row_ptr: Optional[torch.Tensor]) -> bool:
@@ -178,24 +155,16 @@ def nin_consistent(placeholders: Dict[str, Any], row_ptr: Optional[torch.Tensor]
     nin = placeholders.get('num_incoming_edges_per_type')
     if not isinstance(nin, torch.Tensor):
         return False
-    of = placeholders.get('_nin_consistent_of')
-    if of is not None and of[0]() is nin and of[1] == nin._version:
+    if derived.stamp_holds(placeholders.get('_nin_consistent_of'), nin):
         return True
     if row_ptr is None or nin.dim() != 2 or row_ptr.numel() != nin.shape[0] + 1:
         return False
-    key = (id(nin), nin._version, id(row_ptr), row_ptr._version)
-    hit = _NIN_OK.get(key)
-    if hit is not None and hit[0]() is nin and hit[1]() is row_ptr:
-        return hit[2]
+    hit = _NIN_OK.lookup((nin, row_ptr), "nin_ok")
+    if hit is not None:
+        return hit
     deg = (row_ptr[1:] - row_ptr[:-1]).to(torch.float32)
     ok = bool((torch.isfinite(nin).all() & (nin >= 0).all() & ((nin.sum(1) + 1e-3) >= deg).all()).item()) if nin.shape[0] else True
-    if len(_NIN_OK) > 1024:
-        _NIN_OK.clear()
-    _NIN_OK[key] = (weakref.ref(nin), weakref.ref(row_ptr), ok)
-    return ok
-
-
-_ADJ_MAX = _MaxCache()
+    return _NIN_OK.store((nin, row_ptr), "nin_ok", ok)
 
 
 def declare_adjacency_absmax(feed: Dict[str, Any], value: float) -> Dict[str, Any]:
@@ -203,7 +172,7 @@ def declare_adjacency_absmax(feed: Dict[str, Any], value: float) -> Dict[str, An
     the tensor with its identity and version like declare_h0_absmax's: an adjacency tensor replaced or written afterwards is measured."""
     A = feed['adjacency_matrix']
     feed['adjacency_absmax'] = float(value)
-    feed['_adjacency_absmax_of'] = (weakref.ref(A), A._version)
+    feed['_adjacency_absmax_of'] = derived.stamp(A)
     return feed
 
 
@@ -213,13 +182,13 @@ def adjacency_absmax(A: torch.Tensor, placeholders: Optional[Dict[str, Any]] = N
     assumes entries of magnitude <= 1 -- the reference's 0 / 1 matrices; a foreign feed may weight its edges."""
     if placeholders is not None:
         v, of = placeholders.get('adjacency_absmax'), placeholders.get('_adjacency_absmax_of')
-        if v is not None and of is not None and of[0]() is A and of[1] == A._version:
+        if v is not None and derived.stamp_holds(of, A):
             return float(v)
     if A.numel() == 0:
         return 0.0
     if A.dtype != torch.float32:
         return float(A.abs().max())                   # (not the reference's feed dtype: measured outright)
-    return float(_ADJ_MAX.get([A])[0])
+    return float(_cached_absmax(_ADJ_MAX, [A])[0])
 
 
 def h0_absmax(placeholders: Dict[str, Any], h0: Optional[torch.Tensor] = None) -> float:
@@ -228,11 +197,11 @@ def h0_absmax(placeholders: Dict[str, Any], h0: Optional[torch.Tensor] = None) -
     if h0 is None:
         h0 = placeholders['initial_node_representation']
     v, of = placeholders.get('h0_absmax'), placeholders.get('_h0_absmax_of')
-    if v is not None and of is not None and of[0]() is h0 and of[1] == h0._version:
+    if v is not None and derived.stamp_holds(of, h0):
         return float(v)
-    v = _H0_MAX.get([h0])[0]                      # (per tensor object and version: a loop over a few resident feeds measures each once)
+    v = _cached_absmax(_H0_MAX, [h0])[0]                      # (per tensor object and version: a loop over a few resident feeds measures each once)
     placeholders['h0_absmax'] = v
-    placeholders['_h0_absmax_of'] = (weakref.ref(h0), h0._version)
+    placeholders['_h0_absmax_of'] = derived.stamp(h0)
     return float(v)
 
 

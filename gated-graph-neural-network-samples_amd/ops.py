@@ -21,7 +21,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, derived
 from ._lib import check
 
 ACT_IDS = {"tanh": 0, "relu": 1}
@@ -269,7 +269,7 @@ def gru(x_segs: Sequence[torch.Tensor], h: torch.Tensor, Wg: torch.Tensor, bg: t
             and len(x_segs) <= GRU_FUSED_MAX_INPUTS:
         _req(Wg, torch.float32, "Wg"); _req(Wc, torch.float32, "Wc")
         # (the images are cached per weight version and format: this branch runs once per timestep on the non-gather training path)
-        packed = _gru_images().gru(Wg, Wc, len(x_segs), h.shape[1], int(fmt))
+        packed = PACKED.gru(Wg, Wc, len(x_segs), h.shape[1], int(fmt))
         return gru_packed(x_segs, h, packed, bg, bc, activation, out=out, fmt=int(fmt), save=save)
     _req(h, torch.float32, "h")
     V, D = h.shape
@@ -1005,164 +1005,96 @@ def gather_segment_sum_compact(Hc: torch.Tensor, index: MessageIndex, comp: Comp
                         nin, edge_biases, use_avg, out, V, D, T)
 
 
-# ---- pre-packed weights (inference) ---------------------------------------------------------------------
-_GRU_IMAGES_CACHE = None
-
-
-def _gru_images():
-    """ops.gru's own image cache (raw-weight callers that ask for a packed operand format)."""
-    global _GRU_IMAGES_CACHE
-    if _GRU_IMAGES_CACHE is None:
-        _GRU_IMAGES_CACHE = PackedWeights()
-    return _GRU_IMAGES_CACHE
+# ---- pre-packed weights ---------------------------------------------------------------------------------
+def _image(nbytes: int, like: torch.Tensor) -> torch.Tensor:
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=like.device)
 
 
 class PackedWeights:
-    """Cache of the kernels' LDS stage images of weight tensors, keyed by (storage pointer, version counter):
-    during inference the weights do not change between batches, so the pack pre-pass runs once per weight
-    version instead of once per launch.  Any in-place update of a weight bumps tensor._version and repacks."""
+    """The kernels' LDS stage images of weight tensors, one per (weight tensors, kind, format) and weight version (derived.Cache):
+    the pack pre-pass runs once per weight version instead of once per launch.  Any in-place update of a weight bumps
+    tensor._version and repacks; a view with other strides is another key, misses, and is refused by the packer's check."""
 
     def __init__(self):
-        self._gru = {}
-        self._edge = {}
-
-    @staticmethod
-    def _base(t: torch.Tensor) -> torch.Tensor:
-        return t._base if t._base is not None else t
-
-    @classmethod
-    def _key(cls, *tensors):
-        # identity of the owning tensor objects (views share their base's version counter) + view geometry
-        return tuple((id(cls._base(t)), t.data_ptr(), tuple(t.shape)) for t in tensors)
-
-    @classmethod
-    def _lookup(cls, table, key, tensors):
-        """A hit is valid only while the SAME tensor objects are alive at the same version: a pointer/version
-        pair alone can be recycled by the allocator for a different model's weights."""
-        entry = table.get(key)
-        if entry is None:
-            return None
-        refs, versions, packed, ready, stream_id = entry
-        for r, v, t in zip(refs, versions, tensors):
-            if r() is not cls._base(t) or v != t._version:
-                return None
-        # the image was written on another stream: order this stream after the pack launch (an event wait on the device --
-        # a host synchronisation here used to drain the GPU queue once per layer and training step)
-        if ready is not None:
-            cur = torch.cuda.current_stream()
-            if cur.cuda_stream != stream_id:
-                if not ready.query():
-                    cur.wait_event(ready)
-                packed.record_stream(cur)                    # (its memory belongs to the packing stream's pool)
-        return packed
-
-    @classmethod
-    def _store(cls, table, key, tensors, packed):
-        import weakref
-        if len(table) >= 64:     # drop the images of weights that no longer exist; never evict a live model's
-            for k in [k for k, e in table.items() if any(r() is None for r in e[0])]:
-                del table[k]
-            if len(table) >= 1024:
-                table.clear()
-        ready, stream_id = None, 0
-        if packed.is_cuda:
-            ready = torch.cuda.Event()
-            ready.record()                                   # after the pack launch, on the stream that ran it
-            stream_id = torch.cuda.current_stream().cuda_stream
-        table[key] = ([weakref.ref(cls._base(t)) for t in tensors], [t._version for t in tensors], packed, ready, stream_id)
-        return packed
+        self._images = derived.Cache(1024)
 
     def gru(self, Wg: torch.Tensor, Wc: torch.Tensor, nx: int, D: int, fmt: int = GRU_FMT_EXACT) -> torch.Tensor:
         """The fused GRU forward's stage images in the operand format `fmt` (formats.F16X2 / BF16X3; the launch that consumes
         them must be given the same format)."""
-        lib = _lib.load()
-        key = self._key(Wg, Wc) + (int(fmt),)
-        hit = self._lookup(self._gru, key, (Wg, Wc))
-        if hit is None:
+        def make():
+            lib = _lib.load()
             _req(Wg, torch.float32, "Wg"); _req(Wc, torch.float32, "Wc")
-            packed = torch.empty(lib.ggnn_gru_packed_bytes(D, nx) // 4, dtype=torch.float32, device=Wg.device)
+            packed = _image(lib.ggnn_gru_packed_bytes(D, nx), Wg)
             check(lib.ggnn_gru_pack_weights_f32(_ptr(Wg), _ptr(Wc), nx, D, int(fmt), _ptr(packed), _stream()))
-            hit = self._store(self._gru, key, (Wg, Wc), packed)
-        return hit
+            return packed
+        return self._images.get((Wg, Wc), ("gru", nx, D, int(fmt)), make)
 
     def dense_edge(self, W: torch.Tensor) -> torch.Tensor:
         """The E f32 stage images of the graph-resident dense kernel (ggnn_dense_edge_pack_f32), once per weight version."""
-        lib = _lib.load()
-        if not hasattr(self, "_dense_edge"):
-            self._dense_edge = {}
-        key = self._key(W)
-        hit = self._lookup(self._dense_edge, key, (W,))
-        if hit is None:
+        def make():
+            lib = _lib.load()
             _req(W, torch.float32, "edge_weights")
             T, D = W.shape[0], W.shape[1]
-            packed = torch.empty(lib.ggnn_dense_edge_packed_bytes(D, T) // 4, dtype=torch.float32, device=W.device)
+            packed = _image(lib.ggnn_dense_edge_packed_bytes(D, T), W)
             check(lib.ggnn_dense_edge_pack_f32(_ptr(W), T, D, _ptr(packed), _stream()))
-            hit = self._store(self._dense_edge, key, (W,), packed)
-        return hit
+            return packed
+        return self._images.get((W,), "dense_edge", make)
 
     def dense_gru(self, Wg: torch.Tensor, Wc: torch.Tensor, D: int) -> torch.Tensor:
         """The six plain stage images of the graph-resident dense kernel (ggnn_dense_gru_pack_f32), once per weight version."""
-        lib = _lib.load()
-        if not hasattr(self, "_dense_gru"):
-            self._dense_gru = {}
-        key = self._key(Wg, Wc)
-        hit = self._lookup(self._dense_gru, key, (Wg, Wc))
-        if hit is None:
+        def make():
+            lib = _lib.load()
             _req(Wg, torch.float32, "Wg"); _req(Wc, torch.float32, "Wc")
-            packed = torch.empty(lib.ggnn_dense_gru_packed_bytes(D) // 4, dtype=torch.float32, device=Wg.device)
+            packed = _image(lib.ggnn_dense_gru_packed_bytes(D), Wg)
             check(lib.ggnn_dense_gru_pack_f32(_ptr(Wg), _ptr(Wc), D, _ptr(packed), _stream()))
-            hit = self._store(self._dense_gru, key, (Wg, Wc), packed)
-        return hit
+            return packed
+        return self._images.get((Wg, Wc), ("dense_gru", D), make)
 
     def dense_bwd(self, W: torch.Tensor, Wg: torch.Tensor, Wc: torch.Tensor) -> torch.Tensor:
         """The transposed split images of the graph-resident dense backward (dense_bwd_pack), once per weight version."""
-        if not hasattr(self, "_dense_bwd"):
-            self._dense_bwd = {}
-        key = self._key(W, Wg, Wc)
-        hit = self._lookup(self._dense_bwd, key, (W, Wg, Wc))
-        if hit is None:
-            hit = self._store(self._dense_bwd, key, (W, Wg, Wc), dense_bwd_pack(W, Wg, Wc))
-        return hit
+        return self._images.get((W, Wg, Wc), "dense_bwd", lambda: dense_bwd_pack(W, Wg, Wc))
 
     def gru_bwd(self, Wg: torch.Tensor, Wc: torch.Tensor, nx: int, D: int) -> torch.Tensor:
         """Transposed-block stage images of the fused GRU backward (ggnn_gru_bwd_fused_f32), once per weight version."""
-        lib = _lib.load()
-        if not hasattr(self, "_gru_bwd"):
-            self._gru_bwd = {}
-        key = self._key(Wg, Wc)
-        hit = self._lookup(self._gru_bwd, key, (Wg, Wc))
-        if hit is None:
+        def make():
+            lib = _lib.load()
             _req(Wg, torch.float32, "Wg"); _req(Wc, torch.float32, "Wc")
-            packed = torch.empty(lib.ggnn_gru_bwd_packed_bytes(D, nx) // 4, dtype=torch.float32, device=Wg.device)
+            packed = _image(lib.ggnn_gru_bwd_packed_bytes(D, nx), Wg)
             check(lib.ggnn_gru_bwd_fused_f32(None, None, None, None, None, _ptr(Wg), _ptr(Wc), _ptr(packed), None, None, None, None,
                                              None, None, 0, 0, nx, 0, D, 0, _stream()))
-            hit = self._store(self._gru_bwd, key, (Wg, Wc), packed)
-        return hit
+            return packed
+        return self._images.get((Wg, Wc), ("gru_bwd", nx, D), make)
 
     def rnn(self, W: torch.Tensor, nx: int, D: int) -> torch.Tensor:
         """The nx + 1 exact bf16x3 stage images of the gather-fused BasicRNNCell (ggnn_rnn_pack_weights_f32), once per weight
         version.  (nx, D) must be in the supported set: rnn_fused_supported."""
-        if not hasattr(self, "_rnn"):
-            self._rnn = {}
-        key = self._key(W) + (int(nx),)
-        hit = self._lookup(self._rnn, key, (W,))
-        if hit is None:
-            hit = self._store(self._rnn, key, (W,), rnn_pack(W, nx))
-        return hit
+        return self._images.get((W,), ("rnn", int(nx)), lambda: rnn_pack(W, nx))
+
+    def _edge(self, W: torch.Tensor, fmt: int, transposed: bool) -> torch.Tensor:
+        def make():
+            lib = _lib.load()
+            src = _req(W, torch.float32, "edge_weights")
+            T, D = W.shape[0], W.shape[1]
+            if transposed:
+                src = W.transpose(1, 2).contiguous()          # (freed after the pack launch, on the stream that read it)
+            packed = _image(lib.ggnn_msg_transform_compact_workspace_bytes(D, T), W)
+            check(lib.ggnn_edge_weights_pack_f32(_ptr(src), T, D, int(fmt), _ptr(packed), _stream()))
+            return packed
+        return self._images.get((W,), ("edge_t" if transposed else "edge", int(fmt)), make)
 
     def edge(self, W: torch.Tensor, fmt: int = GRU_FMT_EXACT) -> torch.Tensor:
         """The compacted transform's stage images of W [T, D, D] in the operand format `fmt` (the launch that consumes them must be
         given the same format)."""
-        lib = _lib.load()
-        key = self._key(W) + (int(fmt),)
-        hit = self._lookup(self._edge, key, (W,))
-        if hit is None:
-            _req(W, torch.float32, "edge_weights")
-            T, D = W.shape[0], W.shape[1]
-            packed = torch.empty(lib.ggnn_msg_transform_compact_workspace_bytes(D, T) // 4, dtype=torch.float32, device=W.device)
-            check(lib.ggnn_edge_weights_pack_f32(_ptr(W), T, D, int(fmt), _ptr(packed), _stream()))
-            hit = self._store(self._edge, key, (W,), packed)
-        return hit
+        return self._edge(W, fmt, False)
+
+    def edge_t(self, W: torch.Tensor, fmt: int = GRU_FMT_EXACT) -> torch.Tensor:
+        """The images of W.transpose(1, 2) -- edge(W.transpose(1, 2).contiguous()) byte for byte -- keyed on W itself: the
+        backward's transform on W^T keeps no transposed copy and leaves no entry of one behind."""
+        return self._edge(W, fmt, True)
+
+
+# the process-wide images: every route of the package (ops.gru, the autograd path, the native steps) shares them
+PACKED = PackedWeights()
 
 
 def gru_packed(x_segs: Sequence[torch.Tensor], h: torch.Tensor, packed: torch.Tensor, bg: torch.Tensor, bc: torch.Tensor,

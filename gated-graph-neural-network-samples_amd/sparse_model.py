@@ -397,13 +397,12 @@ class SparseGGNNChemModel(ChemModel):
             from .variants import compact_rnn_forward
             return compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, cell[0], cell[1], act)[0]
         if compact_attention:
-            from .autograd import _PACKED
             from .variants import compact_sources
             comp = compact_sources(index)
-            Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(edge_weights), edge_weights.shape[0], comp)
+            Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(edge_weights), edge_weights.shape[0], comp)
             xs = list(residual_states) + [ops.gather_segment_sum_attn_compact(Hc, h, index, comp, attn_w, nin, edge_biases, use_avg)]
             if ops.gru_is_fused(h.shape[1]) and len(xs) <= ops.GRU_FUSED_MAX_INPUTS:
-                packed = _PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(xs), h.shape[1])
+                packed = ops.PACKED.gru(cell.gates_kernel, cell.candidate_kernel, len(xs), h.shape[1])
                 return ops.gru_packed(xs, h, packed, cell.gates_bias, cell.candidate_bias, act)
             return ops.gru(xs, h, cell.gates_kernel, cell.gates_bias, cell.candidate_kernel, cell.candidate_bias, act)
         H = ops.msg_transform(h, edge_weights)
@@ -422,7 +421,7 @@ class SparseGGNNChemModel(ChemModel):
         """compute_final_node_representations through ggnn_sparse_propagate_f32 (the loop of :131-218 in C):
         source-compacted transform and pre-packed weight images where the hidden size supports them.
         attention (attention_route()): ggnn_sparse_propagate_attn_f32, always compacted, every product in the exact format."""
-        from .autograd import USE_COMPACT_TRANSFORM, _PACKED
+        from .autograd import USE_COMPACT_TRANSFORM
         D, T = self._kw, self.num_edge_types
         L = len(self.params['layer_timesteps'])
         comp = None
@@ -435,14 +434,14 @@ class SparseGGNNChemModel(ChemModel):
         layers = [self._kernel_layer(l, False) for l in range(L)]
         edge_w = [lay[0].contiguous() for lay in layers]
         edge_fmts = [ops.GRU_FMT_EXACT] * L if attention else list(self.last_edge_formats)
-        edge_packed = [_PACKED.edge(w, edge_fmts[l]) for l, w in enumerate(edge_w)] if comp is not None else None
+        edge_packed = [ops.PACKED.edge(w, edge_fmts[l]) for l, w in enumerate(edge_w)] if comp is not None else None
         edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
         cells = [lay[3] for lay in layers]
         residuals = [self.params['residual_connections'].get(str(l)) or [] for l in range(L)]
         gru_packed = None
         if ops.gru_is_fused(D):
             # (layers with more inputs than the single-launch kernels take run the generic GRU on the raw weights)
-            gru_packed = [_PACKED.gru(c.gates_kernel, c.candidate_kernel, len(residuals[l]) + 1, D, gru_fmts[l])
+            gru_packed = [ops.PACKED.gru(c.gates_kernel, c.candidate_kernel, len(residuals[l]) + 1, D, gru_fmts[l])
                           if len(residuals[l]) + 1 <= ops.GRU_FUSED_MAX_INPUTS else None for l, c in enumerate(cells)]
         outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals,
                                     edge_w, edge_packed, edge_bias,
@@ -456,18 +455,17 @@ class SparseGGNNChemModel(ChemModel):
         """compute_final_node_representations on rnn_route() through ggnn_sparse_propagate_rnn_f32: compacted transform on packed
         edge images, then the gather-fused BasicRNNCell on its packed images (layers the kernel does not take: the segment sum over
         the compact rows and the generic cell on the raw weights).  Every product in the exact format."""
-        from .autograd import _PACKED
         from .variants import compact_sources
         D = self._kw
         L = len(self.params['layer_timesteps'])
         comp = compact_sources(index)
         layers = [self._kernel_layer(l, False) for l in range(L)]
         edge_w = [lay[0].contiguous() for lay in layers]
-        edge_packed = [_PACKED.edge(w) for w in edge_w]
+        edge_packed = [ops.PACKED.edge(w) for w in edge_w]
         edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
         cells = [lay[3] for lay in layers]
         residuals = [self.params['residual_connections'].get(str(l)) or [] for l in range(L)]
-        rnn_packed = [_PACKED.rnn(c.kernel, len(residuals[l]) + 1, D)
+        rnn_packed = [ops.PACKED.rnn(c.kernel, len(residuals[l]) + 1, D)
                       if edge_bias is None and ops.rnn_fused_supported(D, len(residuals[l]) + 1) else None for l, c in enumerate(cells)]
         outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals, edge_w, edge_packed,
                                     edge_bias, None, None, None, None, None, act, edge_fmt=[ops.GRU_FMT_EXACT] * L,

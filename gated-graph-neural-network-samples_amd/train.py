@@ -120,8 +120,9 @@ class TFAdam:
                                           f["v"].data_ptr(), f["partial"].data_ptr(), f["block_var"].data_ptr(),
                                           f["var_first"].data_ptr(), f["active"].data_ptr(), f["nblocks"], float(clip_norm or 0.0),
                                           lr_t, self.b1, self.b2, self.eps, torch.cuda.current_stream().cuda_stream))
-        # The kernel wrote the weights through raw pointers: bump their version counters, which the caches of packed LDS
-        # weight images (ops.PackedWeights) and of transposed weights are keyed on.
+        # The kernel wrote the weights through raw pointers: bump their version counters.  Everything derived from a weight
+        # (stage images, transposes, masked copies, maxima: derived.py) is valid only while the weight sits at the version it
+        # was made from; the version is not part of a key, so the next use replaces the entry.
         bump = getattr(torch.autograd.graph, "increment_version", None)
         if bump is not None:
             for v in self.vars:

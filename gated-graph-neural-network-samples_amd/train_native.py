@@ -286,7 +286,6 @@ def native_panel_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
 
 
 def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False) -> torch.Tensor:
-    from .autograd import _PACKED
     lib = _lib.load()
     # the entry points of the route: whole-block sizes (32 / 64 / 100) or column panels (128 / 192 / 256), one argument list
     if panel:
@@ -358,11 +357,11 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, pane
             for l in range(L):
                 W = model._edge_weight_vars[l].view(T, D, D)
                 if masks:
-                    W = backward._MASKED.get(W, masks[l][0], masks[l][1])
-                edge_packed.append(_PACKED.edge(W))
-                edge_packed_t.append(_PACKED.edge(backward._TRANSPOSED.get(W, (1, 2))))
-                gru_packed.append(_PACKED.gru(cells[l].gates_kernel, cells[l].candidate_kernel, nxs[l], D, gru_fmts[l]))
-                gru_bwd_packed.append(_PACKED.gru_bwd(cells[l].gates_kernel, cells[l].candidate_kernel, nxs[l], D))
+                    W = backward.masked(W, masks[l][0], masks[l][1])
+                edge_packed.append(ops.PACKED.edge(W))
+                edge_packed_t.append(ops.PACKED.edge_t(W))
+                gru_packed.append(ops.PACKED.gru(cells[l].gates_kernel, cells[l].candidate_kernel, nxs[l], D, gru_fmts[l]))
+                gru_bwd_packed.append(ops.PACKED.gru_bwd(cells[l].gates_kernel, cells[l].candidate_kernel, nxs[l], D))
 
         # ---- forward ------------------------------------------------------------------------------------------------------
         M = index.num_messages
@@ -507,7 +506,6 @@ class _DenseWorkspace:
 def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
     """native_train_step for the dense model: two C calls for the propagation and every graph-model gradient, the readout + loss
     per task between them, clip + Adam.  No torch.autograd, and in a steady state no read-back."""
-    from .autograd import _PACKED
     lib = _lib.load()
     p = model.params
     opt = model.optimizer
@@ -530,9 +528,9 @@ def native_dense_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
         cell = model.weights['node_gru']
         has_bias = bool(p['use_edge_bias'])
         bias = model.weights['edge_biases'].reshape(E, D) if has_bias else None
-        edge_packed = _PACKED.dense_edge(W)
-        gru_packed = _PACKED.dense_gru(cell.gates_kernel, cell.candidate_kernel, D)
-        bwd_packed = _PACKED.dense_bwd(W, cell.gates_kernel, cell.candidate_kernel)
+        edge_packed = ops.PACKED.dense_edge(W)
+        gru_packed = ops.PACKED.dense_gru(cell.gates_kernel, cell.candidate_kernel, D)
+        bwd_packed = ops.PACKED.dense_bwd(W, cell.gates_kernel, cell.candidate_kernel)
         nin = model._in_degrees(A_fed, b, v) if has_bias else None
         h0 = h0.reshape(b, v, D).contiguous()
         A = A_fed.contiguous()

@@ -59,9 +59,8 @@ class VariantStepFn(torch.autograd.Function):
         elif compact_attention:
             # attention, GRU cell, a width with a compacted transform: only the active (node, type) rows are transformed, the
             # attention-weighted sum reads them through the compact slot rows (no dense [V, T*D] product, forward or backward)
-            from .autograd import _PACKED
             assert attention_weights is not None and cell_type == 'gru'
-            Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(W), W.shape[0], compact_sources(index))
+            Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(W), W.shape[0], compact_sources(index))
             incoming = ops.gather_segment_sum_attn_compact(Hc, h, index, index._compact, attention_weights, nin, edge_biases, use_avg)
         else:
             H = ops.msg_transform(h, W)
@@ -75,7 +74,7 @@ class VariantStepFn(torch.autograd.Function):
         if cell_type == 'gru':
             save = {} if ctx.hip_backward else None
             if compact_attention and ops.gru_is_fused(D) and len(xs) <= ops.GRU_FUSED_MAX_INPUTS:
-                out = ops.gru_packed(xs, h, _PACKED.gru(cell[0], cell[2], len(xs), D), cell[1], cell[3], activation, save=save)
+                out = ops.gru_packed(xs, h, ops.PACKED.gru(cell[0], cell[2], len(xs), D), cell[1], cell[3], activation, save=save)
             else:
                 out = ops.gru(xs, h, cell[0], cell[1], cell[2], cell[3], activation, save=save)
             if save is not None:
@@ -138,13 +137,12 @@ def compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, resid
     the cell with the segment sum gathered inside (ops.rnn_packed_gather, which hands `incoming` back) where
     ops.rnn_fused_supported takes the layer and it has no edge bias; otherwise the segment sum over the compact rows and ops.rnn.
     The dense [V, T*D] product is never formed."""
-    from .autograd import _PACKED
     comp = compact_sources(index)
     D, nx = h.shape[1], len(residual_states) + 1
-    Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(edge_weights), edge_weights.shape[0], comp)
+    Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(edge_weights), edge_weights.shape[0], comp)
     if edge_biases is None and ops.rnn_fused_supported(D, nx):
         save = {}
-        out = ops.rnn_packed_gather(list(residual_states), h, _PACKED.rnn(W, nx, D), b, Hc, index, comp.gather_row,
+        out = ops.rnn_packed_gather(list(residual_states), h, ops.PACKED.rnn(W, nx, D), b, Hc, index, comp.gather_row,
                                     nin if use_avg else None, activation, save=save)
         return out, save["incoming"]
     incoming = ops.gather_segment_sum_compact(Hc, index, comp, nin, edge_biases, use_avg)
@@ -161,8 +159,7 @@ def compact_sources(index):
 
 def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
     """The timestep's backward on HIP kernels only (see the module docstring)."""
-    from .autograd import _PACKED
-    from .backward import _TRANSPOSED, transform_backward, weight_grad
+    from .backward import transform_backward, transposed, weight_grad
     index = ctx.index
     V, D = h.shape
     T = W.shape[0]
@@ -176,7 +173,7 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
     if ctx.cell_type == 'gru':
         r, u, c = extra[1:4]
         if (ops.gru_bwd_is_fused(D) and nx <= ops.GRU_FUSED_MAX_INPUTS):
-            dpc, dpg, rh, dh, dxs = ops.gru_bwd_fused(g, h, r, u, c, _PACKED.gru_bwd(cell[0], cell[2], nx, D), nin, ctx.use_avg, nx,
+            dpc, dpg, rh, dh, dxs = ops.gru_bwd_fused(g, h, r, u, c, ops.PACKED.gru_bwd(cell[0], cell[2], nx, D), nin, ctx.use_avg, nx,
                                                       ctx.activation)
             dinc, d_res = dxs[-1], dxs[:-1]
             dWc, dbc = weight_grad(xs + [rh], dpc)          # (one ggnn_xty_f32 launch each where the shapes fit, see weight_grad)
@@ -195,7 +192,7 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
         dcell = list(weight_grad(xs + [h], dP))
         dx = torch.empty((V, nx * D), dtype=torch.float32, device=dev)
         dinc = torch.empty_like(h); dh = torch.empty_like(h)
-        ops.bwd_dx(dP, 1, _TRANSPOSED.get(cell[0]), nx * D, True, dx, dinc, nin, ctx.use_avg, dh, False, False, D)
+        ops.bwd_dx(dP, 1, transposed(cell[0]), nx * D, True, dx, dinc, nin, ctx.use_avg, dh, False, False, D)
         d_res = [dx[:, i * D:(i + 1) * D] for i in range(nx - 1)]
     else:                                                              # CudnnCompatibleGRUCell (:105-108)
         r, u, c, hc = extra[1:5]
@@ -204,9 +201,9 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
         dcell = [*weight_grad(xs + [h], dpg), *weight_grad(xs, dpc), *weight_grad([h], dhc)]
         dx = torch.empty((V, nx * D), dtype=torch.float32, device=dev)
         dinc = torch.empty_like(h)
-        ops.bwd_dx(dpc, 1, _TRANSPOSED.get(Wcx), nx * D, False, dx, None, None, False, None, False, False, D)       # dx = dpc Wcx^T
-        ops.bwd_dx(dhc, 1, _TRANSPOSED.get(Wch), 0, False, None, None, None, False, dh, False, True, D)              # dh += dhc Wch^T
-        ops.bwd_dx(dpg, 2, _TRANSPOSED.get(Wg), nx * D, True, dx, dinc, nin, ctx.use_avg, dh, True, True, D)         # += dpg Wg^T
+        ops.bwd_dx(dpc, 1, transposed(Wcx), nx * D, False, dx, None, None, False, None, False, False, D)       # dx = dpc Wcx^T
+        ops.bwd_dx(dhc, 1, transposed(Wch), 0, False, None, None, None, False, dh, False, True, D)              # dh += dhc Wch^T
+        ops.bwd_dx(dpg, 2, transposed(Wg), nx * D, True, dx, dinc, nin, ctx.use_avg, dh, True, True, D)         # += dpg Wg^T
         d_res = [dx[:, i * D:(i + 1) * D] for i in range(nx - 1)]
 
     # ---- aggregation: dinc is dL/d(sum of (attention-weighted) messages + nin @ bias) --------------------------------------------
@@ -217,7 +214,7 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
     if attn is not None and not index.num_messages:                     # no message: nothing attends, no gradient
         dattn = torch.zeros_like(attn)
     elif attn is not None and getattr(ctx, "compact_attention", False):   # :170-196 on the compact rows, recomputed
-        Hc = ops.msg_transform_compact_packed(h, _PACKED.edge(W), T, comp)
+        Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(W), T, comp)
         weights, coef_s, dfac = ops.attn_backward_target_compact(Hc, h, dinc, index, comp, attn, dh)
         del Hc
         dattn = ops.range_sum(dfac, index.type_off)

@@ -35,7 +35,7 @@ for D in (128, 192, 256):
         Wg, Wc = rnd((nx + 1) * D, 2 * D) * 0.1, rnd((nx + 1) * D, D) * 0.1
         nin = torch.randint(0, 3, (V, T), device=dev).float()
         packed = ops.PackedWeights().gru_bwd(Wg, Wc, nx, D)
-        WcT, WgT = backward._TRANSPOSED.get(Wc), backward._TRANSPOSED.get(Wg)
+        WcT, WgT = backward.transposed(Wc), backward.transposed(Wg)
         dpc, dh, rh, dinc = (torch.empty_like(h) for _ in range(4))
         dpg = torch.empty((V, 2 * D), device=dev)
         dx = torch.empty((V, nx * D), device=dev)
