@@ -106,6 +106,14 @@ SYMBOLS = {
     "ggnn_rnn_packed_gather_f32": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                            c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                            c_void_p]),
+    # ... and its backward in one launch
+    "ggnn_rnn_bwd_fused_supported": (c_int, [c_int, c_int]),
+    "ggnn_rnn_bwd_packed_bytes": (c_size_t, [c_int, c_int]),
+    "ggnn_rnn_bwd_pack_weights_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_rnn_bwd_fused_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, c_void_p]),
+    "ggnn_rnn_bwd_fused_gather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p),
+                                              c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ggnn_sparse_propagate_rnn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64),
                                               c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                               POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
@@ -220,6 +228,17 @@ SYMBOLS = {
                                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)] + [c_void_p] * 8 +
                                                    [POINTER(c_void_p)] * 4 + [c_int] + [POINTER(c_void_p)] * 6 +
                                                    [c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the same step for the BasicRNNCell on the compacted route (params['compact_rnn'] == 'native')
+    "ggnn_sparse_rnn_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64, c_int]),
+    "ggnn_sparse_rnn_train_forward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                                  c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                                  POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_size_t,
+                                                  POINTER(c_int64), c_void_p]),
+    "ggnn_sparse_rnn_train_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int64), c_void_p, c_int, c_int,
+                                                   POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_int,
+                                                   POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p, POINTER(c_void_p),
+                                                   c_void_p, c_size_t, c_void_p, c_void_p]),
     "ggnn_dropout_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_float, c_int64, c_int, c_void_p]),
     "ggnn_gcn_fused_supported": (c_int, [c_int]),
     "ggnn_gcn_image_bytes": (c_size_t, [c_int]),

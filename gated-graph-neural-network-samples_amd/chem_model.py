@@ -421,7 +421,8 @@ class ChemModel(object):
         with the native step the host has slack, packing a batch inline costs 0.3 ms of it, and a second thread only takes
         the interpreter lock away from the launches (5.8 vs 6.05 ms per step, tools/bench_extra.py epoch)."""
         from . import train_native
-        return not (train_native.model_eligible(self) or train_native.attn_model_eligible(self) or train_native.panel_model_eligible(self))
+        return not (train_native.model_eligible(self) or train_native.attn_model_eligible(self) or train_native.panel_model_eligible(self)
+                    or train_native.rnn_model_eligible(self))
 
     def _epoch_batches(self, data, is_training: bool):
         """The epoch's batches.  In a training epoch with params['threaded_batches'] ('auto': threaded_batches_default) a producer thread

@@ -30,6 +30,13 @@
 // and the row-gathered edge-weight product goes through 128-column views of h and dHc whose blocks one small launch adds into the
 // [T, D, D] destination.  The images come from ggnn_sparse_train_panel_prepare_f32 (ggnn_train_panel.hip).
 //
+// With the BasicRNNCell (graph_rnn_cell = RNN, :109-110) on the compacted route (params['compact_rnn'] == 'native') the same two
+// sequences run as ggnn_sparse_rnn_train_forward_f32 / ggnn_sparse_rnn_train_backward_f32: the drivers take the cell as an optional
+// struct (RnnForward / RnnBackward) and launch what they always launched without it.  A timestep of the forward is the compacted
+// transform + ggnn_rnn_packed_gather_f32 keeping `incoming`; of the backward ggnn_rnn_bwd_fused_f32 (its gather form when a node sum
+// is pending) and ONE weight-gradient product, dW += [x.. | incoming | h]^T dP with the bias gradient, where the GRU has two.  The
+// layout drops r / u / c / r*h / dpg; dpc holds dP.  The images come per layer from the single-kind packers (no one-launch prepare).
+//
 // Cross-stream hazards: everything a side-stream product reads (dpc, dpg, r*h, incoming, states, dHc) has its own buffer per
 // timestep, so the main stream never waits for the side stream inside a step; the call ends with the main stream waiting for the
 // side stream's last product, which orders the next step's forward (it reuses the workspace) behind them.
@@ -68,8 +75,9 @@ struct TrainLayout {
 };
 
 // M > 0: the layout of the attention sequences (M messages); M == 0: the default model's, unchanged; panel: the default model's at the
-// column-panel sizes (everything the side stream's products need beyond the per-timestep buffers follows them)
-TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 0, bool panel = false) {
+// column-panel sizes (everything the side stream's products need beyond the per-timestep buffers follows them); rnn: the BasicRNNCell's
+// -- no r / u / c / r*h / dpg, and dpc holds dP = dL/d(pre-activation), the one dY of the cell's weight-gradient product
+TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 0, bool panel = false, bool rnn = false) {
     TrainLayout L{};
     L.steps = steps;
     // per-timestep buffers follow each other WITHOUT padding (V*D*4 is a multiple of 16): the buffers of consecutive timesteps then
@@ -80,10 +88,11 @@ TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 
     auto take = [&](size_t bytes) { const size_t at = p; p += al256(bytes); return at; };
     L.Hc = take(L.rd);
     L.state = take(L.vd * (steps + 1));                  // slot 0: a copy of h0; slot k+1: the state after timestep k
-    L.r = take(L.vd * steps); L.u = take(L.vd * steps); L.c = take(L.vd * steps);
+    const size_t gates = rnn ? 0 : L.vd * steps;         // (a buffer of 0 bytes takes no room)
+    L.r = take(gates); L.u = take(gates); L.c = take(gates);
     L.inc = take(L.vd * steps);
     L.counters = take((size_t)steps * sizeof(int32_t));
-    L.dpc = take(L.vd * steps); L.rh = take(L.vd * steps); L.dh = take(L.vd * steps); L.dpg = take(2 * L.vd * steps);
+    L.dpc = take(L.vd * steps); L.rh = take(gates); L.dh = take(L.vd * steps); L.dpg = take(2 * gates);
     L.dx = take(L.vd * steps * kMaxNx);
     L.dHc = take(L.rd * steps); L.Z = take(L.rd);
     L.md = al256((size_t)M * sizeof(float));
@@ -98,7 +107,7 @@ TrainLayout train_layout(int V, int D, int T, int64_t R, int steps, int64_t M = 
         L.bsum = take((size_t)2 * D * sizeof(float));
         L.xty_bytes = ggnn_xty_workspace_bytes(V > R ? V : (int)R, kEdgeBlock, kEdgeBlock, T);
     } else {
-        L.xty_bytes = ggnn_xty_workspace_bytes((V > R ? V : (int)R) * (steps > 1 ? steps : 1), 4 * D, 2 * D, T);
+        L.xty_bytes = ggnn_xty_workspace_bytes((V > R ? V : (int)R) * (steps > 1 ? steps : 1), 4 * D, rnn ? D : 2 * D, T);
     }
     L.xty = take(L.xty_bytes);
     L.total = p + 256;
@@ -267,7 +276,32 @@ struct AttnBackward {
     int64_t M;
 };
 
+// the BasicRNNCell form (graph_rnn_cell = RNN on the compacted route, params['compact_rnn'] == 'native'): the cell's arguments in
+// place of the GRU's.  A timestep of the forward is the compacted transform + ggnn_rnn_packed_gather_f32 (save_incoming), of the
+// backward ggnn_rnn_bwd_fused[_gather]_f32 + ONE weight-gradient product dW += [x.. | incoming | h]^T dP with the bias gradient.
+struct RnnForward {
+    const float* const* packed;            // per layer: ggnn_rnn_pack_weights_f32's images
+    const float* const* b;                 // per layer: bias [D]
+    int64_t M;                             // messages: the length of gather_row_c
+};
+struct RnnBackward {
+    const float* const* bwd_packed;        // per layer: ggnn_rnn_bwd_pack_weights_f32's images
+    float* const* g_W;                     // per layer: gradient views of W [(nx+1)D, D] and b [D]
+    float* const* g_b;
+};
+
 struct LayerPlan { int first_step, steps, nres; int res[kMaxNx]; };
+
+// every layer of the plan is one the fused RNN cell takes (checked before anything is enqueued)
+int rnn_layers_supported(int D, int num_layers, const LayerPlan* plan) {
+    if (!ggnn_msg_transform_compact_supported(D))
+        return fail(GGNN_E_UNSUPPORTED, "native training step, RNN cell: hidden size %d has no compacted transform", D);
+    for (int l = 0; l < num_layers; ++l)
+        if (!ggnn_rnn_fused_supported(D, plan[l].nres + 1))
+            return fail(GGNN_E_UNSUPPORTED, "native training step, RNN cell: layer %d (D=%d, nx=%d) is outside ggnn_rnn_fused_supported", l, D,
+                        plan[l].nres + 1);
+    return GGNN_OK;
+}
 
 int plan_layers(int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx, LayerPlan* plan,
                 int* total_steps) {
@@ -350,35 +384,42 @@ static int train_forward(
         const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
         const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* bg,
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
-        int64_t* final_state_offset, const AttnForward* at, const TrainRoute& route, ggnn_stream_t stream) {
+        int64_t* final_state_offset, const AttnForward* at, const RnnForward* rn, const TrainRoute& route, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(h0 && row_ptr && gather_row_c && pair_node && type_row_off && ws && final_state_offset, "null pointer");
-    GGNN_CHECK_ARG(edge_packed && bg && bc && gru_packed, "weights missing");
+    GGNN_CHECK_ARG(edge_packed && (rn ? (rn->packed && rn->b && !at && !route.panel) : (bg && bc && gru_packed)), "weights missing");
     GGNN_CHECK_ARG((reinterpret_cast<size_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
     if (route.panel) {
         if (!route.takes(D)) return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: hidden size %d is not 128 / 192 / 256", D);
         GGNN_CHECK_ARG(!at, "the panel route has no attention form");
         GGNN_CHECK_ARG(!use_avg || nin, "nin is required for mean aggregation");
-    } else if (ggnn_gru_is_fused(D) != 1 || !ggnn_msg_transform_compact_supported(D))
+    } else if (!rn && (ggnn_gru_is_fused(D) != 1 || !ggnn_msg_transform_compact_supported(D)))
         return fail(GGNN_E_UNSUPPORTED, "native training step: hidden size %d has no gather-fused GRU / compacted transform", D);
     LayerPlan plan[kMaxLayers];
     int steps = 0;
     if (int rc = plan_layers(num_layers, layer_timesteps, res_ptr, res_idx, plan, &steps)) return rc;
+    if (rn) { if (int rc = rnn_layers_supported(D, num_layers, plan)) return rc; }
     const int64_t R = type_row_off[T];
     GGNN_CHECK_ARG(R > 0, "no messages in the batch");
+    GGNN_CHECK_ARG(!rn || ((!use_avg || nin) && rn->M > 0 && rn->M < (1LL << 31)), "RNN cell: nin missing for mean aggregation, or bad message count");
     GGNN_CHECK_ARG(!at || (at->slot_pair && at->factors && at->M > 0 && at->M < (1LL << 31) && (!use_avg || nin)), "attention arguments missing");
     if (route.panel) {            // (the limits of the launches below, checked before anything is enqueued)
         GGNN_CHECK_ARG(T <= 64 && R < (1LL << 31), "bad sizes T=%d, %lld compact rows", T, (long long)R);
         if ((unsigned long long)V * 2 * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30) || (long long)V * steps >= (1LL << 31))
             return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: V*2D and rows*D must be < 2^30 (V=%d, D=%d, rows=%lld)", V, D, (long long)R);
     }
-    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel);
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel, rn != nullptr);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
+    if (rn) {
+        if ((unsigned long long)V * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30))
+            return fail(GGNN_E_UNSUPPORTED, "native training step, RNN cell: V*D and rows*D must be < 2^30 (V=%d, D=%d, rows=%lld)", V, D, (long long)R);
+        for (int l = 0; l < num_layers; ++l) GGNN_CHECK_ARG(edge_packed[l] && rn->packed[l] && rn->b[l], "layer %d: weights missing", l);
+    }
     char* base = static_cast<char*>(ws);
     float* Hc = reinterpret_cast<float*>(base + L.Hc);
     int32_t* counters = reinterpret_cast<int32_t*>(base + L.counters);
     hipStream_t st = (hipStream_t)stream;
-    GGNN_CHECK_HIP(hipMemsetAsync(counters, 0, (size_t)steps * sizeof(int32_t), st));
+    if (!rn) GGNN_CHECK_HIP(hipMemsetAsync(counters, 0, (size_t)steps * sizeof(int32_t), st));     // (the GRU's tile counters)
     auto buf = [&](size_t off, int step) { return reinterpret_cast<float*>(base + off + (size_t)step * L.vd); };
     const float* states[kMaxLayers + 1];
     states[0] = h0;
@@ -391,14 +432,19 @@ static int train_forward(
         for (int i = 0; i < P.nres; ++i) xs[i] = states[P.res[i]];              // :140-145
         const int nx = P.nres + 1;
         const float* cur = states[l];                                           // :152
-        GGNN_CHECK_ARG(edge_packed[l] && bg[l] && bc[l] && gru_packed[l], "layer %d: weights missing", l);
+        GGNN_CHECK_ARG(rn || (edge_packed[l] && bg[l] && bc[l] && gru_packed[l]), "layer %d: weights missing", l);
         GGNN_CHECK_ARG(!at || at->factors[l], "layer %d: attention factors missing", l);
         for (int s = 0; s < P.steps; ++s) {                                     // :153
             const int k = P.first_step + s;
             if (int rc = ggnn_msg_transform_compact_f32(cur, nullptr, pair_node, type_row_off, Hc, const_cast<float*>(edge_packed[l]),
                                                         edge_img_bytes, V, D, T, GGNN_GRU_FMT_BF16X3, stream)) return rc;
             float* out = buf(L.state, k + 1);
-            if (at) {
+            if (rn) {
+                // :198-216 with the BasicRNNCell: the segment sum gathered inside the cell, `incoming` kept for dW -- the launch
+                // of the autograd route's training forward (variants.compact_rnn_forward)
+                if (int rc = ggnn_rnn_packed_gather_f32(xs, nx, cur, rn->packed[l], rn->b[l], out, Hc, R, row_ptr, gather_row_c, rn->M,
+                                                        use_avg ? nin : nullptr, T, use_avg ? 1 : 0, buf(L.inc, k), V, D, act, stream)) return rc;
+            } else if (at) {
                 // :170-196 the attention-weighted sum into this timestep's `incoming`, then the GRU on it (every product exact:
                 // the two-piece f16 range proof does not cover attention-weighted sums)
                 if (int rc = ggnn_gather_segment_sum_attn_compact_f32(Hc, cur, row_ptr, at->slot_pair, gather_row_c, at->factors[l], nin,
@@ -433,24 +479,27 @@ static int train_backward(
         const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
         const float* const* edge_packed_t, const float* const* gru_bwd_packed, int act,
         float* const* g_edge, float* const* g_Wg, float* const* g_bg, float* const* g_Wc, float* const* g_bc,
-        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, const AttnBackward* at, const TrainRoute& route,
-        ggnn_stream_t stream, ggnn_stream_t side_stream) {
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, const AttnBackward* at, const RnnBackward* rn,
+        const TrainRoute& route, ggnn_stream_t stream, ggnn_stream_t side_stream) {
     GGNN_CHECK_ARG(V > 0 && D > 0 && D % 4 == 0 && T > 0 && T <= 64, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(h0 && pair_node && type_row_off && (at || (rows_rp && rows_gather)) && node_rp && node_order && identity_rows && d_final && ws,
                    "null pointer");
     GGNN_CHECK_ARG(!at || (at->row_ptr && at->slot_pair && at->slot_row && at->msg_perm && at->msg_type_off && at->src_node_ptr && at->src_dst &&
                            at->src_msg && at->src_row && at->edge_packed && at->factors && at->g_attn && at->M > 0 && at->M < (1LL << 31)),
                    "attention arguments missing");
-    GGNN_CHECK_ARG(edge_packed_t && gru_bwd_packed && g_edge && g_Wg && g_bg && g_Wc && g_bc && d_state_ws, "weights / gradient buffers missing");
+    GGNN_CHECK_ARG(edge_packed_t && g_edge && d_state_ws && (rn ? (rn->bwd_packed && rn->g_W && rn->g_b && !at && !route.panel)
+                                                                 : (gru_bwd_packed && g_Wg && g_bg && g_Wc && g_bc)),
+                   "weights / gradient buffers missing");
     GGNN_CHECK_ARG(!use_avg || nin, "nin is required for mean aggregation");
     GGNN_CHECK_ARG((reinterpret_cast<size_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-    if (!route.takes(D))
+    if (!rn && !route.takes(D))
         return fail(GGNN_E_UNSUPPORTED, route.panel ? "native training step, panel route: hidden size %d is not 128 / 192 / 256"
                                                     : "native training step: no whole-block fused GRU backward for hidden size %d", D);
     GGNN_CHECK_ARG(!route.panel || !at, "the panel route has no attention form");
     LayerPlan plan[kMaxLayers];
     int steps = 0;
     if (int rc = plan_layers(num_layers, layer_timesteps, res_ptr, res_idx, plan, &steps)) return rc;
+    if (rn) { if (int rc = rnn_layers_supported(D, num_layers, plan)) return rc; }
     const int64_t R64 = type_row_off[T];
     GGNN_CHECK_ARG(R64 > 0 && R64 < (1LL << 31), "bad compact row count");
     const int R = (int)R64;
@@ -458,8 +507,14 @@ static int train_backward(
         if ((unsigned long long)V * 2 * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30) || (long long)V * steps >= (1LL << 31))
             return fail(GGNN_E_UNSUPPORTED, "native training step, panel route: V*2D and rows*D must be < 2^30 (V=%d, D=%d, rows=%d)", V, D, R);
     }
-    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel);
+    const TrainLayout L = train_layout(V, D, T, R, steps, at ? at->M : 0, route.panel, rn != nullptr);
     if (ws_bytes < L.total) return fail(GGNN_E_WORKSPACE, "training workspace too small: %zu < %zu", ws_bytes, L.total);
+    if (rn) {                     // (the limits of the cell's launches, checked before anything is enqueued)
+        if ((unsigned long long)V * D >= (1ULL << 30) || (unsigned long long)R * D >= (1ULL << 30))
+            return fail(GGNN_E_UNSUPPORTED, "native training step, RNN cell: V*D and rows*D must be < 2^30 (V=%d, D=%d, rows=%d)", V, D, R);
+        for (int l = 0; l < num_layers; ++l)
+            GGNN_CHECK_ARG(edge_packed_t[l] && rn->bwd_packed[l] && g_edge[l] && rn->g_W[l] && rn->g_b[l], "layer %d: pointers missing", l);
+    }
     char* base = static_cast<char*>(ws);
     hipStream_t st = (hipStream_t)stream, side = side_stream ? (hipStream_t)side_stream : (hipStream_t)stream;
     auto buf = [&](size_t off, int step) { return reinterpret_cast<float*>(base + off + (size_t)step * L.vd); };
@@ -497,7 +552,7 @@ static int train_backward(
         const LayerPlan& P = plan[l];
         const int nx = P.nres + 1;
         GGNN_CHECK_ARG(has[l + 1], "no gradient reaches the output of layer %d", l);
-        GGNN_CHECK_ARG(edge_packed_t[l] && gru_bwd_packed[l] && g_edge[l] && g_Wg[l] && g_bg[l] && g_Wc[l] && g_bc[l], "layer %d: pointers missing", l);
+        GGNN_CHECK_ARG(rn || (edge_packed_t[l] && gru_bwd_packed[l] && g_edge[l] && g_Wg[l] && g_bg[l] && g_Wc[l] && g_bc[l]), "layer %d: pointers missing", l);
         GGNN_CHECK_ARG(!at || (at->edge_packed[l] && at->factors[l] && at->g_attn[l]), "layer %d: attention pointers missing", l);
         const float* g = dstate[l + 1];
         for (int s = P.steps - 1; s >= 0; --s) {
@@ -520,7 +575,17 @@ static int train_backward(
             dxp[nx - 1] = dinc;
             float* dpc = buf(L.dpc, k); float* rh = buf(L.rh, k);
             float* dpg = reinterpret_cast<float*>(base + L.dpg + (size_t)k * 2 * L.vd);
-            if (z_pending) {
+            if (rn) {
+                // the whole BasicRNNCell backward of the timestep in one launch; dpc holds dP.  A pending node sum is taken on load
+                if (z_pending) {
+                    if (int rc = ggnn_rnn_bwd_fused_gather_f32(g, Z, node_heads, R, buf(L.state, k + 1), rn->bwd_packed[l], dpc, dxp, dh_dst,
+                                                               nin, T, use_avg ? 1 : 0, nx, V, D, act, stream)) return rc;
+                    z_pending = false;
+                } else {
+                    if (int rc = ggnn_rnn_bwd_fused_f32(g, buf(L.state, k + 1), rn->bwd_packed[l], dpc, dxp, dh_dst, nin, T, use_avg ? 1 : 0,
+                                                        nx, V, D, act, stream)) return rc;
+                }
+            } else if (z_pending) {
                 if (int rc = ggnn_gru_bwd_fused_gather_f32(g, Z, node_heads, h_in, buf(L.r, k), buf(L.u, k), buf(L.c, k),
                                                            const_cast<float*>(gru_bwd_packed[l]), dpc, dpg, rh, dh_dst, dxp, nin, T,
                                                            use_avg ? 1 : 0, nx, V, D, act, stream)) return rc;
@@ -534,6 +599,7 @@ static int train_backward(
             if (dh_direct) has[l] = true;
 
             // ---- GRU weight gradients, side stream: dWc += [x.. | incoming | r*h]^T dpc, dWg += [x.. | incoming | h]^T dpg
+            // (RNN cell: the one product dW += [x.. | incoming | h]^T dP, the bias gradient from its ones row)
             // A layer WITHOUT residual inputs runs them once for all its timesteps: incoming, r*h, dpc, dpg and the input states of
             // consecutive timesteps are consecutive [V,D] ([V,2D]) buffers, i.e. one matrix of S*V rows each -- one product
             // instead of S, and its fixed part (prologue, partial store, reduction launch: ~20 us of ~100) paid once.
@@ -568,24 +634,28 @@ static int train_backward(
                     if (int rc = order_after(side, st)) return rc;
                     const int k0 = P.first_step;
                     int32_t row_off_m[2] = {0, V * P.steps};
-                    const float* X[2] = {buf(L.inc, k0), buf(L.rh, k0)}; int32_t ldx[2] = {D, D};
-                    if (int rc = ggnn_xty_acc_f32(X, 2, D, ldx, nullptr, buf(L.dpc, k0), D, g_Wc[l], g_bc[l], 1, 2 * D, D, 1, row_off_m, 1,
-                                                  xty_ws, xty_ws_bytes, side)) return rc;
+                    const float* X[2] = {buf(L.inc, k0), rn ? buf(L.state, k0) : buf(L.rh, k0)}; int32_t ldx[2] = {D, D};
+                    if (int rc = ggnn_xty_acc_f32(X, 2, D, ldx, nullptr, buf(L.dpc, k0), D, rn ? rn->g_W[l] : g_Wc[l], rn ? rn->g_b[l] : g_bc[l], 1,
+                                                  2 * D, D, 1, row_off_m, 1, xty_ws, xty_ws_bytes, side)) return rc;
                     X[1] = buf(L.state, k0);
-                    if (int rc = ggnn_xty_acc_f32(X, 2, D, ldx, nullptr, reinterpret_cast<float*>(base + L.dpg + (size_t)k0 * 2 * L.vd), 2 * D,
-                                                  g_Wg[l], g_bg[l], 1, 2 * D, 2 * D, 1, row_off_m, 1, xty_ws, xty_ws_bytes, side)) return rc;
+                    if (!rn) {                              // (the RNN cell has the one product)
+                        if (int rc = ggnn_xty_acc_f32(X, 2, D, ldx, nullptr, reinterpret_cast<float*>(base + L.dpg + (size_t)k0 * 2 * L.vd), 2 * D,
+                                                      g_Wg[l], g_bg[l], 1, 2 * D, 2 * D, 1, row_off_m, 1, xty_ws, xty_ws_bytes, side)) return rc;
+                    }
                 }
             } else {
                 if (int rc = order_after(side, st)) return rc;
                 const float* X[4]; int32_t ldx[4];
                 for (int i = 0; i < P.nres; ++i) { X[i] = states[P.res[i]]; ldx[i] = D; }
                 X[nx - 1] = buf(L.inc, k); ldx[nx - 1] = D;
-                X[nx] = rh; ldx[nx] = D;
-                if (int rc = ggnn_xty_acc_f32(X, nx + 1, D, ldx, nullptr, dpc, D, g_Wc[l], g_bc[l], 1, (nx + 1) * D, D, 1, row_off_v, 1,
-                                              xty_ws, xty_ws_bytes, side)) return rc;
+                X[nx] = rn ? h_in : rh; ldx[nx] = D;
+                if (int rc = ggnn_xty_acc_f32(X, nx + 1, D, ldx, nullptr, dpc, D, rn ? rn->g_W[l] : g_Wc[l], rn ? rn->g_b[l] : g_bc[l], 1,
+                                              (nx + 1) * D, D, 1, row_off_v, 1, xty_ws, xty_ws_bytes, side)) return rc;
                 X[nx] = h_in;
-                if (int rc = ggnn_xty_acc_f32(X, nx + 1, D, ldx, nullptr, dpg, 2 * D, g_Wg[l], g_bg[l], 1, (nx + 1) * D, 2 * D, 1, row_off_v, 1,
-                                              xty_ws, xty_ws_bytes, side)) return rc;
+                if (!rn) {
+                    if (int rc = ggnn_xty_acc_f32(X, nx + 1, D, ldx, nullptr, dpg, 2 * D, g_Wg[l], g_bg[l], 1, (nx + 1) * D, 2 * D, 1, row_off_v, 1,
+                                                  xty_ws, xty_ws_bytes, side)) return rc;
+                }
             }
 
             // ---- back through the segment sum and the compacted transform (main stream)
@@ -658,7 +728,7 @@ static int train_backward(
             g = dh_dst;
         }
     }
-    // every deferred node sum was consumed by the GRU backward of the timestep before it (the only step that defers without a
+    // every deferred node sum was consumed by the GRU (RNN cell) backward of the timestep before it (the only step that defers without a
     // consumer would be the very first one, which runs no transform): a pending one here means a gradient was dropped
     GGNN_CHECK_ARG(!z_pending, "internal: a deferred node sum of the transform backward was never added (fuse_node_sum invariant)");
     return order_after(st, side);          // the caller's next launches (optimizer, next forward) see every product
@@ -671,8 +741,8 @@ extern "C" int ggnn_sparse_train_forward_f32(
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
         int64_t* final_state_offset, ggnn_stream_t stream) {
     return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
-                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, TrainRoute{false},
-                         stream);
+                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, nullptr,
+                         TrainRoute{false}, stream);
 }
 
 extern "C" int ggnn_sparse_train_backward_f32(
@@ -685,7 +755,7 @@ extern "C" int ggnn_sparse_train_backward_f32(
         float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
     return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
                           rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act,
-                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, TrainRoute{false}, stream, side_stream);
+                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, nullptr, TrainRoute{false}, stream, side_stream);
 }
 
 // ---- the default model's two sequences at the column-panel sizes 128 / 192 / 256 (see the header comment) ---------------------------
@@ -702,8 +772,8 @@ extern "C" int ggnn_sparse_train_panel_forward_f32(
         const float* const* bc, const float* const* gru_packed, const int32_t* gru_fmt, int act, void* ws, size_t ws_bytes,
         int64_t* final_state_offset, ggnn_stream_t stream) {
     return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
-                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, TrainRoute{true},
-                         stream);
+                         res_idx, edge_packed, bg, bc, gru_packed, gru_fmt, act, ws, ws_bytes, final_state_offset, nullptr, nullptr,
+                         TrainRoute{true}, stream);
 }
 
 extern "C" int ggnn_sparse_train_panel_backward_f32(
@@ -716,7 +786,7 @@ extern "C" int ggnn_sparse_train_panel_backward_f32(
         float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
     return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
                           rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act,
-                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, TrainRoute{true}, stream, side_stream);
+                          g_edge, g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, nullptr, nullptr, TrainRoute{true}, stream, side_stream);
 }
 
 // ---- the same two sequences with propagation attention on the compacted route (see the header comment) -----------------------------
@@ -730,7 +800,7 @@ extern "C" int ggnn_sparse_attn_train_forward_f32(
     GGNN_CHECK_ARG(M > 0 && M < (1LL << 31), "bad message count %lld", (long long)M);
     const AttnForward at{slot_pair, attn_factors, M};
     return train_forward(h0, V, D, T, row_ptr, slot_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
-                         res_idx, edge_packed, bg, bc, gru_packed, nullptr, act, ws, ws_bytes, final_state_offset, &at, TrainRoute{false}, stream);
+                         res_idx, edge_packed, bg, bc, gru_packed, nullptr, act, ws, ws_bytes, final_state_offset, &at, nullptr, TrainRoute{false}, stream);
 }
 
 extern "C" int ggnn_sparse_attn_train_backward_f32(
@@ -752,5 +822,40 @@ extern "C" int ggnn_sparse_attn_train_backward_f32(
                           edge_packed, attn_factors, g_attn, M};
     return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, nullptr,
                           nullptr, nullptr, node_rp, node_order, node_heads, identity_rows, edge_packed_t, gru_bwd_packed, act, g_edge,
-                          g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, &at, TrainRoute{false}, stream, side_stream);
+                          g_Wg, g_bg, g_Wc, g_bc, d_final, d_state_ws, ws, ws_bytes, &at, nullptr, TrainRoute{false}, stream, side_stream);
+}
+
+// ---- the same two sequences for the BasicRNNCell on the compacted route (graph_rnn_cell = RNN; see RnnForward / RnnBackward) ---------
+extern "C" size_t ggnn_sparse_rnn_train_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps) {
+    if (V <= 0 || T <= 0 || T > 64 || total_steps <= 0 || compact_rows < 0 || compact_rows >= (1LL << 31)) return 0;
+    if (!ggnn_rnn_fused_supported(D, 1) || !ggnn_msg_transform_compact_supported(D)) return 0;
+    return train_layout(V, D, T, compact_rows, total_steps, 0, false, true).total;
+}
+
+extern "C" int ggnn_sparse_rnn_train_forward_f32(
+        const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr, const int32_t* gather_row_c, const int32_t* pair_node,
+        const int64_t* type_row_off, const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+        const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed, const float* const* rnn_b,
+        const float* const* rnn_packed, int act, void* ws, size_t ws_bytes, int64_t* final_state_offset, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(rnn_b && rnn_packed, "null pointer (cell weights)");
+    const RnnForward rn{rnn_packed, rnn_b, M};
+    return train_forward(h0, V, D, T, row_ptr, gather_row_c, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+                         res_idx, edge_packed, nullptr, nullptr, nullptr, nullptr, act, ws, ws_bytes, final_state_offset, nullptr, &rn,
+                         TrainRoute{false}, stream);
+}
+
+extern "C" int ggnn_sparse_rnn_train_backward_f32(
+        const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off, const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const int32_t* rows_rp, const int32_t* rows_gather, const int32_t* rows_heads,
+        const int32_t* node_rp, const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+        const float* const* edge_packed_t, const float* const* rnn_bwd_packed, int act,
+        float* const* g_edge, float* const* g_W, float* const* g_b,
+        float* d_final, float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream) {
+    GGNN_CHECK_ARG(rnn_bwd_packed && g_W && g_b, "null pointer (cell weights / gradient views)");
+    const RnnBackward rn{rnn_bwd_packed, g_W, g_b};
+    return train_backward(h0, V, D, T, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr, res_idx, rows_rp,
+                          rows_gather, rows_heads, node_rp, node_order, node_heads, identity_rows, edge_packed_t, nullptr, act,
+                          g_edge, nullptr, nullptr, nullptr, nullptr, d_final, d_state_ws, ws, ws_bytes, nullptr, &rn, TrainRoute{false},
+                          stream, side_stream);
 }

@@ -1070,6 +1070,11 @@ class PackedWeights:
         version.  (nx, D) must be in the supported set: rnn_fused_supported."""
         return self._images.get((W,), ("rnn", int(nx)), lambda: rnn_pack(W, nx))
 
+    def rnn_bwd(self, W: torch.Tensor, nx: int, D: int) -> torch.Tensor:
+        """The nx + 1 exact bf16x3 images of W_s^T of the fused BasicRNNCell backward (ggnn_rnn_bwd_pack_weights_f32), once per
+        weight version.  (nx, D) must be in the supported set: rnn_bwd_fused_supported."""
+        return self._images.get((W,), ("rnn_bwd", int(nx)), lambda: rnn_bwd_pack(W, nx))
+
     def _edge(self, W: torch.Tensor, fmt: int, transposed: bool) -> torch.Tensor:
         def make():
             lib = _lib.load()
@@ -1316,6 +1321,49 @@ def rnn_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, pa
         gather.numel(), None if nin is None else _ptr(nin), index.num_edge_types, 0 if nin is None else 1, _ptr(inc), V, D, act,
         _stream()))
     return out
+
+
+def rnn_bwd_fused_supported(D: int, nx: int) -> bool:
+    """True when the BasicRNNCell backward with nx concatenated inputs has the single fused launch at width D
+    (ggnn_rnn_bwd_fused_supported: the forward's set, rnn_fused_supported)."""
+    return bool(_lib.load().ggnn_rnn_bwd_fused_supported(int(D), int(nx)))
+
+
+def rnn_bwd_pack(W: torch.Tensor, nx: int) -> torch.Tensor:
+    """W [(nx+1) D, D] -> the nx + 1 images of W_s^T of ggnn_rnn_bwd_fused_f32 (PackedWeights.rnn_bwd caches them per weight version)."""
+    lib = _lib.load()
+    _req(W, torch.float32, "W")
+    if W.dim() != 2 or W.shape[0] != (nx + 1) * W.shape[1]:
+        raise ValueError("W must be [(nx+1)*D, D]")
+    D = W.shape[1]
+    packed = torch.empty(max(lib.ggnn_rnn_bwd_packed_bytes(D, nx) // 4, 4), dtype=torch.float32, device=W.device)
+    check(lib.ggnn_rnn_bwd_pack_weights_f32(_ptr(W), nx, D, _ptr(packed), _stream()))
+    return packed
+
+
+def rnn_bwd_fused(g: torch.Tensor, out: torch.Tensor, packed: torch.Tensor, nin: Optional[torch.Tensor], use_avg: bool, nx: int,
+                  activation: str, gather=None):
+    """The BasicRNNCell backward of one timestep in one launch (ggnn_rnn_bwd_fused_f32) -> (dP, dh, [dx_0 .. dx_{nx-1}]); the last
+    dx is d_incoming (already divided by the in-degree for mean aggregation).  gather = (rows, heads): the incoming gradient is
+    g[v] + the sum of the rows of `rows` named by the slot-head record heads[v] (ggnn_rnn_bwd_fused_gather_f32)."""
+    lib = _lib.load()
+    _req(g, torch.float32, "g"); _req(out, torch.float32, "out"); _req(packed, torch.float32, "packed")
+    V, D = out.shape
+    T = nin.shape[1] if nin is not None else 1
+    act = ACT_IDS[activation.lower()]
+    dP = torch.empty_like(out); dh = torch.empty_like(out)
+    dx = [torch.empty_like(out) for _ in range(nx)]
+    dxp = (ctypes.c_void_p * max(nx, 1))(*[t.data_ptr() for t in dx])
+    if gather is not None:
+        rows, heads = gather
+        _req(rows, torch.float32, "rows"); _req(heads, torch.int32, "heads")
+        _launch("rnn_bwd_fused_gather[nx=%d]" % nx, lambda: lib.ggnn_rnn_bwd_fused_gather_f32(
+            _ptr(g), _ptr(rows), _ptr(heads), rows.shape[0], _ptr(out), _ptr(packed), _ptr(dP), dxp, _ptr(dh), _ptr(nin), T,
+            1 if use_avg else 0, nx, V, D, act, _stream()))
+    else:
+        _launch("rnn_bwd_fused[nx=%d]" % nx, lambda: lib.ggnn_rnn_bwd_fused_f32(
+            _ptr(g), _ptr(out), _ptr(packed), _ptr(dP), dxp, _ptr(dh), _ptr(nin), T, 1 if use_avg else 0, nx, V, D, act, _stream()))
+    return dP, dh, dx
 
 
 def gated_readout(last_h: torch.Tensor, h0: torch.Tensor, graph_nodes_list: torch.Tensor, num_graphs: int,

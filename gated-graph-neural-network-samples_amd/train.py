@@ -224,6 +224,9 @@ def train_step(model, batch_data) -> torch.Tensor:
     if train_native.panel_eligible(model, batch_data):
         # the default model at hidden 128 / 192 / 256 with native_panel_training: the same two sequences on their panel route
         return train_native.native_panel_train_step(model, batch_data)
+    if train_native.rnn_eligible(model, batch_data):
+        # the BasicRNNCell on the compacted route with compact_rnn == 'native': the same two sequences in their RNN form
+        return train_native.native_rnn_train_step(model, batch_data)
     if train_native.dense_eligible(model, batch_data):
         # the dense model with graph_resident_training == 'native': the same on the graph-resident kernels (csrc/ggnn_dense_train.hip)
         return train_native.native_dense_train_step(model, batch_data)

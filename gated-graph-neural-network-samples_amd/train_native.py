@@ -27,6 +27,12 @@ The default sparse model at the column-panel hidden sizes 128 / 192 / 256 has it
 ggnn_sparse_train_panel_backward_f32 (the same driver on its panel route, csrc/ggnn_train.hip) when its config says
 native_panel_training = True: panel_eligible / native_panel_train_step, again the default model's step below with a route argument.
 Without the key these sizes keep the autograd step (backward.PropagationStepFn on the panel kernels).
+
+The sparse model with the BasicRNNCell on the compacted route (graph_rnn_cell = RNN, the R-GCN configuration;
+SparseGGNNChemModel.rnn_route) has it on ggnn_sparse_rnn_train_forward_f32 / ggnn_sparse_rnn_train_backward_f32 when its config says
+compact_rnn = 'native' (True keeps variants.CompactRnnStepFn): rnn_eligible / native_rnn_train_step, the default model's step below
+with the cell's arguments in place of the GRU's.  Its weight images come layer by layer from ops.PACKED (one entry per weight
+version): there is no one-launch prepare for this cell.
 """
 from __future__ import annotations
 
@@ -174,6 +180,56 @@ def panel_model_eligible(model) -> bool:
     return _sparse_model_eligible(model, False, panel=True)
 
 
+def rnn_model_eligible(model) -> bool:
+    """The part of `rnn_eligible` that depends on the model only: a sparse model whose config asks for the native step with
+    params['compact_rnn'] == 'native' (read with .get: not a key of default_params, whose keys a reference checkpoint must match;
+    True keeps the autograd step) and whose BasicRNNCell runs on the compacted route (rnn_route()), hidden size unpadded, every
+    layer's (hidden size, inputs) in ops.rnn_fused_supported -- 32 / 64 with at most two residual inputs, 100 with none -- no edge
+    bias, no graph-state dropout, the fused optimizer over exactly the trainable variables, nothing frozen, one-layer readout MLPs,
+    and no active data-parallel context."""
+    p = getattr(model, "params", None)
+    if p is None or not hasattr(model, "_edge_weight_vars") or not hasattr(model, "rnn_route") or not torch.cuda.is_available():
+        return False
+    if not backward.USE_NATIVE_STEP or not backward.USE_COMPACT_TRANSFORM:
+        return False
+    if p.get('compact_rnn') != 'native' or not model.rnn_route() or p['use_edge_bias'] or not p['use_graph']:
+        return False
+    dist = getattr(model, "dist", None)
+    if (dist is not None and dist.active) or torch.device(model.device).type != 'cuda':
+        return False
+    D = p['hidden_size']
+    if model._kw != D or float(p.get('graph_state_dropout_keep_prob', 1.0)) < 1.0:
+        return False
+    L = len(p['layer_timesteps'])
+    if L > 60 or any(int(s) < 1 for s in p['layer_timesteps']):
+        return False
+    if any(not ops.rnn_fused_supported(D, len(p['residual_connections'].get(str(l)) or []) + 1) for l in range(L)):
+        return False
+    return _optimizer_and_readout_eligible(model)
+
+
+def rnn_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """True when this step of a model with the BasicRNNCell can run on the native sequences: rnn_model_eligible, no per-launch
+    timing, and a batch on the GPU, sorted by graph, with at least one message."""
+    return ops._timing is None and rnn_model_eligible(model) and _sparse_batch_eligible(model, batch_data)
+
+
+def _optimizer_and_readout_eligible(model) -> bool:
+    """The fused optimizer over exactly the trainable variables, nothing frozen, one-layer readout MLPs."""
+    p = model.params
+    opt = model.optimizer
+    variables = list(model.trainable_variables.values())
+    if not (opt.fused and len(opt.vars) == len(variables) and all(a is b for a, b in zip(opt.vars, variables))):
+        return False
+    have = {v.data_ptr() for v in variables}
+    if any(v.data_ptr() not in have for v in model.named_variables().values()):        # (--freeze-graph-model)
+        return False
+    for task_id in p['task_ids']:
+        if len(model.weights['regression_gate_task%i' % task_id].params["weights"]) != 1:
+            return False
+    return True
+
+
 def _sparse_model_eligible(model, attention: bool, panel: bool = False) -> bool:
     p = getattr(model, "params", None)
     if p is None or not hasattr(model, "_edge_weight_vars") or not torch.cuda.is_available():
@@ -207,17 +263,7 @@ def _sparse_model_eligible(model, attention: bool, panel: bool = False) -> bool:
         return False
     if any(len(p['residual_connections'].get(str(l)) or []) + 1 > ops.GRU_FUSED_MAX_INPUTS for l in range(L)):
         return False
-    opt = model.optimizer
-    variables = list(model.trainable_variables.values())
-    if not (opt.fused and len(opt.vars) == len(variables) and all(a is b for a, b in zip(opt.vars, variables))):
-        return False
-    have = {v.data_ptr() for v in variables}
-    if any(v.data_ptr() not in have for v in model.named_variables().values()):        # (--freeze-graph-model)
-        return False
-    for task_id in p['task_ids']:
-        if len(model.weights['regression_gate_task%i' % task_id].params["weights"]) != 1:
-            return False
-    return True
+    return _optimizer_and_readout_eligible(model)
 
 
 def eligible(model, batch_data: Dict[str, Any]) -> bool:
@@ -240,6 +286,11 @@ def panel_eligible(model, batch_data: Dict[str, Any]) -> bool:
 def _sparse_eligible(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False) -> bool:
     if ops._timing is not None or not _sparse_model_eligible(model, attention, panel):
         return False
+    return _sparse_batch_eligible(model, batch_data)
+
+
+def _sparse_batch_eligible(model, batch_data: Dict[str, Any]) -> bool:
+    """A batch the native sequences take: on the GPU, sorted by graph, at least one message, no graph-state dropout."""
     D = model.params['hidden_size']
     if float(batch_data.get('graph_state_keep_prob', 1.0)) < 1.0:
         return False
@@ -285,7 +336,14 @@ def native_panel_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
     return _native_sparse_step(model, batch_data, False, panel=True)
 
 
-def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False) -> torch.Tensor:
+def native_rnn_train_step(model, batch_data: Dict[str, Any]) -> torch.Tensor:
+    """native_train_step for the BasicRNNCell on the compacted route: the same two C calls in their RNN form
+    (ggnn_sparse_rnn_train_forward_f32 / ggnn_sparse_rnn_train_backward_f32), the same readout, loss, clip and Adam; the cell's
+    kernel and bias gradients arrive in the optimizer's gradient views like every other graph variable's."""
+    return _native_sparse_step(model, batch_data, False, rnn=True)
+
+
+def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, panel: bool = False, rnn: bool = False) -> torch.Tensor:
     lib = _lib.load()
     # the entry points of the route: whole-block sizes (32 / 64 / 100) or column panels (128 / 192 / 256), one argument list
     if panel:
@@ -332,11 +390,23 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, pane
         nxs = [len(residuals[l]) + 1 for l in range(L)]
         # operand format of each layer's GRU forward: two-piece f16 only where this step's operands are provably in its range
         # (formats.py: max|h0|, the weights' maxima tracked across optimizer steps, tanh cell, mean aggregation), else exact bf16x3
-        gru_fmts = model.gru_formats(h0, ew_keep, 1.0, training=True)
+        gru_fmts = [ops.GRU_FMT_EXACT] * L if rnn else model.gru_formats(h0, ew_keep, 1.0, training=True)
         if attention:                      # (the range proof does not cover attention-weighted sums: every product exact)
             gru_fmts = [ops.GRU_FMT_EXACT] * L
         fm = _i32(gru_fmts)
-        if L <= 16 and USE_FUSED_PREPARE:
+        if rnn:
+            # layer by layer through the version-keyed cache: the images of the key-True route's launches, bit for bit (every
+            # product exact: ReLU states have no bound)
+            edge_packed, edge_packed_t, rnn_packed, rnn_bwd_packed = [], [], [], []
+            for l in range(L):
+                W = model._edge_weight_vars[l].view(T, D, D)
+                if masks:
+                    W = backward.masked(W, masks[l][0], masks[l][1])
+                edge_packed.append(ops.PACKED.edge(W))
+                edge_packed_t.append(ops.PACKED.edge_t(W))
+                rnn_packed.append(ops.PACKED.rnn(cells[l].kernel, nxs[l], D))
+                rnn_bwd_packed.append(ops.PACKED.rnn_bwd(cells[l].kernel, nxs[l], D))
+        elif L <= 16 and USE_FUSED_PREPARE:
             # all ~120 images of the step in ONE launch, the weight-dropout mask applied on the fly (ggnn_sparse_train_prepare_f32)
             imgs = getattr(model, "_native_images", None)
             if imgs is None:
@@ -368,6 +438,10 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, pane
         if attention:
             ws_bytes = lib.ggnn_sparse_attn_train_workspace_bytes(V, D, T, R, steps, M)
             factors = _ptrs(model.gnn_weights.edge_type_attention_weights)
+        elif rnn:
+            ws_bytes = lib.ggnn_sparse_rnn_train_workspace_bytes(V, D, T, R, steps)
+            if not ws_bytes:
+                raise ValueError("native training step, RNN cell: no workspace for V=%d D=%d T=%d rows=%d steps=%d" % (V, D, T, R, steps))
         else:
             ws_bytes = workspace_bytes(V, D, T, R, steps)
             if not ws_bytes:
@@ -375,9 +449,15 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, pane
         ws, dstate = model._native_ws.get(ws_bytes, L, V, D, dev)
         tro = (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
         lt, rp, ri = _i32(p['layer_timesteps']), _i32(res_ptr), _i32(res_idx)
-        bg = _ptrs([c.gates_bias for c in cells]); bc = _ptrs([c.candidate_bias for c in cells])
+        if not rnn:
+            bg = _ptrs([c.gates_bias for c in cells]); bc = _ptrs([c.candidate_bias for c in cells])
         final_off = ctypes.c_int64(0)
-        if attention:
+        if rnn:
+            ops._launch("sparse_rnn_train_forward[steps=%d]" % steps, lambda: lib.ggnn_sparse_rnn_train_forward_f32(
+                h0.data_ptr(), V, D, T, M, index.row_ptr.data_ptr(), comp.gather_row.data_ptr(), comp.pair_node.data_ptr(), tro,
+                nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), _ptrs([c.bias for c in cells]),
+                _ptrs(rnn_packed), act, ws.data_ptr(), ws.numel(), ctypes.byref(final_off), st.cuda_stream))
+        elif attention:
             ops._launch("sparse_attn_train_forward[steps=%d]" % steps, lambda: lib.ggnn_sparse_attn_train_forward_f32(
                 h0.data_ptr(), V, D, T, M, index.row_ptr.data_ptr(), index.gather_row.data_ptr(), comp.gather_row.data_ptr(),
                 comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri, _ptrs(edge_packed), factors, bg, bc,
@@ -415,8 +495,18 @@ def _native_sparse_step(model, batch_data: Dict[str, Any], attention: bool, pane
         gv = lambda t: gviews[t.data_ptr()]
         node_heads = ops._ptr(ops.slot_heads(bwd.node_index, bwd.node_index.row_ptr, bwd.node_index.gather_row, V))
         g_edge = _ptrs([gv(model._edge_weight_vars[l]) for l in range(L)])
-        g_cells = [_ptrs([gv(getattr(c, name)) for c in cells]) for name in ('gates_kernel', 'gates_bias', 'candidate_kernel', 'candidate_bias')]
-        if attention:
+        if not rnn:
+            g_cells = [_ptrs([gv(getattr(c, name)) for c in cells]) for name in ('gates_kernel', 'gates_bias', 'candidate_kernel', 'candidate_bias')]
+        if rnn:
+            ops._launch("sparse_rnn_train_backward[steps=%d]" % steps, lambda: lib.ggnn_sparse_rnn_train_backward_f32(
+                h0.data_ptr(), V, D, T, comp.pair_node.data_ptr(), tro, nin.data_ptr(), 1 if use_avg else 0, L, lt, rp, ri,
+                bwd.rows_index.row_ptr.data_ptr(), bwd.rows_index.gather_row.data_ptr(),
+                ops._ptr(ops.slot_heads(bwd.rows_index, bwd.rows_index.row_ptr, bwd.rows_index.gather_row, R)),
+                bwd.node_index.row_ptr.data_ptr(), bwd.node_index.gather_row.data_ptr(), node_heads,
+                bwd.identity.pair_node.data_ptr(), _ptrs(edge_packed_t), _ptrs(rnn_bwd_packed), act, g_edge,
+                _ptrs([gv(c.kernel) for c in cells]), _ptrs([gv(c.bias) for c in cells]), d_final.data_ptr(), _ptrs(dstate),
+                ws.data_ptr(), ws.numel(), st.cuda_stream, side.cuda_stream))
+        elif attention:
             sni = bwd.source_node_index
             mto = (ctypes.c_int64 * (T + 1))(*index.type_off)
             ops._launch("sparse_attn_train_backward[steps=%d]" % steps, lambda: lib.ggnn_sparse_attn_train_backward_f32(

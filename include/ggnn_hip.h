@@ -496,6 +496,35 @@ int ggnn_rnn_packed_gather_f32(const float* const* x_segs, int nx, const float* 
                                const int32_t* gather_row, int64_t M, const float* nin, int T, int use_avg,
                                float* save_incoming, int V, int D, int act, ggnn_stream_t stream);
 
+/* The whole BasicRNNCell backward of a timestep in ONE launch (tf autodiff of h' = act([x.. | incoming | h] W + b),
+ * chem_tensorflow.py:184 over chem_tensorflow_sparse.py:109-110, with :206-209 for the mean): from g = dL/dh' and the saved out = h'
+ *   dP = g * act'(out)  (tanh: 1 - out^2, ReLU: out > 0; bit for bit ggnn_act_bwd_f32);   Q_s = dP W_s^T, W_s = rows sD..(s+1)D of W
+ *   dx[s] = Q_s (s < nx-1);  dx[nx-1] = d_incoming = Q_{nx-1} [/ (sum_t nin[v,t] + 1e-7) with use_avg];  dh = Q_nx
+ * chained in registers per 16-row tile, the nx + 1 transposed blocks resident in LDS as exact bf16x3 images -- the mirror image of
+ * ggnn_rnn_packed_gather_f32, with its supported set, occupancy rule and launch geometry (ggnn_rnn_fused_launch_geometry holds for
+ * both).  It replaces ggnn_act_bwd_f32 + ggnn_bwd_dx_f32 (and the transposed copy of W that launch is given).  dP [V,D] is written:
+ * it is the dY of the weight-gradient product.
+ *   ggnn_rnn_bwd_fused_supported(D, nx)   == ggnn_rnn_fused_supported(D, nx); the entry points below return GGNN_E_UNSUPPORTED
+ *                                         (ggnn_rnn_bwd_packed_bytes: 0) exactly where it is 0.
+ *   ggnn_rnn_bwd_pack_weights_f32         W [(nx+1)D, D] -> the nx + 1 images of W_s^T, once per weight version
+ *   ggnn_rnn_bwd_fused_f32                dx: HOST array of nx device pointers [V,D] (the last one receives d_incoming); nin [V,T] is
+ *                                         required with use_avg.  No output may alias an input or another output; every pointer is
+ *                                         16-byte aligned.  Rows >= V are neither read nor written.  V == 0 is a no-op; V*D >= 2^30:
+ *                                         GGNN_E_UNSUPPORTED.
+ *   ggnn_rnn_bwd_fused_gather_f32         ... with g_eff[v] = g[v] + the rows of gz [num_rows, D] named by the int4 slot-head record
+ *                                         gz_heads[v] (ggnn_build_slot_heads; an entry of -1 or outside [0, num_rows) adds nothing and
+ *                                         is not dereferenced): the meaning of the pair in ggnn_gru_bwd_fused_gather_f32 -- bit for
+ *                                         bit ggnn_gather_segment_sum_heads_f32(gz, .., accumulate = 1) into g followed by the plain
+ *                                         form, for nodes with at most four rows.  num_rows*D >= 2^30: GGNN_E_UNSUPPORTED. */
+int ggnn_rnn_bwd_fused_supported(int D, int nx);
+size_t ggnn_rnn_bwd_packed_bytes(int D, int nx);
+int ggnn_rnn_bwd_pack_weights_f32(const float* W, int nx, int D, float* packed, ggnn_stream_t stream);
+int ggnn_rnn_bwd_fused_f32(const float* g, const float* out, const float* packed, float* dP, float* const* dx, float* dh,
+                           const float* nin, int T, int use_avg, int nx, int V, int D, int act, ggnn_stream_t stream);
+int ggnn_rnn_bwd_fused_gather_f32(const float* g, const float* gz, const int32_t* gz_heads, int64_t num_rows, const float* out,
+                                  const float* packed, float* dP, float* const* dx, float* dh, const float* nin, int T,
+                                  int use_avg, int nx, int V, int D, int act, ggnn_stream_t stream);
+
 /* ggnn_sparse_propagate_f32 for graph_rnn_cell = RNN on the compacted transform.  The compact form is REQUIRED (pair_node /
  * type_row_off non-NULL, gather_row = the remapped rows; GGNN_E_INVALID otherwise).  Per timestep: the compacted transform on
  * edge_packed[l] (or raw edge_w[l]), then -- for a layer with rnn_packed[l], ggnn_rnn_fused_supported(D, nx) and no edge bias --
@@ -926,6 +955,39 @@ int ggnn_sparse_attn_train_backward_f32(const float* h0, int V, int D, int T, in
                                         float* const* g_edge, float* const* g_attn, float* const* g_Wg, float* const* g_bg,
                                         float* const* g_Wc, float* const* g_bc, float* d_final, float* const* d_state_ws, void* ws,
                                         size_t ws_bytes, ggnn_stream_t stream, ggnn_stream_t side_stream);
+
+/* The same step for graph_rnn_cell = RNN (tf BasicRNNCell, chem_tensorflow_sparse.py:109-110, the R-GCN configuration) on the
+ * compacted route: the conventions of the first pair above (no attention, no edge bias, a batch with M >= 1 messages), with the
+ * cell's arguments in place of the GRU's.  Every layer's (D, nx) must be in ggnn_rnn_fused_supported -- otherwise, and for a batch
+ * without compact rows, GGNN_E_UNSUPPORTED / GGNN_E_INVALID is returned before anything is enqueued.  The images are per layer
+ * ggnn_edge_weights_pack_f32 of W and of its transposes (edge_packed / edge_packed_t), ggnn_rnn_pack_weights_f32 (rnn_packed) and
+ * ggnn_rnn_bwd_pack_weights_f32 (rnn_bwd_packed); there is no one-launch prepare for this cell.  `ws`:
+ * ggnn_sparse_rnn_train_workspace_bytes (0 for a hidden size outside the cell's or on bad arguments; no r / u / c / r*h / dpg
+ * buffers, so smaller than the GRU's), the SAME buffer for both calls.
+ *   forward:  per timestep ggnn_msg_transform_compact_f32 and ggnn_rnn_packed_gather_f32 with save_incoming (M: the length of
+ *     gather_row_c) -- the launches of the autograd route's training forward, so every state is bit-identical to it.
+ *   backward: per timestep, last to first: ggnn_rnn_bwd_fused_f32 (ggnn_rnn_bwd_fused_gather_f32 when the node sum of the timestep
+ *     before is pending); on `side_stream` ONE ggnn_xty_acc_f32, g_W[l] += [x.. | incoming | h]^T dP with g_b[l] += its column
+ *     sums (one product per layer for a residual-free layer of several timesteps); then as above: the transpose segment sum into
+ *     dHc, the transform on W^T, the per-node sum (deferred), the row-gathered edge-weight product on `side_stream`.
+ *   Replaces, per timestep of variants._hip_backward's RNN branch (chem_tensorflow.py:184 over chem_tensorflow_sparse.py:109-110,
+ *   198-216): ggnn_act_bwd_f32, ggnn_xty_f32, a transposed copy of W, ggnn_bwd_dx_f32, and backward.transform_backward's launches. */
+size_t ggnn_sparse_rnn_train_workspace_bytes(int V, int D, int T, int64_t compact_rows, int total_steps);
+int ggnn_sparse_rnn_train_forward_f32(const float* h0, int V, int D, int T, int64_t M, const int32_t* row_ptr,
+                                      const int32_t* gather_row_c, const int32_t* pair_node, const int64_t* type_row_off,
+                                      const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+                                      const int32_t* res_ptr, const int32_t* res_idx, const float* const* edge_packed,
+                                      const float* const* rnn_b, const float* const* rnn_packed, int act, void* ws, size_t ws_bytes,
+                                      int64_t* final_state_offset, ggnn_stream_t stream);
+int ggnn_sparse_rnn_train_backward_f32(const float* h0, int V, int D, int T, const int32_t* pair_node, const int64_t* type_row_off,
+                                       const float* nin, int use_avg, int num_layers, const int32_t* layer_timesteps,
+                                       const int32_t* res_ptr, const int32_t* res_idx, const int32_t* rows_rp,
+                                       const int32_t* rows_gather, const int32_t* rows_heads, const int32_t* node_rp,
+                                       const int32_t* node_order, const int32_t* node_heads, const int32_t* identity_rows,
+                                       const float* const* edge_packed_t, const float* const* rnn_bwd_packed, int act,
+                                       float* const* g_edge, float* const* g_W, float* const* g_b, float* d_final,
+                                       float* const* d_state_ws, void* ws, size_t ws_bytes, ggnn_stream_t stream,
+                                       ggnn_stream_t side_stream);
 
 /* ---- tf.nn.dropout with a counter-based mask (chem_tensorflow_sparse.py:91 edge-weight dropout, :113-114 DropoutWrapper on the
  * new node state; chem_tensorflow_dense.py:104; utils.py:68 readout weights) ------------------------------------------------------

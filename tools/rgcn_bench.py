@@ -4,7 +4,7 @@ eight layers of one timestep, ReLU, mean aggregation, no edge bias).
 
 Two models in one process on the same resident batch -- key off and key on -- measured in `--rounds` interleaved rounds, so both
 arms see the same clocks and the same neighbours; per arm the median and min .. max over the rounds of the device-event time.
-Three legs (all by default, `--leg cell|forward|step` for one):
+Four legs (all by default, `--leg cell,step` for some):
   cell      the node update alone on the same inputs: ggnn_gather_segment_sum_f32 over the compact rows + ggnn_rnn_f32 (two
             launches, `incoming` through HBM, raw weights staged per call) against the one ggnn_rnn_packed_gather_f32 launch,
             `--iters` updates per round.  `incoming` is compared bit for bit first, h' by its largest difference.  For the fused
@@ -13,6 +13,14 @@ Three legs (all by default, `--leg cell|forward|step` for one):
   forward   the inference forward (compute_final_node_representations under no_grad), `--fwd-iters` forwards per round
   step      one training step (train_batch; edge-weight dropout as the reference trains), `--step-iters` steps per round; per arm
             also `host`: the wall-clock ms per step until the train_batch calls have RETURNED (the launching thread's share).
+            A third arm, `native`: the key 'native' (train_native.native_rnn_train_step: two native calls, no torch.autograd),
+            judged against the `compact` arm (the key True).
+  cell-bwd  the cell's backward alone on the same inputs: ggnn_act_bwd_f32 + ggnn_bwd_dx_f32 (`launches`) against the one
+            ggnn_rnn_bwd_fused_f32 launch (`fused`), and with a deferred node sum ggnn_gather_segment_sum_heads_f32 in front of
+            the two (`launches_sum`) against ggnn_rnn_bwd_fused_gather_f32 (`fused_gather`); dP is compared bit for bit first, the
+            products by their largest difference.  For the fused launches also the algorithmic HBM bytes, computed from shapes
+            -- g and out read, dP, d_incoming and dh written, the in-degree table; with the sum one Z row per compact row and
+            a head record per node -- and the fraction of the 8 TB/s roof.
 An arm counts as faster only if its whole min .. max range lies below the other arm's.
 Run from the repository root:  python tools/rgcn_bench.py [--graphs 5600] [--rounds 9] [--out profiles/rgcn_route.json]
 """
@@ -30,6 +38,7 @@ import ggnn_amd  # noqa: E402
 from attention_bench import HBM_ROOF, _interleaved  # noqa: E402
 
 ARMS = ("dense", "compact")                                 # key off, key on
+NATIVE = "native"                                           # key 'native': the step leg's third arm
 README = {"use_edge_bias": False, "use_edge_msg_avg_aggregation": True, "residual_connections": {},
           "layer_timesteps": [1, 1, 1, 1, 1, 1, 1, 1], "graph_rnn_cell": "RNN", "graph_rnn_activation": "ReLU"}
 
@@ -38,10 +47,12 @@ def _models(a):
     ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
     cfg = dict(README, hidden_size=a.hidden, batch_size=100000, random_seed=0)
     arms = {}
-    for name in ARMS:
+    for name in ARMS + (NATIVE,):
+        extra = {"dense": {}, "compact": {"compact_rnn": True}, NATIVE: {"compact_rnn": "native"}}[name]
         model = ggnn_amd.SparseGGNNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms,
-                                              "--config": dict(cfg, **({"compact_rnn": True} if name == "compact" else {}))})
-        assert model.rnn_route() == (name == "compact"), name
+                                              "--config": dict(cfg, **extra)})
+        assert model.rnn_route() == (name != "dense"), name
+        assert ggnn_amd.train_native.rnn_model_eligible(model) == (name == NATIVE), name
         arms[name] = model
     return arms
 
@@ -86,7 +97,74 @@ def cell_leg(a, arms):
     return res
 
 
+def cell_bwd_leg(a, arms):
+    ops = ggnn_amd.ops
+    model = arms["compact"]
+    feed = next(iter(model.make_minibatch_iterator(model.valid_data, is_training=False)))
+    index, nin = feed["message_index"], feed["num_incoming_edges_per_type"]
+    comp = index._compact
+    if getattr(comp, "_bwd", None) is None:
+        ops.prepare_message_index(index, model._kw, True, training=True)
+        comp = index._compact
+    bwd = ops.compact_backward(index, comp)
+    V, T, R = index.num_nodes, index.num_edge_types, comp.num_rows
+    D = model._kw
+    assert ops.rnn_bwd_fused_supported(D, 1), "the cell-bwd leg needs a width with the fused backward at nx = 1"
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    g = torch.randn((V, D), device="cuda", generator=gen)
+    out = torch.relu(torch.rand((V, D), device="cuda", generator=gen) * 2 - 1)          # a ReLU output: about half the entries 0
+    Z = torch.randn((R, D), device="cuda", generator=gen)
+    W = model.gnn_weights.rnn_cells[0].kernel.detach().contiguous()
+    WT = ggnn_amd.backward.transposed(W)
+    packed = ops.rnn_bwd_pack(W, 1)
+    act = model.params["graph_rnn_activation"]
+    ni = bwd.node_index
+    heads = ops.slot_heads(ni, ni.row_ptr, ni.gather_row, V)
+    lib = ggnn_amd._lib.load()
+    results = {}
+    dx = torch.empty((V, D), device="cuda"); dinc = torch.empty_like(g); dh = torch.empty_like(g); gs = torch.empty_like(g)
+
+    def launches(grad=g, key="launches"):
+        dP = ops.act_bwd(grad, out, act)
+        ops.bwd_dx(dP, 1, WT, D, True, dx, dinc, nin, True, dh, False, False, D)
+        results[key] = (dP, dinc, dh)
+
+    def launches_sum():                                     # (the sum accumulates in place, as in the step: gs keeps growing while timed)
+        ggnn_amd._lib.check(lib.ggnn_gather_segment_sum_heads_f32(Z.data_ptr(), ni.row_ptr.data_ptr(), ni.gather_row.data_ptr(), heads.data_ptr(),
+                                                                  None, None, 0, gs.data_ptr(), V, D, 1, 1, torch.cuda.current_stream().cuda_stream))
+        launches(gs, "launches_sum")
+
+    def fused():
+        dP, dh_f, dxs = ops.rnn_bwd_fused(g, out, packed, nin, True, 1, act)
+        results["fused"] = (dP, dxs[0], dh_f)
+
+    def fused_gather():
+        dP, dh_f, dxs = ops.rnn_bwd_fused(g, out, packed, nin, True, 1, act, gather=(Z, heads))
+        results["fused_gather"] = (dP, dxs[0], dh_f)
+    cmp = {}
+    for old, new in (("launches", "fused"), ("launches_sum", "fused_gather")):
+        gs.copy_(g)
+        {"launches": launches, "launches_sum": launches_sum}[old](); {"fused": fused, "fused_gather": fused_gather}[new]()
+        a_, b_ = [tuple(t.clone() for t in results[k]) for k in (old, new)]
+        finite = torch.isfinite(a_[1]).all(dim=1)           # (a node without incoming edges divides by 1e-7: compare the others)
+        cmp[new] = {"dP_bit_identical": bool(torch.equal(a_[0], b_[0])),
+                    "max_abs_difference_of_dinc": float((a_[1] - b_[1])[finite].abs().max()), "max_abs_dinc": float(a_[1][finite].abs().max()),
+                    "max_abs_difference_of_dh": float((a_[2] - b_[2]).abs().max()), "max_abs_dh": float(a_[2].abs().max())}
+    res = _interleaved({"launches": launches, "fused": fused, "launches_sum": launches_sum, "fused_gather": fused_gather}, a.iters, a.rounds,
+                       unit=1e3, pairs=(("launches", "fused"), ("launches_sum", "fused_gather")))   # us
+    bts = 5 * V * D * 4 + V * T * 4
+    bts_g = bts + R * D * 4 + V * 16
+    res.update({"unit": "us per cell backward (launches: ggnn_act_bwd_f32 + ggnn_bwd_dx_f32; launches_sum: "
+                        "ggnn_gather_segment_sum_heads_f32 (accumulating in place) in front of them; fused / fused_gather: the one launch; every arm allocates its outputs)",
+                "V": V, "R": R, "T": T, "D": D, "backwards_per_round": a.iters, "comparison": cmp,
+                "fused_bytes_derived": int(bts), "fused_roof_fraction": round(bts / HBM_ROOF / (res["fused"]["median"] * 1e-6), 3),
+                "fused_gather_bytes_derived": int(bts_g),
+                "fused_gather_roof_fraction": round(bts_g / HBM_ROOF / (res["fused_gather"]["median"] * 1e-6), 3)})
+    return res
+
+
 def forward_leg(a, arms):
+    arms = {n: arms[n] for n in ARMS}
     feeds = {n: next(iter(arms[n].make_minibatch_iterator(arms[n].valid_data, is_training=False))) for n in ARMS}
     finals = {}
 
@@ -116,7 +194,7 @@ def step_leg(a, arms):
         np.random.seed(0)
         feeds[n] = dict(next(iter(m.make_minibatch_iterator(m.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
     fns = {n: (lambda n=n: arms[n].train_batch(feeds[n])) for n in arms}
-    res = _interleaved(fns, a.step_iters, a.rounds, host=True)
+    res = _interleaved(fns, a.step_iters, a.rounds, pairs=(("dense", "compact"), ("compact", NATIVE)), host=True)
     res.update({"unit": "ms per training step", "V": int(feeds["dense"]["initial_node_representation"].shape[0]),
                 "steps_per_round": a.step_iters, "edge_weight_dropout_keep_prob": feeds["dense"]["edge_weight_dropout_keep_prob"]})
     return res
@@ -126,7 +204,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=5600)
     ap.add_argument("--hidden", type=int, default=100)
-    ap.add_argument("--leg", choices=("all", "cell", "forward", "step"), default="all")
+    ap.add_argument("--leg", default="all", help="all, or a comma-separated list of cell, cell-bwd, forward, step")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--fwd-iters", type=int, default=20)
@@ -137,10 +215,13 @@ def main():
     arms = _models(a)
     out = {"metric": "sparse GGNN with the BasicRNNCell (R-GCN configuration), synthetic QM9: dense-transform route (key off) vs "
                      "compacted route (compact_rnn)", "graphs": a.graphs, "hidden_size": a.hidden, "rounds": a.rounds,
+           "step_arms": {"dense": "key off", "compact": "compact_rnn True", NATIVE: "compact_rnn 'native'"},
            "layer_timesteps": arms["dense"].params["layer_timesteps"], "graph_rnn_activation": arms["dense"].params["graph_rnn_activation"]}
-    legs = {"cell": cell_leg, "forward": forward_leg, "step": step_leg}
+    legs = {"cell": cell_leg, "cell-bwd": cell_bwd_leg, "forward": forward_leg, "step": step_leg}
+    chosen = list(legs) if a.leg == "all" else a.leg.split(",")
+    assert all(n in legs for n in chosen), "unknown leg in %r" % a.leg
     for name, leg in legs.items():
-        if a.leg in ("all", name):
+        if name in chosen:
             out[name] = leg(a, arms)
     line = json.dumps(out)
     print(line)
