@@ -106,6 +106,14 @@ SYMBOLS = {
     "ggnn_rnn_packed_gather_f32": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                            c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                            c_void_p]),
+    # ... at hidden 128 / 192 / 256 on column panels (ggnn_rnn_panel.hip)
+    "ggnn_rnn_panel_supported": (c_int, [c_int, c_int]),
+    "ggnn_rnn_panel_packed_bytes": (c_size_t, [c_int, c_int]),
+    "ggnn_rnn_panel_pack_weights_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_rnn_panel_launch_geometry": (None, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "ggnn_rnn_panel_gather_f32": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                          c_void_p]),
     # ... and its backward in one launch
     "ggnn_rnn_bwd_fused_supported": (c_int, [c_int, c_int]),
     "ggnn_rnn_bwd_packed_bytes": (c_size_t, [c_int, c_int]),

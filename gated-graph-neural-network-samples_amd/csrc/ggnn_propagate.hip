@@ -11,7 +11,8 @@
 // one driver below; without attention it launches what it always launched.
 //
 // The cell is a parameter of the driver: with an RnnCell (ggnn_sparse_propagate_rnn_f32; graph_rnn_cell = RNN, the R-GCN
-// configuration) the node update is the BasicRNNCell -- ggnn_rnn_packed_gather_f32 (2 kernels per timestep) for a layer with packed
+// configuration) the node update is the BasicRNNCell -- ggnn_rnn_packed_gather_f32 (2 kernels per timestep; at hidden 128 / 192 / 256
+// ggnn_rnn_panel_gather_f32 on panel images) for a layer with packed
 // images, a supported (D, nx) and no edge bias, ggnn_gather_segment_sum_f32 + ggnn_rnn_f32 (3 kernels) otherwise -- always behind
 // the compacted transform.  Without one the GRU entry points launch exactly what they launched before.
 #include "ggnn_common.h"
@@ -113,8 +114,10 @@ static int propagate(
         GGNN_CHECK_ARG(!attn_factors || factors_l, "attn_factors[%d] is null", l);
         const bool gather_in_gru = !rnn && !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
                                    (unsigned long long)V * T * D < (1ULL << 30);      // (its 32-bit byte offsets)
+        // (the two supported sets are disjoint: rnn->packed[l] holds the images of whichever cell takes (D, nx))
+        const bool panel_rnn = rnn && ggnn_rnn_panel_supported(D, nx);
         const bool gather_in_rnn = rnn && fuse_gather > 0 && nx <= fuse_gather && rnn->packed && rnn->packed[l] &&
-                                   ggnn_rnn_fused_supported(D, nx) && bias_l == nullptr &&
+                                   (panel_rnn || ggnn_rnn_fused_supported(D, nx)) && bias_l == nullptr &&
                                    (unsigned long long)V * D < (1ULL << 30) && (unsigned long long)(rows > 0 ? rows : 1) * D < (1ULL << 30);
         if (rnn) GGNN_CHECK_ARG(rnn->b[l] && (gather_in_rnn || (rnn->w && rnn->w[l])), "layer %d needs raw RNN weights (no fused cell for it)", l);
         for (int s = 0; s < steps; ++s) {          // :153
@@ -134,7 +137,10 @@ static int propagate(
             static const bool dyn_tiles = [] { const char* e = getenv("GGNN_DYN_TILES"); return !e || atoi(e) != 0; }();
             int32_t* counter = (dyn_tiles && step_no < kTileCounters) ? counters + step_no : nullptr;
             ++step_no;
-            if (gather_in_rnn) {
+            if (gather_in_rnn && panel_rnn) {
+                rc = ggnn_rnn_panel_gather_f32(xs, nx, cur, rnn->packed[l], rnn->b[l], out, H, rows > 0 ? rows : 1, row_ptr, gather_row,
+                                               rnn->M, nin, T, use_avg, nullptr, V, D, act, stream);
+            } else if (gather_in_rnn) {
                 rc = ggnn_rnn_packed_gather_f32(xs, nx, cur, rnn->packed[l], rnn->b[l], out, H, rows > 0 ? rows : 1, row_ptr, gather_row,
                                                 rnn->M, nin, T, use_avg, nullptr, V, D, act, stream);
             } else if (rnn) {

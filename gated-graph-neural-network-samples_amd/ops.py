@@ -1070,6 +1070,11 @@ class PackedWeights:
         version.  (nx, D) must be in the supported set: rnn_fused_supported."""
         return self._images.get((W,), ("rnn", int(nx)), lambda: rnn_pack(W, nx))
 
+    def rnn_panel(self, W: torch.Tensor, nx: int, D: int) -> torch.Tensor:
+        """The (nx + 1) D / 64 exact bf16x3 panel images of the panel BasicRNNCell (ggnn_rnn_panel_pack_weights_f32), once per
+        weight version.  (nx, D) must be in the supported set: rnn_panel_supported."""
+        return self._images.get((W,), ("rnn_panel", int(nx)), lambda: rnn_panel_pack(W, nx))
+
     def rnn_bwd(self, W: torch.Tensor, nx: int, D: int) -> torch.Tensor:
         """The nx + 1 exact bf16x3 images of W_s^T of the fused BasicRNNCell backward (ggnn_rnn_bwd_pack_weights_f32), once per
         weight version.  (nx, D) must be in the supported set: rnn_bwd_fused_supported."""
@@ -1294,6 +1299,48 @@ def rnn_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, pa
     input segment -- the aggregated messages -- is summed from the transformed rows `Hc` inside the kernel (no edge bias; the
     mean with num_incoming_edges_per_type, the plain sum with None).  gather_row: message slot -> row of Hc (None: the index's
     own).  save (dict): receives the gathered segment as save["incoming"] (training: an operand of the weight gradient)."""
+    return _rnn_gather_launch("ggnn_rnn_packed_gather_f32", "rnn_fused_gather[nx=%d]", residual_segs, h, packed, b, Hc, index,
+                              gather_row, num_incoming_edges_per_type, activation, save)
+
+
+def rnn_panel_supported(D: int, nx: int) -> bool:
+    """True when the BasicRNNCell with nx concatenated inputs has the gather-fused COLUMN-PANEL launch at width D
+    (ggnn_rnn_panel_supported: D = 128 / 192 / 256 with nx <= 3; disjoint from rnn_fused_supported)."""
+    return bool(_lib.load().ggnn_rnn_panel_supported(int(D), int(nx)))
+
+
+def rnn_panel_launch_geometry(D: int, nx: int) -> Tuple[int, int]:
+    """(rows a workgroup of the panel RNN cell covers per pass, the most workgroups a launch starts)."""
+    rows, wgs = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().ggnn_rnn_panel_launch_geometry(int(D), int(nx), ctypes.byref(rows), ctypes.byref(wgs))
+    return rows.value, wgs.value
+
+
+def rnn_panel_pack(W: torch.Tensor, nx: int) -> torch.Tensor:
+    """W [(nx+1) D, D] -> the (nx + 1) D / 64 panel images of ggnn_rnn_panel_gather_f32 (PackedWeights.rnn_panel caches them per
+    weight version)."""
+    lib = _lib.load()
+    _req(W, torch.float32, "W")
+    if W.dim() != 2 or W.shape[0] != (nx + 1) * W.shape[1]:
+        raise ValueError("W must be [(nx+1)*D, D]")
+    D = W.shape[1]
+    packed = torch.empty(max(lib.ggnn_rnn_panel_packed_bytes(D, nx) // 4, 4), dtype=torch.float32, device=W.device)
+    check(lib.ggnn_rnn_panel_pack_weights_f32(_ptr(W), nx, D, _ptr(packed), _stream()))
+    return packed
+
+
+def rnn_panel_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, packed: torch.Tensor, b: torch.Tensor,
+                     Hc: torch.Tensor, index: MessageIndex, gather_row: Optional[torch.Tensor],
+                     num_incoming_edges_per_type: Optional[torch.Tensor], activation: str = "tanh",
+                     save: Optional[dict] = None) -> torch.Tensor:
+    """rnn_packed_gather at hidden 128 / 192 / 256 (ggnn_rnn_panel_gather_f32; packed: rnn_panel_pack's images): the same
+    arguments, the same gather arithmetic and the same save= behaviour."""
+    return _rnn_gather_launch("ggnn_rnn_panel_gather_f32", "rnn_panel_gather[nx=%d]", residual_segs, h, packed, b, Hc, index,
+                              gather_row, num_incoming_edges_per_type, activation, save)
+
+
+def _rnn_gather_launch(symbol: str, launch_name: str, residual_segs, h, packed, b, Hc, index, gather_row,
+                       num_incoming_edges_per_type, activation, save) -> torch.Tensor:
     lib = _lib.load()
     _req(h, torch.float32, "h"); _req(Hc, torch.float32, "Hc"); _req(b, torch.float32, "b")
     V, D = h.shape
@@ -1316,7 +1363,7 @@ def rnn_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, pa
     inc = None
     if save is not None:
         inc = save["incoming"] = torch.empty_like(h)
-    _launch("rnn_fused_gather[nx=%d]" % nx, lambda: lib.ggnn_rnn_packed_gather_f32(
+    _launch(launch_name % nx, lambda: getattr(lib, symbol)(
         segs, nx, _ptr(h), _ptr(packed), _ptr(b), _ptr(out), _ptr(Hc), Hc.shape[0], _ptr(index.row_ptr), _ptr(gather),
         gather.numel(), None if nin is None else _ptr(nin), index.num_edge_types, 0 if nin is None else 1, _ptr(inc), V, D, act,
         _stream()))

@@ -290,6 +290,13 @@ class SparseGGNNChemModel(ChemModel):
         return bool(p.get('compact_rnn')) and self.cell_type == 'rnn' and not p['use_propagation_attention'] \
             and torch.device(self.device).type == 'cuda' and ops.compact_supported(self._kw)
 
+    def rnn_panel_route(self) -> bool:
+        """True when rnn_route() holds and the opt-in key params['rnn_panel_cell'] is set: layers at kernel width 128 / 192 / 256 with
+        at most two residual inputs and no edge bias run the column-panel cell (ops.rnn_panel_gather) in place of the segment sum
+        over the compact rows + ops.rnn.  Every other layer, width and route is untouched; compact_rnn = 'native' is not eligible
+        at these widths and stays compact_rnn = True."""
+        return bool(self.params.get('rnn_panel_cell')) and self.params.get('compact_rnn') != 'native' and self.rnn_route()
+
     # ---- the hot path -----------------------------------------------------------------------------------
     def compute_final_node_representations(self) -> torch.Tensor:
         """chem_tensorflow_sparse.py:117-218."""
@@ -315,6 +322,7 @@ class SparseGGNNChemModel(ChemModel):
         gru_fmts = self.gru_formats(h0, ew_keep, st_keep, need_grad)
         attn_route = self.attention_route() and h0.is_cuda
         rnn_route = self.rnn_route() and h0.is_cuda
+        rnn_panel = rnn_route and self.rnn_panel_route()
 
         if rnn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
             # inference with the RNN cell on the compacted route: ONE native call, the cell fused with the segment sum where it can be
@@ -357,10 +365,12 @@ class SparseGGNNChemModel(ChemModel):
                     # non-default switches, training: HIP forward, autograd-derived backward (variants.py)
                     from .variants import variant_step
                     cur = variant_step(cur, index, nin, edge_weights, edge_biases, attn_w, use_avg, layer_residual_states,
-                                       self.cell_type, tuple(cell), act, compact_attention=attn_route, compact_rnn=rnn_route)
+                                       self.cell_type, tuple(cell), act, compact_attention=attn_route, compact_rnn=rnn_route,
+                                       rnn_panel=rnn_panel)
                 elif variant:
                     cur = self._variant_step(cur, index, nin, edge_weights.contiguous(), edge_biases, attn_w, use_avg,
-                                             layer_residual_states, cell, act, compact_attention=attn_route, compact_rnn=rnn_route)
+                                             layer_residual_states, cell, act, compact_attention=attn_route, compact_rnn=rnn_route,
+                                             rnn_panel=rnn_panel)
                 else:
                     cur = propagation_step(cur, index, nin, edge_weights, edge_biases, use_avg,
                                            layer_residual_states, cell, act, need_grad,
@@ -387,7 +397,7 @@ class SparseGGNNChemModel(ChemModel):
         return uid
 
     def _variant_step(self, h, index, nin, edge_weights, edge_biases, attn_w, use_avg, residual_states, cell, act,
-                      compact_attention: bool = False, compact_rnn: bool = False):
+                      compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False):
         """One timestep with the non-default switches of chem_tensorflow_sparse.py: propagation attention
         (:147-149, 170-196) and/or the BasicRNNCell / CudnnCompatibleGRUCell cells (:105-110).  Dense transform, unless
         compact_attention (attention_route()): compacted transform, attention sum over the compact rows, packed GRU;
@@ -395,7 +405,8 @@ class SparseGGNNChemModel(ChemModel):
         (ops.rnn_packed_gather) or, for layers it does not take, the segment sum over the compact rows and ops.rnn."""
         if compact_rnn:
             from .variants import compact_rnn_forward
-            return compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, cell[0], cell[1], act)[0]
+            return compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, cell[0], cell[1], act,
+                                       **(dict(panel=True) if rnn_panel else {}))[0]
         if compact_attention:
             from .variants import compact_sources
             comp = compact_sources(index)
@@ -454,7 +465,8 @@ class SparseGGNNChemModel(ChemModel):
     def _propagate_native_rnn(self, h0, index, nin, use_avg, act) -> torch.Tensor:
         """compute_final_node_representations on rnn_route() through ggnn_sparse_propagate_rnn_f32: compacted transform on packed
         edge images, then the gather-fused BasicRNNCell on its packed images (layers the kernel does not take: the segment sum over
-        the compact rows and the generic cell on the raw weights).  Every product in the exact format."""
+        the compact rows and the generic cell on the raw weights; with rnn_panel_route() the panel cell at widths 128 / 192 / 256).
+        Every product in the exact format."""
         from .variants import compact_sources
         D = self._kw
         L = len(self.params['layer_timesteps'])
@@ -465,8 +477,18 @@ class SparseGGNNChemModel(ChemModel):
         edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
         cells = [lay[3] for lay in layers]
         residuals = [self.params['residual_connections'].get(str(l)) or [] for l in range(L)]
-        rnn_packed = [ops.PACKED.rnn(c.kernel, len(residuals[l]) + 1, D)
-                      if edge_bias is None and ops.rnn_fused_supported(D, len(residuals[l]) + 1) else None for l, c in enumerate(cells)]
+        panel = self.rnn_panel_route()
+
+        def images(l, c):                                   # (the two cells' supported sets are disjoint)
+            nx = len(residuals[l]) + 1
+            if edge_bias is not None:
+                return None
+            if ops.rnn_fused_supported(D, nx):
+                return ops.PACKED.rnn(c.kernel, nx, D)
+            if panel and ops.rnn_panel_supported(D, nx):
+                return ops.PACKED.rnn_panel(c.kernel, nx, D)
+            return None
+        rnn_packed = [images(l, c) for l, c in enumerate(cells)]
         outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals, edge_w, edge_packed,
                                     edge_bias, None, None, None, None, None, act, edge_fmt=[ops.GRU_FMT_EXACT] * L,
                                     rnn=([c.kernel for c in cells], [c.bias for c in cells], rnn_packed))

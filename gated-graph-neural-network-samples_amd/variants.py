@@ -15,7 +15,9 @@ backward the same kernels with ggnn_attn_bwd_target_compact_f32 on the recompute
 With params['compact_rnn'] (SparseGGNNChemModel.rnn_route: the BasicRNNCell without attention, a width with a compacted transform)
 the step is CompactRnnStepFn: forward ops.msg_transform_compact_packed -> ops.rnn_packed_gather (the cell with the segment sum
 gathered inside; `incoming` comes back from the launch) or, for layers that kernel does not take, ops.gather_segment_sum_compact ->
-ops.rnn; the backward is the BasicRNNCell branch below, which runs transform_backward on the compact rows anyway.
+ops.rnn; the backward is the BasicRNNCell branch below, which runs transform_backward on the compact rows anyway.  With
+params['rnn_panel_cell'] as well (rnn_panel_route) the step is CompactRnnPanelStepFn: at widths 128 / 192 / 256 the forward's cell is
+ops.rnn_panel_gather, `incoming` saved the same way; same backward.
 Hidden sizes beyond the fused kernels' (128 / 192 / 256 and what pads to them) run the same backward on the generic kernels:
 the un-fused GRU backward, ggnn_gemm_tn_f32 / ggnn_colsum_f32 for the weight and bias gradients.  The timestep restated in
 differentiable torch ops lives in tests/variant_oracle.py (a test oracle; BACKWARD_ORACLE below is its hook).
@@ -44,7 +46,7 @@ class VariantStepFn(torch.autograd.Function):
 
     @staticmethod
     def step_forward(ctx, compact_attention, h, index, nin, use_avg, cell_type, activation, num_cell, num_res, edge_weights,
-                     edge_biases, attention_weights, *rest, compact_rnn=False):
+                     edge_biases, attention_weights, *rest, compact_rnn=False, rnn_panel=False):
         cell, residuals = rest[:num_cell], rest[num_cell:num_cell + num_res]
         h = h.contiguous()
         W = edge_weights.contiguous()
@@ -55,7 +57,8 @@ class VariantStepFn(torch.autograd.Function):
             # the BasicRNNCell without attention, a width with a compacted transform: only the active (node, type) rows are
             # transformed and the cell gathers its own segment sum where the fused kernel takes the layer
             assert attention_weights is None and cell_type == 'rnn'
-            out, incoming = compact_rnn_forward(h, index, nin, W, edge_biases, use_avg, residuals, cell[0], cell[1], activation)
+            out, incoming = compact_rnn_forward(h, index, nin, W, edge_biases, use_avg, residuals, cell[0], cell[1], activation,
+                                                **(dict(panel=True) if rnn_panel else {}))
         elif compact_attention:
             # attention, GRU cell, a width with a compacted transform: only the active (node, type) rows are transformed, the
             # attention-weighted sum reads them through the compact slot rows (no dense [V, T*D] product, forward or backward)
@@ -132,14 +135,29 @@ class CompactRnnStepFn(VariantStepFn):
         return VariantStepFn.step_forward(ctx, False, *args, compact_rnn=True)
 
 
-def compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, W, b, activation):
+class CompactRnnPanelStepFn(VariantStepFn):
+    """CompactRnnStepFn under params['rnn_panel_cell']: the forward runs the panel cell (ops.rnn_panel_gather, `incoming` saved) where
+    ops.rnn_panel_supported takes the layer; same arguments, same saved tensors, same backward."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return VariantStepFn.step_forward(ctx, False, *args, compact_rnn=True, rnn_panel=True)
+
+
+def compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, W, b, activation, panel=False):
     """One BasicRNNCell timestep on the compacted route -> (h', incoming): the compacted transform on packed edge images, then
     the cell with the segment sum gathered inside (ops.rnn_packed_gather, which hands `incoming` back) where
     ops.rnn_fused_supported takes the layer and it has no edge bias; otherwise the segment sum over the compact rows and ops.rnn.
+    panel (params['rnn_panel_cell']): at widths 128 / 192 / 256 such a layer takes the column-panel cell (ops.rnn_panel_gather).
     The dense [V, T*D] product is never formed."""
     comp = compact_sources(index)
     D, nx = h.shape[1], len(residual_states) + 1
     Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(edge_weights), edge_weights.shape[0], comp)
+    if panel and edge_biases is None and ops.rnn_panel_supported(D, nx):
+        save = {}
+        out = ops.rnn_panel_gather(list(residual_states), h, ops.PACKED.rnn_panel(W, nx, D), b, Hc, index, comp.gather_row,
+                                   nin if use_avg else None, activation, save=save)
+        return out, save["incoming"]
     if edge_biases is None and ops.rnn_fused_supported(D, nx):
         save = {}
         out = ops.rnn_packed_gather(list(residual_states), h, ops.PACKED.rnn(W, nx, D), b, Hc, index, comp.gather_row,
@@ -233,9 +251,10 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
 
 def variant_step(h, index, nin, edge_weights, edge_biases: Optional[torch.Tensor], attention_weights: Optional[torch.Tensor],
                  use_avg: bool, residual_states: Sequence[torch.Tensor], cell_type: str, cell: Sequence[torch.Tensor],
-                 activation: str, compact_attention: bool = False, compact_rnn: bool = False) -> torch.Tensor:
+                 activation: str, compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False) -> torch.Tensor:
     """compact_attention: the step of SparseGGNNChemModel.attention_route() (attention, GRU cell, a compacted-transform width);
-    compact_rnn: the step of SparseGGNNChemModel.rnn_route() (BasicRNNCell, no attention, a compacted-transform width)."""
-    fn = CompactRnnStepFn if compact_rnn else CompactAttentionStepFn if compact_attention else VariantStepFn
+    compact_rnn: the step of SparseGGNNChemModel.rnn_route() (BasicRNNCell, no attention, a compacted-transform width);
+    rnn_panel: with it, the panel cell where it takes the layer (SparseGGNNChemModel.rnn_panel_route())."""
+    fn = (CompactRnnPanelStepFn if rnn_panel else CompactRnnStepFn) if compact_rnn else CompactAttentionStepFn if compact_attention else VariantStepFn
     return fn.apply(h, index, nin, use_avg, cell_type, activation, len(cell), len(residual_states), edge_weights,
                     edge_biases, attention_weights, *cell, *residual_states)

@@ -496,6 +496,27 @@ int ggnn_rnn_packed_gather_f32(const float* const* x_segs, int nx, const float* 
                                const int32_t* gather_row, int64_t M, const float* nin, int T, int use_avg,
                                float* save_incoming, int V, int D, int act, ggnn_stream_t stream);
 
+/* The same cell at hidden sizes 128 / 192 / 256, where the nx + 1 blocks no longer fit LDS: the (nx + 1) D / 64 COLUMN-PANEL images
+ * [D, 64] of W stream through a two-slot LDS-DMA ring (ggnn_rnn_panel.hip; exact bf16x3 only), the K segment outermost, so every
+ * operand row is read once whatever nx.  Replaces, per timestep of chem_tensorflow_sparse.py:198-216 with :109-110, the launches
+ * ggnn_gather_segment_sum_f32 (incoming [V, D] written to memory) + ggnn_rnn_f32 (which reads it back and re-stages W).  The gather
+ * arithmetic, the defensive addressing and the save_incoming contract are ggnn_rnn_packed_gather_f32's, word for word.
+ *   ggnn_rnn_panel_supported(D, nx)   1 for D in {128, 192, 256} with nx in 1..3; 0 otherwise (disjoint from
+ *                                     ggnn_rnn_fused_supported).  The entry points below return GGNN_E_UNSUPPORTED
+ *                                     (ggnn_rnn_panel_packed_bytes: 0, the geometry: 0 / 0) exactly where it is 0.
+ *   ggnn_rnn_panel_packed_bytes       (nx + 1) * (D / 64) * (D / 32) * 12288
+ *   ggnn_rnn_panel_pack_weights_f32   W [(nx+1)D, D] -> image s * (D / 64) + p = rows s D .., columns 64 p ..; once per weight version
+ *   ggnn_rnn_panel_launch_geometry    {rows a workgroup covers per pass, the most workgroups a launch starts}
+ *   ggnn_rnn_panel_gather_f32         the launch; the argument list and rules of ggnn_rnn_packed_gather_f32. */
+int ggnn_rnn_panel_supported(int D, int nx);
+size_t ggnn_rnn_panel_packed_bytes(int D, int nx);
+int ggnn_rnn_panel_pack_weights_f32(const float* W, int nx, int D, float* packed, ggnn_stream_t stream);
+void ggnn_rnn_panel_launch_geometry(int D, int nx, int* rows_per_workgroup, int* max_workgroups);
+int ggnn_rnn_panel_gather_f32(const float* const* x_segs, int nx, const float* h, const float* packed, const float* b,
+                              float* h_out, const float* Hrows, int64_t num_rows, const int32_t* row_ptr,
+                              const int32_t* gather_row, int64_t M, const float* nin, int T, int use_avg,
+                              float* save_incoming, int V, int D, int act, ggnn_stream_t stream);
+
 /* The whole BasicRNNCell backward of a timestep in ONE launch (tf autodiff of h' = act([x.. | incoming | h] W + b),
  * chem_tensorflow.py:184 over chem_tensorflow_sparse.py:109-110, with :206-209 for the mean): from g = dL/dh' and the saved out = h'
  *   dP = g * act'(out)  (tanh: 1 - out^2, ReLU: out > 0; bit for bit ggnn_act_bwd_f32);   Q_s = dP W_s^T, W_s = rows sD..(s+1)D of W
@@ -528,7 +549,8 @@ int ggnn_rnn_bwd_fused_gather_f32(const float* g, const float* gz, const int32_t
 /* ggnn_sparse_propagate_f32 for graph_rnn_cell = RNN on the compacted transform.  The compact form is REQUIRED (pair_node /
  * type_row_off non-NULL, gather_row = the remapped rows; GGNN_E_INVALID otherwise).  Per timestep: the compacted transform on
  * edge_packed[l] (or raw edge_w[l]), then -- for a layer with rnn_packed[l], ggnn_rnn_fused_supported(D, nx) and no edge bias --
- * ggnn_rnn_packed_gather_f32; otherwise ggnn_gather_segment_sum_f32 over the compact rows and ggnn_rnn_f32 on rnn_w[l].
+ * ggnn_rnn_packed_gather_f32 (with ggnn_rnn_panel_supported(D, nx) instead: ggnn_rnn_panel_gather_f32, rnn_packed[l] then being
+ * ggnn_rnn_panel_pack_weights_f32's images); otherwise ggnn_gather_segment_sum_f32 over the compact rows and ggnn_rnn_f32 on rnn_w[l].
  *   rnn_w [(nx+1)D, D], rnn_b [D], rnn_packed (ggnn_rnn_pack_weights_f32; the array or single entries may be NULL): HOST arrays of
  *   num_layers DEVICE pointers.  M: the length of gather_row.  fuse_gather: as in ggnn_sparse_propagate_f32 (the largest nx that
  *   runs the fused cell; 0: never).  Same workspace as ggnn_sparse_propagate_f32. */

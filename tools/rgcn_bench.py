@@ -23,6 +23,12 @@ Four legs (all by default, `--leg cell,step` for some):
             a head record per node -- and the fraction of the 8 TB/s roof.
 An arm counts as faster only if its whole min .. max range lies below the other arm's.
 Run from the repository root:  python tools/rgcn_bench.py [--graphs 5600] [--rounds 9] [--out profiles/rgcn_route.json]
+
+--hidden 128 / 192 / 256 (one or a comma-separated list): the PANEL comparison instead.  Per width two models on the compacted
+route in the same process -- `compact` (compact_rnn True alone: segment sum over the compact rows + ggnn_rnn_f32) and `panel` (plus
+rnn_panel_cell: the one ggnn_rnn_panel_gather_f32 launch) -- through the cell, forward and step legs above, `panel` judged against
+`compact`.  The cell leg adds the panel launch's algorithmic HBM bytes and matrix flops (2 V (nx+1) D^2; six bf16 products per
+exact product) against both roofs.      python tools/rgcn_bench.py --hidden 128,192,256 --out profiles/rgcn_panel.json
 """
 import argparse
 import json
@@ -36,6 +42,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ggnn_amd  # noqa: E402
 from attention_bench import HBM_ROOF, _interleaved  # noqa: E402
+
+MATRIX_ROOF_BF16 = 2.5e15                                   # flop/s of v_mfma_f32_16x16x32_bf16 on the whole chip (tools/dense_bench.py)
+PANEL_ARMS = ("compact", "panel")                           # compact_rnn True alone, plus rnn_panel_cell
 
 ARMS = ("dense", "compact")                                 # key off, key on
 NATIVE = "native"                                           # key 'native': the step leg's third arm
@@ -95,6 +104,118 @@ def cell_leg(a, arms):
                 "max_abs_difference_of_outputs": diff, "max_abs_output": float(results["dense"][0].abs().max()),
                 "fused_bytes_derived": int(bts), "fused_roof_fraction": round(bts / HBM_ROOF / (res["compact"]["median"] * 1e-6), 3)})
     return res
+
+
+def _panel_models(a, hidden):
+    ms = ggnn_amd.synthetic_qm9(a.graphs, mean_nodes=18, seed=0)
+    cfg = dict(README, hidden_size=hidden, batch_size=100000, random_seed=0, compact_rnn=True)
+    arms = {}
+    for name in PANEL_ARMS:
+        model = ggnn_amd.SparseGGNNChemModel({"--quiet": True, "--device": "cuda:0", "train_data": ms, "valid_data": ms,
+                                              "--config": dict(cfg, **({"rnn_panel_cell": True} if name == "panel" else {}))})
+        assert model.rnn_route() and model.rnn_panel_route() == (name == "panel"), name
+        arms[name] = model
+    return arms
+
+
+def panel_cell_leg(a, arms):
+    ops = ggnn_amd.ops
+    model = arms["panel"]
+    feed = next(iter(model.make_minibatch_iterator(model.valid_data, is_training=False)))
+    index, nin = feed["message_index"], feed["num_incoming_edges_per_type"]
+    comp = index._compact
+    V, T, M, R = index.num_nodes, index.num_edge_types, index.num_messages, comp.num_rows
+    D = model._kw
+    assert ops.rnn_panel_supported(D, 1), "the panel cell leg needs a width with the panel cell at nx = 1"
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    h = torch.rand((V, D), device="cuda", generator=gen) * 2 - 1
+    cell = model.gnn_weights.rnn_cells[0]
+    W, b = cell.kernel.detach().contiguous(), cell.bias.detach().contiguous()
+    Hc = ops.msg_transform_compact(h, model.gnn_weights.edge_weights[0].detach().view(T, D, D).contiguous(), comp)
+    packed = ops.rnn_panel_pack(W, 1)
+    act = model.params["graph_rnn_activation"]
+    results = {}
+
+    def composed():
+        inc = ops.gather_segment_sum_compact(Hc, index, comp, nin, None, True)
+        results["compact"] = (ops.rnn([inc], h, W, b, act), inc)
+
+    def panel():
+        save = {}
+        results["panel"] = (ops.rnn_panel_gather([], h, packed, b, Hc, index, comp.gather_row, nin, act, save=save), save["incoming"])
+
+    def panel_inference():
+        ops.rnn_panel_gather([], h, packed, b, Hc, index, comp.gather_row, nin, act)
+    composed(); panel()
+    same_incoming = bool(torch.equal(results["compact"][1], results["panel"][1]))
+    diff = float((results["compact"][0] - results["panel"][0]).abs().max())
+    res = _interleaved({"compact": composed, "panel": panel_inference}, a.iters, a.rounds, unit=1e3, pairs=(PANEL_ARMS,))   # us
+    bts = M * D * 4 + V * 2 * D * 4 + (V + 1) * 4 + M * 4 + V * T * 4
+    flops = 2 * V * 2 * D * D
+    t = res["panel"]["median"] * 1e-6
+    res.update({"unit": "us per node update (compact arm: segment sum over the compact rows + ggnn_rnn_f32; panel arm: the one launch)",
+                "V": V, "M": M, "R": R, "T": T, "D": D, "updates_per_round": a.iters, "incoming_bit_identical": same_incoming,
+                "max_abs_difference_of_outputs": diff, "max_abs_output": float(results["compact"][0].abs().max()),
+                "panel_bytes_derived": int(bts), "panel_hbm_roof_fraction": round(bts / HBM_ROOF / t, 3),
+                "panel_flops_derived": int(flops), "panel_bf16_products_per_product": 6,
+                "panel_matrix_roof_fraction": round(6 * flops / MATRIX_ROOF_BF16 / t, 3)})
+    return res
+
+
+def panel_forward_leg(a, arms):
+    feeds = {n: next(iter(arms[n].make_minibatch_iterator(arms[n].valid_data, is_training=False))) for n in PANEL_ARMS}
+    finals = {}
+
+    def make(n):
+        model = arms[n]
+
+        def run():
+            model.feed(feeds[n])
+            finals[n] = model.compute_final_node_representations()
+        return run
+    with torch.no_grad():
+        fns = {n: make(n) for n in PANEL_ARMS}
+        for fn in fns.values():
+            fn()
+        diff = float((finals["compact"] - finals["panel"]).abs().max())
+        scale = float(finals["compact"].abs().max())
+        res = _interleaved(fns, a.fwd_iters, a.rounds, pairs=(PANEL_ARMS,))
+    V = feeds["compact"]["initial_node_representation"].shape[0]
+    res.update({"unit": "ms per forward", "V": int(V), "timesteps": int(sum(arms["compact"].params["layer_timesteps"])),
+                "forwards_per_round": a.fwd_iters, "max_abs_difference_of_final_states": diff, "max_abs_final_state": scale})
+    return res
+
+
+def panel_step_leg(a, arms):
+    feeds = {}
+    for n, m in arms.items():
+        np.random.seed(0)
+        feeds[n] = dict(next(iter(m.make_minibatch_iterator(m.train_data, is_training=True))), out_layer_dropout_keep_prob=1.0)
+    fns = {n: (lambda n=n: arms[n].train_batch(feeds[n])) for n in arms}
+    res = _interleaved(fns, a.step_iters, a.rounds, pairs=(PANEL_ARMS,), host=True)
+    res.update({"unit": "ms per training step", "V": int(feeds["compact"]["initial_node_representation"].shape[0]),
+                "steps_per_round": a.step_iters, "edge_weight_dropout_keep_prob": feeds["compact"]["edge_weight_dropout_keep_prob"]})
+    return res
+
+
+def panel_main(a, widths):
+    out = {"metric": "sparse GGNN with the BasicRNNCell (R-GCN configuration), synthetic QM9, compacted route: composed cell "
+                     "(compact_rnn alone) vs the column-panel cell (plus rnn_panel_cell)", "graphs": a.graphs, "rounds": a.rounds,
+           "arms": {"compact": "compact_rnn True", "panel": "compact_rnn True, rnn_panel_cell True"}, "widths": {}}
+    legs = {"cell": panel_cell_leg, "forward": panel_forward_leg, "step": panel_step_leg}
+    chosen = list(legs) if a.leg == "all" else a.leg.split(",")
+    assert all(n in legs for n in chosen), "the panel comparison has the legs cell, forward, step (got %r)" % a.leg
+    for hidden in widths:
+        arms = _panel_models(a, hidden)
+        w = out["widths"][str(hidden)] = {"hidden_size": hidden, "layer_timesteps": arms["compact"].params["layer_timesteps"],
+                                          "graph_rnn_activation": arms["compact"].params["graph_rnn_activation"]}
+        for name, leg in legs.items():
+            if name in chosen:
+                w[name] = leg(a, arms)
+        w["panel_faster_on_every_leg"] = all(w[n]["panel_faster"] for n in chosen)
+        del arms
+        torch.cuda.empty_cache()
+    return out
 
 
 def cell_bwd_leg(a, arms):
@@ -203,7 +324,7 @@ def step_leg(a, arms):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=5600)
-    ap.add_argument("--hidden", type=int, default=100)
+    ap.add_argument("--hidden", default="100", help="one hidden size, or 128 / 192 / 256 (a comma-separated list of them): the panel comparison")
     ap.add_argument("--leg", default="all", help="all, or a comma-separated list of cell, cell-bwd, forward, step")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=200)
@@ -212,6 +333,16 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "rgcn_bench needs a GPU"
+    widths = [int(w) for w in str(a.hidden).split(",")]
+    if all(w in (128, 192, 256) for w in widths):
+        line = json.dumps(panel_main(a, widths))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
+    assert len(widths) == 1, "several widths at once: the panel comparison only (128, 192, 256)"
+    a.hidden = widths[0]
     arms = _models(a)
     out = {"metric": "sparse GGNN with the BasicRNNCell (R-GCN configuration), synthetic QM9: dense-transform route (key off) vs "
                      "compacted route (compact_rnn)", "graphs": a.graphs, "hidden_size": a.hidden, "rounds": a.rounds,
