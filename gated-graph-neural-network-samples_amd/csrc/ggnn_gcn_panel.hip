@@ -34,7 +34,7 @@
 namespace ggnn {
 namespace {
 
-constexpr int kGcnPanelNW = 8;                                     // waves per workgroup: one workgroup per CU, 2 waves per SIMD
+constexpr int kGcnPanelNW = kPanelNW;
 
 template <int D>
 using GcnPanelImg = PanelGruSplitCfg<D, kSplitBf16x3>;
@@ -42,11 +42,6 @@ using GcnPanelImg = PanelGruSplitCfg<D, kSplitBf16x3>;
 // a packed layer image: the D / 64 panel images of one weight matrix, back to back
 template <int D>
 constexpr size_t gcn_panel_layer_image_bytes() { return (size_t)PanelCfg<D>::NP * GcnPanelImg<D>::IMG_BYTES; }
-
-// gathered rows in flight per lane while it aggregates: the aggregate is D / 4 registers and so is every row (D = 256: 64 + 2 x 64;
-// 192: 48 + 3 x 48; 128: 32 + 4 x 32).  One more at D = 192 / 256 spills (8 / 28 B of scratch per lane).
-template <int D>
-constexpr int gcn_panel_rows_in_flight() { return D <= 128 ? 4 : (D <= 192 ? 3 : 2); }
 
 template <int D>
 __global__ void gcn_panel_pack_kernel(const float* __restrict__ W, int transpose, float* __restrict__ img) {
@@ -105,28 +100,15 @@ __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
     using C = PanelCfg<D>;
     using SC = GcnPanelImg<D>;
     constexpr int NW = kGcnPanelNW, NP = C::NP, NC = C::NC, PARTS = SC::PARTS, SLOTF = SC::PART, IMGF = SC::IMG;
-    constexpr int RF = gcn_panel_rows_in_flight<D>();
-    extern __shared__ __attribute__((aligned(16))) float ring[];     // [2][PART]
+    extern __shared__ __attribute__((aligned(16))) float ring_lds[];     // [2][PART]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
-    const int n_tiles = (V + 15) / 16;
-    const int base = blockIdx.x * NW, stride = gridDim.x * NW;
-    const int n_pass = base < n_tiles ? (n_tiles - base + stride - 1) / stride : 0;      // (wave 0 has a tile in each)
+    const PanelPassWalk<NW> walk((V + 15) / 16, blockIdx.x, gridDim.x);
+    PanelRing<SC::PART_BYTES, NW> ring{ring_lds, wave, lane};
+    if (walk.n_pass > 0) ring.fill_first(packed);
 
-    int cur = 0;
-    auto dma = [&](const float* src, float* dst) { dma_image_asm<SC::PART_BYTES, NW>(src, dst, wave, lane); };
-    // the barrier of a round in which this wave issued `keep` vector-memory instructions BEHIND its DMA pieces (a panel's stores): the
-    // counter retires in order, so "at most keep outstanding" proves the pieces landed (msg_transform_ring_kernel's publish_keep)
-    auto publish_keep = [&](auto keep_c) {
-        if constexpr (decltype(keep_c)::value == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
-    if (n_pass > 0) dma(packed, ring);
-
-    // ACT: this wave has a tile (else it only feeds the ring and meets the barriers)
-    auto run_pass = [&](auto active_c, int idx, bool first_pass, bool last_pass) {
+    walk.run(wave, [&](auto active_c, int idx, bool first_pass, bool last_pass) {
         constexpr bool ACT = decltype(active_c)::value;
         const int r = idx * 16 + li;
         Frag<D> a;
@@ -139,77 +121,57 @@ __global__ __launch_bounds__(kGcnPanelNW * 64) void gcn_panel_layer_kernel(
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) a.v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-            int k = beg;
-            for (; k + RF <= end; k += RF) gcn_panel_gather<D, RF>(a, x, col, val, k, V, kq);
-            if constexpr (RF > 2) {
-                if (k + 2 <= end) { gcn_panel_gather<D, 2>(a, x, col, val, k, V, kq); k += 2; }
-            }
-            if (k < end) gcn_panel_gather<D, 1>(a, x, col, val, k, V, kq);
+            panel_gather_ladder<D>(beg, end, [&](auto n_c, int k) { gcn_panel_gather<D, decltype(n_c)::value>(a, x, col, val, k, V, kq); });
             if (!BWD && s_out && r < V) {
                 const unsigned ob = ((unsigned)r * (unsigned)D + 4u * (unsigned)kq) * 4u;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) st4_b(s_out, ob + 64u * c, a.v[c]);
             }
         }
-        if (first_pass) { dma_wait(); __syncthreads(); }        // part 0 of panel 0 has landed (later passes: the previous pass's last round)
+        if (first_pass) ring.first_ready();                     // (later passes: the previous pass's last round)
         f32x4 acc[4];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            auto round = [&](auto part_c) {
+            panel_for_parts<PARTS>([&](auto part_c) {
                 constexpr int part = decltype(part_c)::value;
                 const bool more = part + 1 < PARTS || p + 1 < NP || !last_pass;
-                const float* nsrc = part + 1 < PARTS ? packed + (size_t)p * IMGF + (size_t)(part + 1) * SLOTF
-                                                     : packed + (size_t)(p + 1 < NP ? p + 1 : 0) * IMGF;
-                // every wave issues its pieces of the next part FIRST: a part issued behind a burst would not land before the barrier
-                if (more) dma(nsrc, ring + (cur ^ 1) * SLOTF);
-                // BWD: the lane's four gate quads of this panel, issued BEHIND the round's DMA pieces and in front of the burst that
-                // hides them.  publish_keep(4) below still proves the pieces landed, by construction: every st4_b's value is a select
-                // on one of these loads (and on ep.row_key[r], where given), so hipcc's own waits have retired all of them -- and, the
-                // counter being in order, the DMA pieces issued before them -- when the last store is issued; no vector-memory
-                // instruction follows the stores, so "at most 4 outstanding" can only leave the four stores, as in the forward.
-                // A row r >= V loads nothing (and stores nothing); a wave without a tile (ACT = false) issues neither.
                 f32x4 gate[4];
-                if constexpr (BWD && ACT && part == PARTS - 1) {
-                    if (r < V) {
+                panel_round<part, PARTS, ACT, true>(ring, more, panel_next_part<PARTS, IMGF, SLOTF>(packed, p, part, p + 1 < NP ? p + 1 : 0),
+                    [&] {
+                        // BWD: the lane's four gate quads of this panel, issued BEHIND the round's DMA pieces and in front of the burst that
+                        // hides them.  The counted wait below still holds, by construction: every st4_b's value is a select on one of these
+                        // loads (and on ep.row_key[r], where given), so hipcc's own waits have retired all of them when the last store is
+                        // issued, and no vector-memory instruction follows the stores.  A row r >= V loads nothing (and stores nothing).
+                        if constexpr (BWD && part == PARTS - 1) {
+                            if (r < V) {
 #pragma unroll
-                        for (int nt = 0; nt < 4; ++nt)
-                            gate[nt] = ld4_b(gate_out, ((unsigned)r * (unsigned)D + (unsigned)(p * 64 + nt * 16 + 4 * kq)) * 4u);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT) panel_part_mma_split<D, part == 0, false, part, kSplitBf16x3>(acc, a, ring + cur * SLOTF, li, kq);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT && part == PARTS - 1) {
-                    // (every tile has a valid first row: the four stores are issued by every wave with a tile, behind the round's DMA)
-                    if (r < V) {
-                        // (the lane's column passes through an empty asm: without it hipcc hoists the first Philox round of all D / 4
-                        //  column quads out of the pass loop -- 48 registers live across the gather, 44 B of scratch at D = 256)
-                        int kqe = kq;
-                        asm volatile("" : "+v"(kqe));
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const int c0 = p * 64 + nt * 16 + 4 * kqe;
-                            f32x4 v = gcn_epilogue(acc[nt], r, c0, ep);
-                            if constexpr (BWD) v = gcn_relu_gate(v, gate[nt]);
-                            st4_b(out, ((unsigned)r * (unsigned)D + (unsigned)c0) * 4u, v);
+                                for (int nt = 0; nt < 4; ++nt)
+                                    gate[nt] = ld4_b(gate_out, ((unsigned)r * (unsigned)D + (unsigned)(p * 64 + nt * 16 + 4 * kq)) * 4u);
+                            }
                         }
-                    }
-                    publish_keep(std::integral_constant<int, 4>{});
-                } else {
-                    publish_keep(std::integral_constant<int, 0>{});
-                }
-                cur ^= 1;
-            };
-            round(std::integral_constant<int, 0>{});
-            if constexpr (PARTS > 1) round(std::integral_constant<int, 1>{});
-            if constexpr (PARTS > 2) round(std::integral_constant<int, 2>{});
+                        return 0;
+                    },
+                    [&] { panel_part_mma_split<D, part == 0, false, part, kSplitBf16x3>(acc, a, ring.slot(), li, kq); },
+                    [&] {
+                        // (every tile has a valid first row: the four stores are issued by every wave with a tile, behind the round's DMA)
+                        if (r < V) {
+                            // (the lane's column passes through an empty asm: without it hipcc hoists the first Philox round of all D / 4
+                            //  column quads out of the pass loop -- 48 registers live across the gather, 44 B of scratch at D = 256)
+                            int kqe = kq;
+                            asm volatile("" : "+v"(kqe));
+#pragma unroll
+                            for (int nt = 0; nt < 4; ++nt) {
+                                const int c0 = p * 64 + nt * 16 + 4 * kqe;
+                                f32x4 v = gcn_epilogue(acc[nt], r, c0, ep);
+                                if constexpr (BWD) v = gcn_relu_gate(v, gate[nt]);
+                                st4_b(out, ((unsigned)r * (unsigned)D + (unsigned)c0) * 4u, v);
+                            }
+                        }
+                        return 4;
+                    });
+            });
         }
-    };
-    for (int pass = 0; pass < n_pass; ++pass) {
-        const int idx = base + pass * stride + wave;
-        if (idx < n_tiles) run_pass(std::true_type{}, idx, pass == 0, pass + 1 == n_pass);
-        else run_pass(std::false_type{}, idx, pass == 0, pass + 1 == n_pass);
-    }
+    });
 }
 
 template <int D>
@@ -219,22 +181,11 @@ int gcn_panel_pack(const float* W, int transpose, float* img, hipStream_t st) {
     return GGNN_OK;
 }
 
-// workgroups of a launch: one per CU (the ring is 96 KiB at D = 128 / 256 and a wave holds up to 256 registers), no more than passes
-long long gcn_panel_blocks(int V) {
-    const long long n_tiles = (V + 15) / 16;
-    return std::min<long long>((n_tiles + kGcnPanelNW - 1) / kGcnPanelNW, (long long)num_cus());
-}
-
 template <int D, bool BWD = false>
 int gcn_panel_launch(const float* x, const int* row_ptr, const int* col, const float* val, int nnz, const float* img,
                      const GcnEpilogue& ep, float* out, float* s_out, int V, hipStream_t st, const float* gate_out = nullptr) {
-    constexpr size_t lds = (size_t)2 * GcnPanelImg<D>::PART_BYTES;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (lds > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&gcn_panel_layer_kernel<D, BWD>, lds, lds_ok));
-    hipLaunchKernelGGL((gcn_panel_layer_kernel<D, BWD>), dim3((unsigned)gcn_panel_blocks(V)), dim3(kGcnPanelNW * 64), lds, st, x, row_ptr,
-                       col, val, nnz, img, ep, out, s_out, V, gate_out);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    return panel_launch<&gcn_panel_layer_kernel<D, BWD>>((size_t)2 * GcnPanelImg<D>::PART_BYTES, 48 * 1024, panel_blocks(V, kGcnPanelNW), st,
+                                                          x, row_ptr, col, val, nnz, img, ep, out, s_out, V, gate_out);
 }
 
 template <int D>
@@ -250,21 +201,15 @@ int gcn_panel_train_pack(const float* const* W, int L, float* images, hipStream_
 
 int gcn_panel_dispatch(const float* x, const int* row_ptr, const int* col, const float* val, int nnz, const float* img,
                        const GcnEpilogue& ep, float* out, float* s_out, int V, int D, hipStream_t st) {
-    switch (D) {
-        case 256: return gcn_panel_launch<256>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
-        case 192: return gcn_panel_launch<192>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
-        default: return gcn_panel_launch<128>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st);
-    }
+    return panel_for_D(D, [&](auto d) { return gcn_panel_launch<decltype(d)::value>(x, row_ptr, col, val, nnz, img, ep, out, s_out, V, st); });
 }
 
 // the layer backward: out = relu_gate(dropout(A_hat^T (dP W^T)), gate_out)
 int gcn_panel_dispatch_bwd(const float* dP, const int* row_ptr_t, const int* col_t, const float* val_t, int nnz, const float* img_T,
                            const GcnEpilogue& ep, const float* gate_out, float* out, int V, int D, hipStream_t st) {
-    switch (D) {
-        case 256: return gcn_panel_launch<256, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
-        case 192: return gcn_panel_launch<192, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
-        default: return gcn_panel_launch<128, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
-    }
+    return panel_for_D(D, [&](auto d) {
+        return gcn_panel_launch<decltype(d)::value, true>(dP, row_ptr_t, col_t, val_t, nnz, img_T, ep, out, nullptr, V, st, gate_out);
+    });
 }
 
 int gcn_panel_unsupported(int D) {
@@ -276,15 +221,11 @@ int gcn_panel_unsupported(int D) {
 
 using namespace ggnn;
 
-extern "C" int ggnn_gcn_panel_supported(int D) { return D == 128 || D == 192 || D == 256; }
+extern "C" int ggnn_gcn_panel_supported(int D) { return panel_hidden_ok(D); }
 
 extern "C" size_t ggnn_gcn_panel_image_bytes(int D) {
-    switch (D) {
-        case 256: return gcn_panel_layer_image_bytes<256>();
-        case 192: return gcn_panel_layer_image_bytes<192>();
-        case 128: return gcn_panel_layer_image_bytes<128>();
-        default: return 0;
-    }
+    if (!panel_hidden_ok(D)) return 0;
+    return panel_for_D(D, [](auto d) { return gcn_panel_layer_image_bytes<decltype(d)::value>(); });
 }
 
 extern "C" void ggnn_gcn_panel_launch_geometry(int* rows_per_workgroup, int* max_workgroups) {
@@ -295,12 +236,7 @@ extern "C" void ggnn_gcn_panel_launch_geometry(int* rows_per_workgroup, int* max
 extern "C" int ggnn_gcn_panel_pack_weights_f32(const float* W, int D, int transpose, float* img, ggnn_stream_t stream) {
     if (!ggnn_gcn_panel_supported(D)) return gcn_panel_unsupported(D);
     GGNN_CHECK_ARG(W && img && aligned16(img), "null or misaligned pointer");
-    hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 256: return gcn_panel_pack<256>(W, transpose, img, st);
-        case 192: return gcn_panel_pack<192>(W, transpose, img, st);
-        default: return gcn_panel_pack<128>(W, transpose, img, st);
-    }
+    return panel_for_D(D, [&](auto d) { return gcn_panel_pack<decltype(d)::value>(W, transpose, img, (hipStream_t)stream); });
 }
 
 extern "C" int ggnn_gcn_panel_layer_f32(const float* x, const int32_t* row_ptr, const int32_t* col, const float* val, int64_t nnz,
@@ -340,12 +276,7 @@ extern "C" int ggnn_gcn_panel_train_pack_f32(const float* const* W, int num_laye
     if (!ggnn_gcn_panel_supported(D)) return gcn_panel_unsupported(D);
     GGNN_CHECK_ARG(W && images && aligned16(images), "null or misaligned pointer");
     for (int l = 0; l < num_layers; ++l) GGNN_CHECK_ARG(W[l] != nullptr, "null weight pointer of layer %d", l);
-    hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 256: return gcn_panel_train_pack<256>(W, num_layers, images, st);
-        case 192: return gcn_panel_train_pack<192>(W, num_layers, images, st);
-        default: return gcn_panel_train_pack<128>(W, num_layers, images, st);
-    }
+    return panel_for_D(D, [&](auto d) { return gcn_panel_train_pack<decltype(d)::value>(W, num_layers, images, (hipStream_t)stream); });
 }
 
 extern "C" size_t ggnn_gcn_panel_workspace_bytes(int V, int D, int num_layers) {

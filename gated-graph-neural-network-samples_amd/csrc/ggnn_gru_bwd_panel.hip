@@ -57,38 +57,22 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_bwd_panel_kernel(GruBwdArgs 
     constexpr int PARTS = SPLIT ? SC::PARTS : 1;
     constexpr int NP = C::NP, NC = C::NC;
     static_assert(NP >= 2 && NP <= 4, "stage macros cover 2..4 panels");
-    extern __shared__ __attribute__((aligned(16))) float ring[];    // [2][SLOTF]
+    extern __shared__ __attribute__((aligned(16))) float ring_lds[];    // [2][SLOTF]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
     const int nstage = 3 * (a.nx + 1) * NP;
 
-    // tickets: full rounds of NW tiles per workgroup, then the rest spread thin over all workgroups (tail_w tiles each)
-    const int wt_total = (a.V + 15) / 16;
     const int nb = gridDim.x;
-    const int full_tk = wt_total / (NW * nb) * nb;
-    const int rest = wt_total - full_tk * NW;
-    const int tail_w = (rest + nb - 1) / nb;
-    const int n_tk = full_tk + (tail_w ? (rest + tail_w - 1) / tail_w : 0);
-    auto tile_of = [&](int t) -> int {
-        if (t < full_tk) return t * NW + wave;
-        if (t >= n_tk) return -1;
-        const int tl = full_tk * NW + (t - full_tk) * tail_w + wave;
-        return (wave < tail_w && tl < wt_total) ? tl : -1;
-    };
-
-    int cur = 0;
-    auto dma = [&](const float* src, float* dst) {
-        if constexpr (SPLIT) dma_image_asm<SC::PART_BYTES, NW>(src, dst, wave, lane);
-        else dma_block<C::IMG_BYTES, NW>(src, dst, wave, lane);
-    };
-    auto publish = [&]() { if constexpr (SPLIT) dma_wait(); __syncthreads(); };
-    dma(packed, ring);
-    publish();
+    const PanelTickets<NW> tickets(a.V, nb);
+    const int n_tk = tickets.n_tk;
+    PanelRing<SPLIT ? SC::PART_BYTES : C::IMG_BYTES, NW, SPLIT> ring{ring_lds, wave, lane};
+    ring.fill_first(packed);
+    ring.first_ready();
 
     for (int tk = blockIdx.x; tk < n_tk; tk += nb) {
-        const int tile = tile_of(tk);
+        const int tile = tickets.tile_of(tk, wave);
         const bool active = tile >= 0;                                  // wave-uniform
         const bool last_pass = tk + nb >= n_tk;
 
@@ -101,49 +85,26 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_bwd_panel_kernel(GruBwdArgs 
             const int rc = row < a.V ? row : a.V - 1;                   // (always a valid row to read)
 
             u32x4 qh[SPLIT ? SC::NC2 : 1], qm[SPLIT ? SC::NC2 : 1], ql[SPLIT ? SC::NC2 : 1];   // resident planes of the operand fragment
-            auto make_planes = [&](const Frag<D>& A) {
-                if constexpr (SPLIT && ACT) {
-#pragma unroll
-                    for (int c2 = 0; c2 < SC::NC2; ++c2) {
-                        const f32x4 x = A.v[2 * c2], y = A.v[2 * c2 + 1];
-                        unsigned hh[4], mm[4], ll[4];
-                        split_pair(x.x, x.y, hh[0], mm[0], ll[0]); split_pair(x.z, x.w, hh[1], mm[1], ll[1]);
-                        split_pair(y.x, y.y, hh[2], mm[2], ll[2]); split_pair(y.z, y.w, hh[3], mm[3], ll[3]);
-                        qh[c2] = u32x4{hh[0], hh[1], hh[2], hh[3]}; qm[c2] = u32x4{mm[0], mm[1], mm[2], mm[3]}; ql[c2] = u32x4{ll[0], ll[1], ll[2], ll[3]};
-                    }
-                }
-            };
-            // one stage: DMA of the next image (part) into the ring's other slot, the MFMAs on the current one, `after()` (this
-            // wave's loads for the NEXT group of stages: they fly while the partner wave multiplies), the barrier that publishes
+            // one stage: PARTS rounds on one image; `after` = this wave's loads for the NEXT group of stages
             auto stage = [&](auto zero_c, f32x4 (&acc)[4], const Frag<D>& A, int img_idx, auto&& after) {
                 const int nidx = img_idx + 1 < nstage ? img_idx + 1 : 0;
                 const bool more = (img_idx + 1 < nstage) || !last_pass;
-                auto round = [&](auto part_c) {
+                panel_for_parts<PARTS>([&](auto part_c) {
                     constexpr int part = decltype(part_c)::value;
-                    const bool more_p = part + 1 < PARTS || more;
-                    const float* nsrc = part + 1 < PARTS ? packed + (size_t)img_idx * IMGF + (size_t)(part + 1) * SLOTF
-                                                         : packed + (size_t)nidx * IMGF;
-                    if (more_p) dma(nsrc, ring + (cur ^ 1) * SLOTF);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (ACT) {
-                        if constexpr (SPLIT) panel_part_mma_planes<D, decltype(zero_c)::value && part == 0, part>(acc, qh, qm, ql, ring + cur * SLOTF, li, kq);
-                        else panel_mma<D, decltype(zero_c)::value>(acc, A, ring + cur * SLOTF, li, kq);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (ACT) { if constexpr (part == PARTS - 1) after(); }
-                    publish();
-                    cur ^= 1;
-                };
-                round(std::integral_constant<int, 0>{});
-                if constexpr (PARTS > 1) round(std::integral_constant<int, 1>{});
-                if constexpr (PARTS > 2) round(std::integral_constant<int, 2>{});
+                    panel_round<part, PARTS, ACT, false>(ring, part + 1 < PARTS || more,
+                                                         panel_next_part<PARTS, IMGF, SLOTF>(packed, img_idx, part, nidx), [] {},
+                        [&] {
+                            if constexpr (SPLIT) panel_part_mma_planes<D, decltype(zero_c)::value && part == 0, part>(acc, qh, qm, ql, ring.slot(), li, kq);
+                            else panel_mma<D, decltype(zero_c)::value>(acc, A, ring.slot(), li, kq);
+                        }, after);
+                });
             };
             auto nothing = [] {};
             // a group: the resident fragment x the NP panels of one transposed block; `after` runs in the last of its stages
             Frag<D> af;
             f32x4 acc[NP][4];
             auto group = [&](auto zero_c, int img0, auto&& after) {
-                make_planes(af);
+                if constexpr (SPLIT && ACT) frag_to_planes<D>(af, qh, qm, ql);
                 stage(zero_c, acc[0], af, img0, nothing);
                 if constexpr (NP == 2) stage(zero_c, acc[1], af, img0 + 1, after);
                 else {
@@ -292,7 +253,6 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_bwd_panel_kernel(GruBwdArgs 
 template <int D, bool SPLIT>
 static int launch_gru_bwd_panel(const GruBwdArgs& a, const float* Wg, const float* Wc, float* packed, hipStream_t st) {
     using C = PanelCfg<D>;
-    constexpr int NW = 8;
     if (Wg) {
         hipLaunchKernelGGL((gru_bwd_panel_pack_kernel<D, SPLIT>), dim3(8, panel_gru_bwd_images(D, a.nx)), dim3(256), 0, st, Wg, Wc, a.nx, packed);
         GGNN_CHECK_HIP(hipGetLastError());
@@ -301,14 +261,7 @@ static int launch_gru_bwd_panel(const GruBwdArgs& a, const float* Wg, const floa
     if ((unsigned long long)a.V * 2 * D >= (1ULL << 30))
         return fail(GGNN_E_UNSUPPORTED, "fused GRU backward indexes with 32-bit byte offsets: V*2D must be < 2^30 (V=%d, D=%d)", a.V, D);
     const size_t lds = (size_t)2 * (SPLIT ? PanelGruSplitCfg<D>::PART_BYTES : C::IMG_BYTES);
-    const int wt_total = (a.V + 15) / 16;
-    int nb = num_cus();
-    if (nb > wt_total) nb = wt_total;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (lds > 64 * 1024) GGNN_CHECK_HIP((allow_dynamic_lds(&ggnn_gru_bwd_panel_kernel<D, NW, SPLIT>, lds, lds_ok)));
-    hipLaunchKernelGGL((ggnn_gru_bwd_panel_kernel<D, NW, SPLIT>), dim3(nb), dim3(NW * 64), lds, st, a, (const float*)packed);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    return panel_launch<&ggnn_gru_bwd_panel_kernel<D, kPanelNW, SPLIT>>(lds, 64 * 1024, panel_blocks(a.V, 1), st, a, (const float*)packed);
 }
 
 template <int D>
@@ -317,7 +270,7 @@ static int gru_bwd_panel_d(const GruBwdArgs& a, const float* Wg, const float* Wc
     return split_matrix_path() ? launch_gru_bwd_panel<D, true>(a, Wg, Wc, packed, st) : launch_gru_bwd_panel<D, false>(a, Wg, Wc, packed, st);
 }
 
-int gru_bwd_panel_supported(int D) { return D == 128 || D == 192 || D == 256; }
+int gru_bwd_panel_supported(int D) { return panel_hidden_ok(D); }
 
 size_t gru_bwd_panel_packed_bytes(int D, int nx) {
     if (!gru_bwd_panel_supported(D)) return 0;
@@ -327,12 +280,8 @@ size_t gru_bwd_panel_packed_bytes(int D, int nx) {
 }
 
 int gru_bwd_panel_dispatch(int D, const GruBwdArgs& a, const float* Wg, const float* Wc, float* packed, hipStream_t st) {
-    switch (D) {
-        case 128: return gru_bwd_panel_d<128>(a, Wg, Wc, packed, st);
-        case 192: return gru_bwd_panel_d<192>(a, Wg, Wc, packed, st);
-        case 256: return gru_bwd_panel_d<256>(a, Wg, Wc, packed, st);
-        default: return fail(GGNN_E_UNSUPPORTED, "no panel GRU backward for hidden size %d", D);
-    }
+    if (!panel_hidden_ok(D)) return fail(GGNN_E_UNSUPPORTED, "no panel GRU backward for hidden size %d", D);
+    return panel_for_D(D, [&](auto d) { return gru_bwd_panel_d<decltype(d)::value>(a, Wg, Wc, packed, st); });
 }
 
 }  // namespace ggnn

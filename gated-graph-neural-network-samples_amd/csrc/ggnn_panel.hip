@@ -140,6 +140,39 @@ __device__ __forceinline__ f32x4 panel_tanh4(f32x4 z, f32x4 b_scaled) {
     return 1.0f - 2.0f * rcp_4(exp2_4(z * k + b_scaled) + 1.0f);
 }
 
+// h'[:, panel p] = u h + (1 - u) c for the lane's row (< V) from the panel's u and candidate accumulators; bias_s: the kernel's
+// scaled biases [-log2e*bg (2D) | 2 log2e*bc (D) | bc (D)].  The h columns of the panel are fetched here and not a stage ahead: 16
+// more live registers across the r*h stage; the ~0.5k clocks of L2 latency per 65k-clock panel are covered by the partner wave.
+// H_FIRST (the ring passes): all four h quads in flight before the arithmetic; else (the cooperative tail, whose products hold more
+// registers) one quad per tile.
+template <int D, int FMT, bool SAVE, bool H_FIRST>
+__device__ __forceinline__ void gru_panel_epilogue(const GruFusedArgs& a, const float* bias_s, const f32x4 (&acc_u)[4],
+                                                   const f32x4 (&acc_c)[4], int row, int p, int kq) {
+    f32x4 hcol[4];
+    if constexpr (H_FIRST) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) hcol[nt] = ld4_b(a.h, ((unsigned)row * D + p * 64 + nt * 16 + 4 * kq) * 4u);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int col = p * 64 + nt * 16 + 4 * kq;
+        if constexpr (!H_FIRST) hcol[nt] = ld4_b(a.h, ((unsigned)row * D + col) * 4u);
+        const f32x4 u = panel_sigmoid4<FMT>(acc_u[nt], ld4(bias_s + D + col));
+        f32x4 c;
+        if (a.act == GGNN_ACT_TANH) {
+            c = panel_tanh4<FMT>(acc_c[nt], ld4(bias_s + 2 * D + col));
+        } else {
+            c = acc_c[nt] * SplitFmt<FMT>::acc_scale + ld4(bias_s + 3 * D + col);
+            c.x = fmaxf(c.x, 0.f); c.y = fmaxf(c.y, 0.f); c.z = fmaxf(c.z, 0.f); c.w = fmaxf(c.w, 0.f);
+        }
+        st4_b(a.h_out, ((unsigned)row * D + col) * 4u, u * hcol[nt] + (1.0f - u) * c);
+        if constexpr (SAVE) {
+            st4_b(a.save_u, ((unsigned)row * D + col) * 4u, u);
+            st4_b(a.save_c, ((unsigned)row * D + col) * 4u, c);
+        }
+    }
+}
+
 template <int D, int NX, int NW, bool SAVE, bool SPLIT, int FMT = kSplitBf16x3>
 __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a, const float* __restrict__ packed) {
     static_assert(SPLIT || FMT == kSplitBf16x3, "the f32-MFMA kernels have no operand format");
@@ -154,7 +187,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
     extern __shared__ __attribute__((aligned(16))) float lds_[];    // [biases | ring [2][IMG]]
     constexpr int BIAS_FLOATS = (4 * D + 63) / 64 * 64;
     float* bias_s = lds_;                      // [-log2e*bg (2D) | 2 log2e*bc (D) | bc (D)]
-    float* ring = lds_ + BIAS_FLOATS;
+    float* ring_lds = lds_ + BIAS_FLOATS;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -164,38 +197,30 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
     for (int i = tid; i < 4 * D; i += NW * 64)
         bias_s[i] = i < 2 * D ? -kLog2e * a.bg[i] : (i < 3 * D ? 2.0f * kLog2e * a.bc[i - 2 * D] : a.bc[i - 3 * D]);
 
-    // tickets: full rounds of NW tiles per workgroup, then the rest spread thin over all workgroups (tail_w tiles each)
-    const int wt_total = (a.V + 15) / 16;
     const int nb = gridDim.x;
-    const int full_tk = wt_total / (NW * nb) * nb;
-    const int rest = wt_total - full_tk * NW;
-    const int tail_w = (rest + nb - 1) / nb;
-    const int n_tk = full_tk + (tail_w ? (rest + tail_w - 1) / tail_w : 0);
+    const PanelTickets<NW> tickets(a.V, nb);
+    const int full_tk = tickets.full_tk, n_tk = tickets.n_tk;
     // One-tile tail tickets (tail_w == 1, the usual case) are worked COOPERATIVELY: wave p < NP takes panel p of the tile (phase R
     // for its 64 columns, r*h exchanged through LDS, then phase UC for its panel), weights straight from the images in L2 --
     // 3 NS stages on each of NP waves instead of 3 NS NP stages on one wave while seven idle.
-    const bool coop_tail = (tail_w == 1) && (NP <= NW);
+    const bool coop_tail = (tickets.tail_w == 1) && (NP <= NW);
     const int n_main = coop_tail ? full_tk : n_tk;              // tickets [n_main, n_tk) are cooperative tail passes
-    auto tile_of = [&](int t) -> int {
-        if (t < full_tk) return t * NW + wave;
-        if (t >= n_tk) return -1;
-        if (coop_tail) return full_tk * NW + (t - full_tk);     // (every wave: the same tile)
-        const int tl = full_tk * NW + (t - full_tk) * tail_w + wave;
-        return (wave < tail_w && tl < wt_total) ? tl : -1;
-    };
+    auto tile_of = [&](int t) -> int { return tickets.tile_of(t, wave, coop_tail); };
     auto row_of = [&](int t) -> int {          // clamped row of this lane in ticket t (always a valid row to read)
         const int tile = tile_of(t);
         const int r = (tile >= 0 ? tile : 0) * 16 + li;
         return r < a.V ? r : a.V - 1;
     };
 
+    // The ring cursor, the round and the part ladder are PanelRing's, panel_round's and panel_for_parts' (ggnn_panel.hpp) written out:
+    // on the shared forms the three D = 256 SAVE bf16x3 instantiations go from 252-253 to 256 registers and 24-28 B of scratch per lane.
     int cur = 0;
     auto dma = [&](const float* src, float* dst) {
         if constexpr (SPLIT) dma_image_asm<SC::PART_BYTES, NW>(src, dst, wave, lane);
         else dma_block<C::IMG_BYTES, NW>(src, dst, wave, lane);
     };
     auto publish = [&]() { if constexpr (SPLIT) dma_wait(); __syncthreads(); };
-    dma(packed, ring);
+    dma(packed, ring_lds);
     Frag<D> af;                                // the ONE resident activation fragment (segment of the current stage)
     int tk = blockIdx.x;
     if (tk < n_main) load_frag<D>(af, a.x[0], row_of(tk), kq);
@@ -214,47 +239,34 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
         // a diamond whose accumulator phis the register allocator does not coalesce: 296 instead of 230 registers at D = 256.)
         auto run_pass = [&](auto active_c) {
             constexpr bool ACT = decltype(active_c)::value;
-            // one stage: [late waves: DMA of the next image] MFMAs [early waves: DMA]; then `after()` (this wave's loads for
-            // the NEXT stage: they fly while the partner wave multiplies) and the barrier that publishes the next image
+            // one stage: PARTS rounds of [late waves, or all with GGNN_PANEL_DMA_FIRST: DMA of the next part] MFMAs [early waves: DMA];
+            // then `after()` (this wave's loads for the NEXT stage: they fly while the partner wave multiplies) and the barrier
             // Resident planes of the fragment the next stages multiply (GGNN_PANEL_PLANES, split form): phase R multiplies a segment's
             // fragment by NP panels in a row, phase UC multiplies an x segment's by its u and candidate panels back to back -- the
             // fragment is split ONCE for such a run (10 of the 24 splits of an NX = 1 pass go) and its f32 registers are free for
             // the next fragment's loads; stages that multiply a fragment once (h -> u, r*h -> c) split chunk by chunk as before.
             constexpr bool PLANES = SPLIT && GGNN_PANEL_PLANES;
             u32x4 qh[PLANES ? SC::NC2 : 1], qm[PLANES ? SC::NC2 : 1], ql[PLANES ? SC::NC2 : 1];
-            auto make_planes = [&](const Frag<D>& A) {
-                if constexpr (PLANES && ACT) {
-#pragma unroll
-                    for (int c2 = 0; c2 < SC::NC2; ++c2) {
-                        const f32x4 x = A.v[2 * c2], y = A.v[2 * c2 + 1];
-                        unsigned hh[4], mm[4], ll[4];
-                        split_pair<FMT>(x.x, x.y, hh[0], mm[0], ll[0]); split_pair<FMT>(x.z, x.w, hh[1], mm[1], ll[1]);
-                        split_pair<FMT>(y.x, y.y, hh[2], mm[2], ll[2]); split_pair<FMT>(y.z, y.w, hh[3], mm[3], ll[3]);
-                        qh[c2] = u32x4{hh[0], hh[1], hh[2], hh[3]}; qm[c2] = u32x4{mm[0], mm[1], mm[2], mm[3]}; ql[c2] = u32x4{ll[0], ll[1], ll[2], ll[3]};
-                    }
-                }
-            };
+            auto make_planes = [&](const Frag<D>& A) { if constexpr (PLANES && ACT) frag_to_planes<D, FMT>(A, qh, qm, ql); };
             auto stage = [&](auto zero_c, f32x4 (&acc)[4], const Frag<D>& A, int img_idx, auto&& after, auto planes_c) {
                 constexpr bool USEP = PLANES && decltype(planes_c)::value;
                 const int nidx = img_idx + 1 < NSTAGE ? img_idx + 1 : 0;
                 const bool more = (img_idx + 1 < NSTAGE) || !last_pass;
                 auto round = [&](auto part_c) {
                     constexpr int part = decltype(part_c)::value;
-                    // what the ring's other slot receives during this round: the next part of this image, or the first of the next
+                    constexpr bool ZERO = decltype(zero_c)::value && part == 0;
                     const bool more_p = part + 1 < PARTS || more;
-                    const float* nsrc = part + 1 < PARTS ? packed + (size_t)img_idx * IMGF + (size_t)(part + 1) * SLOTF
-                                                         : packed + (size_t)nidx * IMGF;
-                    float* ndst = ring + (cur ^ 1) * SLOTF;
+                    const float* nsrc = panel_next_part<PARTS, IMGF, SLOTF>(packed, img_idx, part, nidx);
                     const bool dma_first = late || GGNN_PANEL_DMA_FIRST;
-                    if (dma_first && more_p) dma(nsrc, ndst);
+                    if (dma_first && more_p) dma(nsrc, ring_lds + (cur ^ 1) * SLOTF);
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (ACT) {
-                        if constexpr (USEP) panel_part_mma_planes<D, decltype(zero_c)::value && part == 0, part, FMT>(acc, qh, qm, ql, ring + cur * SLOTF, li, kq);
-                        else if constexpr (SPLIT) panel_part_mma_split<D, decltype(zero_c)::value && part == 0, false, part, FMT>(acc, A, ring + cur * SLOTF, li, kq);
-                        else panel_mma<D, decltype(zero_c)::value>(acc, A, ring + cur * SLOTF, li, kq);
+                        if constexpr (USEP) panel_part_mma_planes<D, ZERO, part, FMT>(acc, qh, qm, ql, ring_lds + cur * SLOTF, li, kq);
+                        else if constexpr (SPLIT) panel_part_mma_split<D, ZERO, false, part, FMT>(acc, A, ring_lds + cur * SLOTF, li, kq);
+                        else panel_mma<D, decltype(zero_c)::value>(acc, A, ring_lds + cur * SLOTF, li, kq);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!dma_first && more_p) dma(nsrc, ndst);
+                    if (!dma_first && more_p) dma(nsrc, ring_lds + (cur ^ 1) * SLOTF);
                     if constexpr (ACT) { if constexpr (part == PARTS - 1) after(); }
                     publish();
                     cur ^= 1;
@@ -315,32 +327,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
                 auto after_h = [&] { load_frag<D>(af, a.x[0], last_panel ? rown : rowc, kq); };
                 stage(std::false_type{}, acc_u, af, img0 + 2 * NX, after_h, std::false_type{});
                 stage(std::false_type{}, acc_c, rh, img0 + 2 * NX + 1, nothing, std::false_type{});
-                if constexpr (ACT) {
-                    if (row < a.V) {
-                        // (the h columns of this panel are fetched here, not a stage ahead: 16 more live registers across the
-                        //  r*h stage; the ~0.5k clocks of L2 latency per 65k-clock panel are covered by the partner wave)
-                        f32x4 hcol[4];
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) hcol[nt] = ld4_b(a.h, ((unsigned)row * D + p * 64 + nt * 16 + 4 * kq) * 4u);
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const int col = p * 64 + nt * 16 + 4 * kq;
-                            const f32x4 u = panel_sigmoid4<FMT>(acc_u[nt], ld4(bias_s + D + col));
-                            f32x4 c;
-                            if (a.act == GGNN_ACT_TANH) {
-                                c = panel_tanh4<FMT>(acc_c[nt], ld4(bias_s + 2 * D + col));
-                            } else {
-                                c = acc_c[nt] * SplitFmt<FMT>::acc_scale + ld4(bias_s + 3 * D + col);
-                                c.x = fmaxf(c.x, 0.f); c.y = fmaxf(c.y, 0.f); c.z = fmaxf(c.z, 0.f); c.w = fmaxf(c.w, 0.f);
-                            }
-                            st4_b(a.h_out, ((unsigned)row * D + col) * 4u, u * hcol[nt] + (1.0f - u) * c);
-                            if constexpr (SAVE) {
-                                st4_b(a.save_u, ((unsigned)row * D + col) * 4u, u);
-                                st4_b(a.save_c, ((unsigned)row * D + col) * 4u, c);
-                            }
-                        }
-                    }
-                }
+                if constexpr (ACT) { if (row < a.V) gru_panel_epilogue<D, FMT, SAVE, true>(a, bias_s, acc_u, acc_c, row, p, kq); }
             }
         };
         if (active) run_pass(std::true_type{});
@@ -355,7 +342,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
         const int rowc = row < a.V ? row : a.V - 1;
         const int p = wave;                                     // this wave's panel
         const bool on = p < NP;
-        float* rh_x = ring;
+        float* rh_x = ring_lds;
         auto gimg = [&](int img_idx) { return packed + (size_t)img_idx * IMGF; };
         auto gmma = [&](auto zero_c, f32x4 (&acc)[4], const Frag<D>& A, const float* img) {     // whole image, straight from L2
             if constexpr (SPLIT) {
@@ -402,26 +389,7 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
             load_frag<D>(af, a.h, rowc, kq);
             gmma(std::false_type{}, acc_u, af, gimg(img0 + 2 * NX));
             gmma(std::false_type{}, acc_c, rh, gimg(img0 + 2 * NX + 1));
-            if (row < a.V) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const int col = p * 64 + nt * 16 + 4 * kq;
-                    const f32x4 hcol = ld4_b(a.h, ((unsigned)row * D + col) * 4u);
-                    const f32x4 u = panel_sigmoid4<FMT>(acc_u[nt], ld4(bias_s + D + col));
-                    f32x4 c;
-                    if (a.act == GGNN_ACT_TANH) {
-                        c = panel_tanh4<FMT>(acc_c[nt], ld4(bias_s + 2 * D + col));
-                    } else {
-                        c = acc_c[nt] * SplitFmt<FMT>::acc_scale + ld4(bias_s + 3 * D + col);
-                        c.x = fmaxf(c.x, 0.f); c.y = fmaxf(c.y, 0.f); c.z = fmaxf(c.z, 0.f); c.w = fmaxf(c.w, 0.f);
-                    }
-                    st4_b(a.h_out, ((unsigned)row * D + col) * 4u, u * hcol + (1.0f - u) * c);
-                    if constexpr (SAVE) {
-                        st4_b(a.save_u, ((unsigned)row * D + col) * 4u, u);
-                        st4_b(a.save_c, ((unsigned)row * D + col) * 4u, c);
-                    }
-                }
-            }
+            if (row < a.V) gru_panel_epilogue<D, FMT, SAVE, false>(a, bias_s, acc_u, acc_c, row, p, kq);
         }
     }
 }
@@ -429,7 +397,6 @@ __global__ __launch_bounds__(NW * 64) void ggnn_gru_panel_kernel(GruFusedArgs a,
 template <int D, int NX, bool SAVE, bool SPLIT, int FMT = kSplitBf16x3>
 static int launch_gru_panel_m(const GruFusedArgs& a_in, float* packed, hipStream_t st) {
     using C = PanelCfg<D>;
-    constexpr int NW = 8;
     GruFusedArgs a = a_in;
     if (a.Wg) {   // raw weights given: build the stage images first
         hipLaunchKernelGGL((gru_panel_pack_kernel<D, SPLIT, FMT>), dim3(8, panel_gru_images(D, NX)), dim3(256), 0, st, a.Wg, a.Wc, NX, packed);
@@ -442,26 +409,17 @@ static int launch_gru_panel_m(const GruFusedArgs& a_in, float* packed, hipStream
     size_t ringb = (size_t)2 * (SPLIT ? PanelGruSplitCfg<D, FMT>::PART_BYTES : C::IMG_BYTES);
     if (ringb < (size_t)16 * (D + 4) * sizeof(float)) ringb = (size_t)16 * (D + 4) * sizeof(float);
     const size_t lds = ringb + (size_t)((4 * D + 63) / 64 * 64) * sizeof(float);
-    const int wt_total = (a.V + 15) / 16;
-    int nb = num_cus();
-    if (nb > wt_total) nb = wt_total;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (lds > 64 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&ggnn_gru_panel_kernel<D, NX, NW, SAVE, SPLIT, FMT>, lds, lds_ok));
-    hipLaunchKernelGGL((ggnn_gru_panel_kernel<D, NX, NW, SAVE, SPLIT, FMT>), dim3(nb), dim3(NW * 64), lds, st, a, (const float*)packed);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    return panel_launch<&ggnn_gru_panel_kernel<D, NX, kPanelNW, SAVE, SPLIT, FMT>>(lds, 64 * 1024, panel_blocks(a.V, 1), st, a, (const float*)packed);
 }
 
-int gru_panel_supported(int D) { return D == 128 || D == 192 || D == 256; }
+int gru_panel_supported(int D) { return panel_hidden_ok(D); }
 
 int gru_panel_pack_floats(int D, int nx) {
     if (!gru_panel_supported(D)) return 0;
     // (sized for either operand format of the split form: the larger of the two image sizes)
-    auto mx = [](int a, int b) { return a > b ? a : b; };
-    const int img = !split_matrix_path() ? D * 64
-                  : (D == 128 ? mx(PanelGruSplitCfg<128>::IMG, PanelGruSplitCfg<128, kSplitF16x2>::IMG)
-                     : (D == 192 ? mx(PanelGruSplitCfg<192>::IMG, PanelGruSplitCfg<192, kSplitF16x2>::IMG)
-                                 : mx(PanelGruSplitCfg<256>::IMG, PanelGruSplitCfg<256, kSplitF16x2>::IMG)));
+    const int img = !split_matrix_path() ? D * 64 : panel_for_D(D, [](auto d) {
+        return std::max(PanelGruSplitCfg<decltype(d)::value>::IMG, PanelGruSplitCfg<decltype(d)::value, kSplitF16x2>::IMG);
+    });
     return panel_gru_images(D, nx) * img;
 }
 
@@ -484,6 +442,25 @@ struct PanelRows {
     int wg_off[kMaxTypesP + 1];        // workgroups of type t (all its panels): wg_off[t] .. wg_off[t+1]-1, a multiple of NP each
     int T;
 };
+
+// the types' compact rows row_off[0 .. T] and `mult` x n workgroups for a type, n in proportion to its rows out of `budget` for all types
+// together: no more than it has passes of kPanelNW tiles, at least one where it has rows
+static PanelRows panel_rows(const int* row_off, int T, int budget, int mult) {
+    PanelRows pr{};
+    pr.T = T;
+    const int R = row_off[T];
+    for (int t = 0; t < T; ++t) {
+        pr.row_off[t] = row_off[t];
+        const long long rows = row_off[t + 1] - row_off[t];
+        long long n = rows * budget / R;
+        const long long rounds = (rows + 16 * kPanelNW - 1) / (16 * kPanelNW);
+        if (n > rounds) n = rounds;
+        if (rows > 0 && n < 1) n = 1;
+        pr.wg_off[t + 1] = pr.wg_off[t] + (int)n * mult;
+    }
+    pr.row_off[T] = R;
+    return pr;
+}
 
 // workgroup (type t, panel p, j-th of the type's workgroups on that panel): keeps image (t, p) in LDS and walks 16-row tiles
 // j*NW + wave, + stride, ... of the type's active pairs; the rows of tile k+1 are fetched under the MFMAs of tile k.
@@ -554,61 +531,34 @@ __global__ __launch_bounds__(NW * 64) void msg_transform_ring_kernel(const float
     using C = PanelCfg<D>;
     using SC = PanelGruSplitCfg<D, FMT>;
     constexpr int NP = C::NP, PARTS = SC::PARTS, SLOTF = SC::PART, IMGF = SC::IMG, NC2 = SC::NC2;
-    extern __shared__ __attribute__((aligned(16))) float ring[];     // [2][PART]
+    extern __shared__ __attribute__((aligned(16))) float ring_lds[];     // [2][PART]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
     int t = 0;
     while (t + 1 < pr.T && (int)blockIdx.x >= pr.wg_off[t + 1]) ++t;
-    const int j = (int)blockIdx.x - pr.wg_off[t];
-    const int stride = (pr.wg_off[t + 1] - pr.wg_off[t]) * NW;
     const int row_beg = pr.row_off[t], row_end = pr.row_off[t + 1];
     const int n_wt = (row_end - row_beg + 15) / 16;
-    const int n_pass = j * NW < n_wt ? (n_wt - j * NW + stride - 1) / stride : 0;     // passes of this workgroup (its wave 0 has a tile in each)
-    int idx = j * NW + wave;
+    const PanelPassWalk<NW> walk(n_wt, (int)blockIdx.x - pr.wg_off[t], pr.wg_off[t + 1] - pr.wg_off[t]);
+    const int stride = walk.stride, idx0 = walk.base + wave;
     const float* timg = packed + (size_t)t * NP * IMGF;
 
     auto row_of = [&](int i) { const int r = row_beg + i * 16 + li; return r < row_end ? r : row_end - 1; };
-    int cur = 0;
-    auto dma = [&](const float* src, float* dst) { dma_image_asm<SC::PART_BYTES, NW>(src, dst, wave, lane); };
-    auto publish = [&]() { dma_wait(); __syncthreads(); };
-    // the barrier of a round in which this wave issued `keep` vector-memory instructions BEHIND its DMA pieces (the next tile's rows,
-    // a panel's stores): the counter retires in order, so "at most keep outstanding" proves the pieces landed and leaves the rest in
-    // flight across the barrier (they have until the next round's barrier)
-    auto publish_keep = [&](int keep) {
-        switch (keep) {                                              // (wave-uniform; s_waitcnt takes an immediate)
-#define GGNN_WC(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); break;
-            GGNN_WC(0) GGNN_WC(1) GGNN_WC(2) GGNN_WC(3) GGNN_WC(4) GGNN_WC(5) GGNN_WC(6) GGNN_WC(7) GGNN_WC(8) GGNN_WC(9) GGNN_WC(10)
-            GGNN_WC(11) GGNN_WC(12) GGNN_WC(13) GGNN_WC(14) GGNN_WC(15) GGNN_WC(16) GGNN_WC(17) GGNN_WC(18) GGNN_WC(19) GGNN_WC(20)
-            GGNN_WC(21) GGNN_WC(22) GGNN_WC(23) GGNN_WC(24) GGNN_WC(25) GGNN_WC(26)
-#undef GGNN_WC
-            default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
-        }
-        __builtin_amdgcn_s_barrier();
-    };
-    static_assert(C::NC == 8 || C::NC == 12 || C::NC == 16, "publish_keep knows the row-load counts of D = 128 / 192 / 256");
+    PanelRing<SC::PART_BYTES, NW> ring{ring_lds, wave, lane};
+    static_assert(C::NC <= 16, "PanelRing's counted waits cover a fragment's row loads + a panel's stores up to D = 256");
     Frag<D> a;
     int node_n = 0;
-    if (n_pass > 0) dma(timg, ring);
-    if (idx < n_wt) load_frag<D>(a, h, pair_node[row_of(idx)], kq);
-    if (idx + stride < n_wt) node_n = pair_node[row_of(idx + stride)];
-    publish();
+    if (walk.n_pass > 0) ring.fill_first(timg);
+    if (idx0 < n_wt) load_frag<D>(a, h, pair_node[row_of(idx0)], kq);
+    if (idx0 + stride < n_wt) node_n = pair_node[row_of(idx0 + stride)];
+    ring.first_ready();
 
-    // the rounds of one pass: NP panels x PARTS parts; ACT: this wave has a tile (else it only feeds the ring and meets the barriers)
-    auto run_pass = [&](auto active_c, bool last_pass) {
+    // the rounds of one pass: NP panels x PARTS parts
+    walk.run(wave, [&](auto active_c, int idx, bool, bool last_pass) {
         constexpr bool ACT = decltype(active_c)::value;
         u32x4 ph[NC2], pm[NC2], pl[NC2];
         const int r = row_beg + idx * 16 + li;
-        if constexpr (ACT) {
-#pragma unroll
-            for (int c2 = 0; c2 < NC2; ++c2) {
-                const f32x4 x = a.v[2 * c2], y = a.v[2 * c2 + 1];
-                unsigned hh[4], mm[4], ll[4];
-                split_pair<FMT>(x.x, x.y, hh[0], mm[0], ll[0]); split_pair<FMT>(x.z, x.w, hh[1], mm[1], ll[1]);
-                split_pair<FMT>(y.x, y.y, hh[2], mm[2], ll[2]); split_pair<FMT>(y.z, y.w, hh[3], mm[3], ll[3]);
-                ph[c2] = u32x4{hh[0], hh[1], hh[2], hh[3]}; pm[c2] = u32x4{mm[0], mm[1], mm[2], mm[3]}; pl[c2] = u32x4{ll[0], ll[1], ll[2], ll[3]};
-            }
-        }
+        if constexpr (ACT) frag_to_planes<D, FMT>(a, ph, pm, pl);
         // the next tile's rows go into the fragment's registers (dead now) in the pass's first round, BEHIND the round's DMA
         const bool has_next = ACT && idx + stride < n_wt;
         const int node_next = node_n;
@@ -616,40 +566,29 @@ __global__ __launch_bounds__(NW * 64) void msg_transform_ring_kernel(const float
         f32x4 acc[4];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            auto round = [&](auto part_c) {
+            panel_for_parts<PARTS>([&](auto part_c) {
                 constexpr int part = decltype(part_c)::value;
                 const bool more = part + 1 < PARTS || p + 1 < NP || !last_pass;
-                const float* nsrc = part + 1 < PARTS ? timg + (size_t)p * IMGF + (size_t)(part + 1) * SLOTF
-                                                     : timg + (size_t)(p + 1 < NP ? p + 1 : 0) * IMGF;
-                // Every wave issues its pieces of the next part FIRST (a round is ~3k clocks of MFMAs for the SIMD's two waves: a part
-                // issued behind a burst would not land before the round's barrier), then -- first round of a pass -- the next tile's rows.
-                int keep = 0;
-                if (more) dma(nsrc, ring + (cur ^ 1) * SLOTF);
-                if constexpr (ACT) { if (p == 0 && part == 0 && has_next) { load_frag<D>(a, h, node_next, kq); keep += C::NC; } }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT) panel_part_mma_planes<D, part == 0, part, FMT>(acc, ph, pm, pl, ring + cur * SLOTF, li, kq);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT && part == PARTS - 1) {
-                    // (every tile has a valid first row: the four stores are issued by every wave with a tile)
-                    if (r < row_end) {
+                // (a round is ~3k clocks of MFMAs for the SIMD's two waves.)  The rows and the stores are issued BEHIND the round's DMA
+                // pieces and nothing follows them: they may stay in flight across the barrier.
+                panel_round<part, PARTS, ACT, true>(ring, more, panel_next_part<PARTS, IMGF, SLOTF>(timg, p, part, p + 1 < NP ? p + 1 : 0),
+                    [&] {
+                        if (!(p == 0 && part == 0 && has_next)) return 0;
+                        load_frag<D>(a, h, node_next, kq);
+                        return C::NC;
+                    },
+                    [&] { panel_part_mma_planes<D, part == 0, part, FMT>(acc, ph, pm, pl, ring.slot(), li, kq); },
+                    [&] {
+                        // (every tile has a valid first row: the four stores are issued by every wave with a tile)
+                        if (r < row_end) {
 #pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) st4_b(Hc, ((unsigned)r * (unsigned)D + p * 64 + nt * 16 + 4 * kq) * 4u, acc[nt] * SplitFmt<FMT>::acc_scale);
-                    }
-                    keep += 4;
-                }
-                // the rows / the stores were issued BEHIND the round's DMA pieces: they may stay in flight across the barrier
-                publish_keep(keep);
-                cur ^= 1;
-            };
-            round(std::integral_constant<int, 0>{});
-            if constexpr (PARTS > 1) round(std::integral_constant<int, 1>{});
-            if constexpr (PARTS > 2) round(std::integral_constant<int, 2>{});
+                            for (int nt = 0; nt < 4; ++nt) st4_b(Hc, ((unsigned)r * (unsigned)D + p * 64 + nt * 16 + 4 * kq) * 4u, acc[nt] * SplitFmt<FMT>::acc_scale);
+                        }
+                        return 4;
+                    });
+            });
         }
-        idx += stride;
-    };
-    int pass = 0;
-    for (; pass < n_pass && idx < n_wt; ++pass) run_pass(std::true_type{}, pass + 1 == n_pass);
-    for (; pass < n_pass; ++pass) run_pass(std::false_type{}, pass + 1 == n_pass);
+    });
 }
 
 // GGNN_PANEL_TRANSFORM: 1 (default) the ring kernel above (split path only), 0 the stationary-image kernel.  Read once: the packed
@@ -677,12 +616,8 @@ static_assert(PanelGruSplitCfg<256>::IMG == PanelSplitCfg<256>::IMG && PanelGruS
 // floats of ONE (type, panel) image of the transform, in the process's matrix path
 int transform_panel_image_floats(int D) {
     const bool sp = split_matrix_path();
-    switch (D) {
-        case 128: return sp ? PanelSplitCfg<128>::IMG : PanelCfg<128>::IMG;
-        case 192: return sp ? PanelSplitCfg<192>::IMG : PanelCfg<192>::IMG;
-        case 256: return sp ? PanelSplitCfg<256>::IMG : PanelCfg<256>::IMG;
-        default: return 0;
-    }
+    if (!panel_hidden_ok(D)) return 0;
+    return panel_for_D(D, [&](auto d) { return sp ? PanelSplitCfg<decltype(d)::value>::IMG : PanelCfg<decltype(d)::value>::IMG; });
 }
 
 // FMT: only the ring kernel (split path) has the two-piece f16 form; the stationary-image kernel and the f32 path ignore it
@@ -690,7 +625,7 @@ template <int D, bool SPLIT, int FMT = kSplitBf16x3>
 static int launch_transform_panel_m(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V,
                                   float* packed, float* Hc, hipStream_t st) {
     using C = PanelCfg<D>;
-    constexpr int NW = 8, NP = C::NP;
+    constexpr int NP = C::NP;
     if (W) {
         hipLaunchKernelGGL((edge_weight_panel_pack_kernel<D, SPLIT, FMT>), dim3(8, T * NP), dim3(256), 0, st, W, packed, (int)(SPLIT && transform_ring()));
         GGNN_CHECK_HIP(hipGetLastError());
@@ -699,53 +634,19 @@ static int launch_transform_panel_m(const float* h, const float* W, const int* p
     if (R == 0 || h == nullptr) return GGNN_OK;
     if ((unsigned long long)R * D >= (1ULL << 30) || (unsigned long long)V * D >= (1ULL << 30))
         return fail(GGNN_E_UNSUPPORTED, "compacted transform indexes with 32-bit byte offsets: rows*D and V*D must be < 2^30");
-    // one workgroup per CU (64 KiB image + ~176 VGPRs per wave); every type gets workgroups in proportion to its rows,
-    // the same number on each of its NP panels, at least one per panel, no more than it has 8-tile rounds
-    PanelRows pr{};
-    pr.T = T;
-    const int budget = num_cus() / NP > 0 ? num_cus() / NP : 1;          // workgroups per panel, all types together
-    pr.wg_off[0] = 0;
-    for (int t = 0; t < T; ++t) {
-        pr.row_off[t] = row_off[t];
-        const long long rows = row_off[t + 1] - row_off[t];
-        long long n = rows * budget / R;
-        const long long rounds = (rows + 16 * NW - 1) / (16 * NW);
-        if (n > rounds) n = rounds;
-        if (rows > 0 && n < 1) n = 1;
-        pr.wg_off[t + 1] = pr.wg_off[t] + (int)n * NP;
-    }
-    pr.row_off[T] = R;
     if constexpr (SPLIT) {
         if (transform_ring()) {
-            // workgroups per type in proportion to its rows (one per CU all types together), no more than it has 8-tile passes
-            PanelRows rr{};
-            rr.T = T; rr.wg_off[0] = 0;
-            for (int t = 0; t < T; ++t) {
-                rr.row_off[t] = row_off[t];
-                const long long rows = row_off[t + 1] - row_off[t];
-                long long n = rows * num_cus() / R;
-                const long long rounds = (rows + 16 * NW - 1) / (16 * NW);
-                if (n > rounds) n = rounds;
-                if (rows > 0 && n < 1) n = 1;
-                rr.wg_off[t + 1] = rr.wg_off[t] + (int)n;
-            }
-            rr.row_off[T] = R;
-            static std::atomic<unsigned long long> lds_ok_r{0};
-            constexpr size_t lds_r = (size_t)2 * PanelGruSplitCfg<D, FMT>::PART_BYTES;
-            if (lds_r > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&msg_transform_ring_kernel<D, NW, FMT>, lds_r, lds_ok_r));
-            hipLaunchKernelGGL((msg_transform_ring_kernel<D, NW, FMT>), dim3(rr.wg_off[T]), dim3(NW * 64), lds_r, st, h, pair_node, rr,
-                               (const float*)packed, Hc);
-            GGNN_CHECK_HIP(hipGetLastError());
-            return GGNN_OK;
+            // workgroups per type in proportion to its rows (one per CU all types together)
+            const PanelRows rr = panel_rows(row_off, T, num_cus(), 1);
+            return panel_launch<&msg_transform_ring_kernel<D, kPanelNW, FMT>>((size_t)2 * PanelGruSplitCfg<D, FMT>::PART_BYTES, 48 * 1024,
+                                                                               rr.wg_off[T], st, h, pair_node, rr, (const float*)packed, Hc);
         }
     }
-    static std::atomic<unsigned long long> lds_ok{0};
-    constexpr size_t lds = SPLIT ? PanelSplitCfg<D>::IMG_BYTES : C::IMG_BYTES;
-    if (lds > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&msg_transform_panel_kernel<D, NW, SPLIT>, lds, lds_ok));
-    hipLaunchKernelGGL((msg_transform_panel_kernel<D, NW, SPLIT>), dim3(pr.wg_off[T]), dim3(NW * 64), lds, st, h, pair_node, pr,
-                       (const float*)packed, Hc);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    // one workgroup per CU (64 KiB image + ~176 VGPRs per wave); every type gets workgroups in proportion to its rows,
+    // the same number on each of its NP panels, at least one per panel
+    const PanelRows pr = panel_rows(row_off, T, num_cus() / NP > 0 ? num_cus() / NP : 1, NP);
+    return panel_launch<&msg_transform_panel_kernel<D, kPanelNW, SPLIT>>(SPLIT ? PanelSplitCfg<D>::IMG_BYTES : C::IMG_BYTES, 48 * 1024,
+                                                                          pr.wg_off[T], st, h, pair_node, pr, (const float*)packed, Hc);
 }
 
 template <int D>
@@ -761,12 +662,8 @@ static int launch_transform_panel(const float* h, const float* W, const int* pai
 int transform_panel_dispatch(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V, int D,
                              float* packed, float* Hc, int fmt, hipStream_t st) {
     if (T > kMaxTypesP) return fail(GGNN_E_UNSUPPORTED, "more than %d edge types", kMaxTypesP);
-    switch (D) {
-        case 128: return launch_transform_panel<128>(h, W, pair_node, row_off, T, V, packed, Hc, fmt, st);
-        case 192: return launch_transform_panel<192>(h, W, pair_node, row_off, T, V, packed, Hc, fmt, st);
-        case 256: return launch_transform_panel<256>(h, W, pair_node, row_off, T, V, packed, Hc, fmt, st);
-        default: return fail(GGNN_E_UNSUPPORTED, "no panel transform for hidden size %d", D);
-    }
+    if (!panel_hidden_ok(D)) return fail(GGNN_E_UNSUPPORTED, "no panel transform for hidden size %d", D);
+    return panel_for_D(D, [&](auto d) { return launch_transform_panel<decltype(d)::value>(h, W, pair_node, row_off, T, V, packed, Hc, fmt, st); });
 }
 
 }  // namespace ggnn

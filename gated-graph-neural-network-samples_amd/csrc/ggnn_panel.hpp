@@ -1,6 +1,12 @@
-// Building blocks of the column-panel kernels for hidden sizes 128 / 192 / 256 (ggnn_panel.hip: forward GRU and transform;
-// ggnn_gru_bwd_panel.hip: GRU backward): panel geometry, the f32 and chunk-major split image formats, the stage products and the
-// LDS-DMA of an image.  See the header comment of ggnn_panel.hip.
+// The shared layer of the column-panel kernels for hidden sizes 128 / 192 / 256.  Its five users:
+//     ggnn_gru_panel_kernel, msg_transform_ring_kernel (ggnn_panel.hip)    forward GRU, compacted transform
+//     ggnn_gru_bwd_panel_kernel (ggnn_gru_bwd_panel.hip)                   GRU backward
+//     gcn_panel_layer_kernel (ggnn_gcn_panel.hip)                          GCN layer, forward and BWD
+//     rnn_panel_kernel (ggnn_rnn_panel.hip)                                R-GCN cell
+// Each multiplies a wave's 16 x D fragment by 64-column panel images that stream through a two-slot LDS-DMA ring.  Here: the panel
+// geometry, the f32 and chunk-major split image formats, the stage products and the image DMA; the ring and its publishing barriers
+// (PanelRing), the round and the part ladder (panel_round, panel_for_parts), the pass and ticket walks (PanelPassWalk, PanelTickets),
+// the rows-in-flight gather ladder, and the host side of a launch.  See the header comment of ggnn_panel.hip.
 #pragma once
 #include "ggnn_split.hpp"
 // 1: panel_part_mma_split recomputes the lane part of its LDS / L2 addresses in every call (the lane coordinates pass through an empty asm).
@@ -151,16 +157,31 @@ __device__ __forceinline__ PanelSrc<true> panel_gru_bwd_image_src(const float* W
     return {w == 0 ? Wc : Wg, w == 2 ? D : 0, seg * D + p * C::BN, w == 0 ? D : 2 * D};
 }
 
+// the 8 values of a fragment's 32-chunk (two quads) -> one quad per plane
+template <int FMT = kSplitBf16x3>
+__device__ __forceinline__ void chunk_planes(f32x4 x, f32x4 y, u32x4& hi, u32x4& mid, u32x4& lo) {
+    unsigned h[4], m[4], l[4];
+    split_pair<FMT>(x.x, x.y, h[0], m[0], l[0]); split_pair<FMT>(x.z, x.w, h[1], m[1], l[1]);
+    split_pair<FMT>(y.x, y.y, h[2], m[2], l[2]); split_pair<FMT>(y.z, y.w, h[3], m[3], l[3]);
+    hi = u32x4{h[0], h[1], h[2], h[3]}; mid = u32x4{m[0], m[1], m[2], m[3]}; lo = u32x4{l[0], l[1], l[2], l[3]};
+}
+
 template <int FMT = kSplitBf16x3>
 __device__ __forceinline__ void frag_planes(f32x4 x, f32x4 y, u32x4& hi, u32x4& mid, u32x4& lo) {
     // The fragment is the same for every stage of its segment, so the compiler would split it ONCE and keep all planes live across
     // the stages (96 registers at D = 256: ~450 B of scratch).  The empty asm makes the inputs opaque: the split is redone per stage,
     // 44 vector instructions per 24 MFMAs, and only one chunk's planes are live.
     asm volatile("" : "+v"(x.x), "+v"(x.y), "+v"(x.z), "+v"(x.w), "+v"(y.x), "+v"(y.y), "+v"(y.z), "+v"(y.w));
-    unsigned h[4], m[4], l[4];
-    split_pair<FMT>(x.x, x.y, h[0], m[0], l[0]); split_pair<FMT>(x.z, x.w, h[1], m[1], l[1]);
-    split_pair<FMT>(y.x, y.y, h[2], m[2], l[2]); split_pair<FMT>(y.z, y.w, h[3], m[3], l[3]);
-    hi = u32x4{h[0], h[1], h[2], h[3]}; mid = u32x4{m[0], m[1], m[2], m[3]}; lo = u32x4{l[0], l[1], l[2], l[3]};
+    chunk_planes<FMT>(x, y, hi, mid, lo);
+}
+
+// the whole fragment -> RESIDENT planes (panel_part_mma_planes' operand), split once for the stages that multiply it in a row
+// (N = D / 32; deduced, because a kernel form without planes declares one-element dummies and still names this call)
+template <int D, int FMT = kSplitBf16x3, int N>
+__device__ __forceinline__ void frag_to_planes(const Frag<D>& a, u32x4 (&ph)[N], u32x4 (&pm)[N], u32x4 (&pl)[N]) {
+    static_assert(N == D / 32 || N == 1, "one quad per plane and 32-chunk");
+#pragma unroll
+    for (int c2 = 0; c2 < N; ++c2) chunk_planes<FMT>(a.v[2 * c2], a.v[2 * c2 + 1], ph[c2], pm[c2], pl[c2]);
 }
 
 // acc[0..3] (+)= chunks [part*CP, (part+1)*CP) of the fragment x the same chunks of a split panel image; `chunks` points at the
@@ -326,6 +347,178 @@ __device__ __forceinline__ void panel_part_mma_planes(f32x4 (&acc)[4], const u32
         if (more) wh = slot(u + 1, 0);
         acc[j] = c;
     }
+}
+
+// ---- the two-slot ring ---------------------------------------------------------------------------------------------------------------
+// Slot `cur` holds the part the round multiplies; the other slot receives the next part during the round; the round's barrier
+// publishes it and flips.  ASM: slots are filled by dma_image_asm (split images), else by dma_block (the f32 images of the GRU
+// backward, which hipcc waits for itself).
+//
+// The counted wait.  A round's DMA pieces are the FIRST vector-memory instructions a wave issues in it, and the vector-memory counter
+// retires in order.  If the wave issued `keep` more behind them (the next tile's rows, a panel's stores) and nothing after those,
+// "at most keep outstanding" can only leave those `keep`: the pieces have landed, and the rest stays in flight across the barrier (it
+// has until the next round's barrier).  Each kernel says at its call why its `keep` instructions are the last ones it issued.
+template <int SLOT_BYTES, int NW, bool ASM = true>
+struct PanelRing {
+    static constexpr int SLOTF = SLOT_BYTES / 4;
+    float* const lds;                                  // [2][SLOTF]
+    const int wave, lane;
+    int cur = 0;
+    __device__ __forceinline__ void dma(const float* src, float* dst) const {
+        if constexpr (ASM) dma_image_asm<SLOT_BYTES, NW>(src, dst, wave, lane);
+        else dma_block<SLOT_BYTES, NW>(src, dst, wave, lane);
+    }
+    __device__ __forceinline__ void fill_first(const float* src) const { dma(src, lds); }
+    __device__ __forceinline__ void fill_next(const float* src) const { dma(src, lds + (cur ^ 1) * SLOTF); }
+    __device__ __forceinline__ const float* slot() const { return lds + cur * SLOTF; }
+    // everything this wave has issued has landed, for every wave (no flip: the wait for the first fill)
+    __device__ __forceinline__ void first_ready() const { if constexpr (ASM) dma_wait(); __syncthreads(); }
+    __device__ __forceinline__ void publish() { first_ready(); cur ^= 1; }
+    __device__ __forceinline__ void publish_keep(int keep) {         // (wave-uniform; s_waitcnt takes an immediate)
+        switch (keep) {
+#define GGNN_WC(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); break;
+            GGNN_WC(0) GGNN_WC(1) GGNN_WC(2) GGNN_WC(3) GGNN_WC(4) GGNN_WC(5) GGNN_WC(6) GGNN_WC(7) GGNN_WC(8) GGNN_WC(9) GGNN_WC(10)
+            GGNN_WC(11) GGNN_WC(12) GGNN_WC(13) GGNN_WC(14) GGNN_WC(15) GGNN_WC(16) GGNN_WC(17) GGNN_WC(18) GGNN_WC(19) GGNN_WC(20)
+            GGNN_WC(21) GGNN_WC(22) GGNN_WC(23) GGNN_WC(24) GGNN_WC(25) GGNN_WC(26)
+#undef GGNN_WC
+            default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
+        }
+        __builtin_amdgcn_s_barrier();
+        cur ^= 1;
+    }
+    template <int KEEP>
+    __device__ __forceinline__ void publish_keep() { static_assert(KEEP >= 0 && KEEP <= 26, "no such wait"); publish_keep(KEEP); }
+};
+
+// what the ring's other slot receives while part `part` of image `img` is multiplied: the next part of this image, else the first
+// part of image `nimg`
+template <int PARTS, int IMGF, int SLOTF>
+__device__ __forceinline__ const float* panel_next_part(const float* packed, int img, int part, int nimg) {
+    return part + 1 < PARTS ? packed + (size_t)img * IMGF + (size_t)(part + 1) * SLOTF : packed + (size_t)nimg * IMGF;
+}
+
+// fn(part) for every part of an image, unrolled
+template <int PARTS, class F>
+__device__ __forceinline__ void panel_for_parts(F&& fn) {
+    static_assert(PARTS >= 1 && PARTS <= 3, "an image comes in 1 .. 3 parts");
+    fn(std::integral_constant<int, 0>{});
+    if constexpr (PARTS > 1) fn(std::integral_constant<int, 1>{});
+    if constexpr (PARTS > 2) fn(std::integral_constant<int, 2>{});
+}
+
+// One round of a stage.  Every wave issues its pieces of the next part FIRST (`more`: there is one): a part issued behind a burst
+// lands late in the round or not before its barrier.  Then, for a wave with a tile (ACT; a wave without one only feeds the ring and
+// meets the barriers): before() -- loads that the burst hides --, the MFMA burst mma() on the current slot, and in an image's last
+// part after() -- the stage's epilogue, or this wave's loads for the next stage, which fly while the partner wave of the SIMD
+// multiplies.  KEEP: before() and after() return how many vector-memory instructions they issued, and the barrier is PanelRing's
+// counted wait; else the barrier is the full wait of the GRU backward.
+// (The forward GRU spells the ring and this round out in its own text, with GGNN_PANEL_DMA_FIRST's early / late-wave choice: see there.)
+template <int part, int PARTS, bool ACT, bool KEEP, class Ring, class Before, class Mma, class After>
+__device__ __forceinline__ void panel_round(Ring& ring, bool more, const float* nsrc, Before&& before, Mma&& mma, After&& after) {
+    int keep = 0;
+    if (more) ring.fill_next(nsrc);
+    if constexpr (ACT && KEEP) keep += before();
+    else if constexpr (ACT) before();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (ACT) mma();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (ACT && part == PARTS - 1) {
+        if constexpr (KEEP) keep += after();
+        else after();
+    }
+    if constexpr (KEEP) ring.publish_keep(keep);
+    else ring.publish();
+}
+
+// ---- who works which 16-row tile ------------------------------------------------------------------------------------------------------
+// Pass walk (GCN layer, R-GCN cell, ring transform): a workgroup's pass takes NW consecutive tiles, one per wave; its passes are
+// `stride` tiles apart.  run_pass(ACT, tile, first_pass, last_pass); ACT = false_type: this wave has no tile in the pass.
+template <int NW>
+struct PanelPassWalk {
+    int n_tiles, base, stride, n_pass;
+    __device__ __forceinline__ PanelPassWalk(int n_tiles_, int first_wg, int n_wg)
+        : n_tiles(n_tiles_), base(first_wg * NW), stride(n_wg * NW),
+          n_pass(base < n_tiles ? (n_tiles - base + stride - 1) / stride : 0) {}      // (wave 0 has a tile in each)
+    template <class F>
+    __device__ __forceinline__ void run(int wave, F&& run_pass) const {
+#pragma unroll 1
+        for (int pass = 0; pass < n_pass; ++pass) {
+            const int idx = base + pass * stride + wave;
+            if (idx < n_tiles) run_pass(std::true_type{}, idx, pass == 0, pass + 1 == n_pass);
+            else run_pass(std::false_type{}, idx, pass == 0, pass + 1 == n_pass);
+        }
+    }
+};
+
+// Ticket walk (the two GRU kernels): workgroup b works tickets b, b + nb, ..; full rounds of NW tiles per workgroup first, then the
+// rest spread thin over all workgroups (tail_w tiles each).
+template <int NW>
+struct PanelTickets {
+    int wt_total, full_tk, tail_w, n_tk;
+    __device__ __forceinline__ PanelTickets(int V, int nb) {
+        wt_total = (V + 15) / 16;
+        full_tk = wt_total / (NW * nb) * nb;
+        const int rest = wt_total - full_tk * NW;
+        tail_w = (rest + nb - 1) / nb;
+        n_tk = full_tk + (tail_w ? (rest + tail_w - 1) / tail_w : 0);
+    }
+    // the tile of `wave` in ticket t, -1: none.  same_tile: a tail ticket names ONE tile for every wave (the cooperative tail)
+    __device__ __forceinline__ int tile_of(int t, int wave, bool same_tile = false) const {
+        if (t < full_tk) return t * NW + wave;
+        if (t >= n_tk) return -1;
+        if (same_tile) return full_tk * NW + (t - full_tk);
+        const int tl = full_tk * NW + (t - full_tk) * tail_w + wave;
+        return (wave < tail_w && tl < wt_total) ? tl : -1;
+    }
+};
+
+// ---- the gather of a pass-walk kernel ---------------------------------------------------------------------------------------------------
+// gathered rows in flight per lane while it aggregates: the aggregate is D / 4 registers and so is every row (D = 256: 64 + 2 x 64;
+// 192: 48 + 3 x 48; 128: 32 + 4 x 32).  One more at D = 192 / 256 spills (8 / 28 B of scratch per lane).
+template <int D>
+constexpr int panel_rows_in_flight() { return D <= 128 ? 4 : (D <= 192 ? 3 : 2); }
+
+// slots [beg, end) in order: gather(N, k) adds the rows of slots k .. k+N-1, N = rows in flight, then 2, then 1
+template <int D, class G>
+__device__ __forceinline__ void panel_gather_ladder(int beg, int end, G&& gather) {
+    constexpr int RF = panel_rows_in_flight<D>();
+    int k = beg;
+    for (; k + RF <= end; k += RF) gather(std::integral_constant<int, RF>{}, k);
+    if constexpr (RF > 2) {
+        if (k + 2 <= end) { gather(std::integral_constant<int, 2>{}, k); k += 2; }
+    }
+    if (k < end) gather(std::integral_constant<int, 1>{}, k);
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------
+constexpr int kPanelNW = 8;                            // waves per workgroup: one workgroup per CU, 2 waves per SIMD
+constexpr bool panel_hidden_ok(int D) { return D == 128 || D == 192 || D == 256; }
+
+// fn(integral_constant<int, D>) for a D that panel_hidden_ok
+template <class F>
+auto panel_for_D(int D, F&& fn) {
+    switch (D) {
+        case 256: return fn(std::integral_constant<int, 256>{});
+        case 192: return fn(std::integral_constant<int, 192>{});
+        default: return fn(std::integral_constant<int, 128>{});
+    }
+}
+
+// workgroups of a launch over `rows` rows: one per CU (the ring is up to 128 KiB and a wave holds up to 256 registers), no more than
+// there are groups of `tiles_per_wg` 16-row tiles
+inline int panel_blocks(long long rows, int tiles_per_wg) {
+    const long long n_tiles = (rows + 15) / 16;
+    return (int)std::min<long long>((n_tiles + tiles_per_wg - 1) / tiles_per_wg, (long long)num_cus());
+}
+
+// launch of a kernel with `lds` bytes of dynamic LDS, opted in once per device where it exceeds `optin_above`
+template <auto Kernel, class... Args>
+int panel_launch(size_t lds, size_t optin_above, int blocks, hipStream_t st, Args... args) {
+    static std::atomic<unsigned long long> lds_ok{0};
+    if (lds > optin_above) GGNN_CHECK_HIP(allow_dynamic_lds(Kernel, lds, lds_ok));
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(kPanelNW * 64), lds, st, args...);
+    GGNN_CHECK_HIP(hipGetLastError());
+    return GGNN_OK;
 }
 
 }  // namespace ggnn

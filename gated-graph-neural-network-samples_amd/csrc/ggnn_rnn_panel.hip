@@ -5,7 +5,7 @@
 //     h'          = act([x_0 | .. | x_{nx-2} | incoming | h] W + b)          W [(nx+1) D, D], act = tanh / ReLU
 //
 // At D <= 100 all nx + 1 weight blocks stay in LDS for the whole launch (ggnn_rnn_fused.hip); at D = 128 two exact three-piece blocks
-// are already 192 KiB.  Here the structure is that of the panel GCN layer (ggnn_gcn_panel.hip): one workgroup of 8 waves per CU owns
+// are already 192 KiB.  Here, on the shared panel layer (ggnn_panel.hpp), one workgroup of 8 waves per CU owns
 // a PASS of 8 x 16 rows, each wave a 16-row tile, and the (nx + 1) D / 64 panel images [D, 64] of W stream through a two-slot LDS-DMA
 // ring in PanelGruSplitCfg::PARTS parts (D = 128: whole 48 KiB images; 192: thirds of 24 KiB; 256: halves of 48 KiB).
 //
@@ -24,7 +24,7 @@
 // Schedule of a workgroup: [DMA part 0 of the first image] | pass: gather (per wave, no barrier) -> (nx + 1) NP PARTS rounds of
 // {DMA of the next part into the other slot, (first round of a segment: its fragment load), MFMA burst on this slot, (last segment,
 // last part of a panel: epilogue + 4 stores), barrier}.  The last round of a pass brings in the first part of the NEXT pass, so a
-// pass's gather meets a ready ring.  The round barrier is ggnn_gcn_panel.hip's publish_keep.  The segment loop is a run-time loop
+// pass's gather meets a ready ring.  The round barrier is PanelRing's counted wait.  The segment loop is a run-time loop
 // (the rounds of ONE segment are unrolled, not all of them: D = 256 / nx = 3 would be 3072 MFMAs of straight-line code).
 //
 // Exact bf16x3 only: ReLU states have no bound, so the two-piece f16 format's operand range cannot be proven (ggnn_rnn_fused.hip).
@@ -38,19 +38,15 @@
 namespace ggnn {
 namespace {
 
-constexpr int kRnnPanelNW = 8;                                     // waves per workgroup: one workgroup per CU, 2 waves per SIMD
+constexpr int kRnnPanelNW = kPanelNW;
 
 template <int D>
 using RnnPanelImg = PanelGruSplitCfg<D, kSplitBf16x3>;
 
-constexpr bool rnn_panel_ok(int D, int nx) { return (D == 128 || D == 192 || D == 256) && nx >= 1 && nx <= 3; }
+constexpr bool rnn_panel_ok(int D, int nx) { return panel_hidden_ok(D) && nx >= 1 && nx <= 3; }
 
 template <int D>
 constexpr size_t rnn_panel_bytes(int nx) { return (size_t)(nx + 1) * PanelCfg<D>::NP * RnnPanelImg<D>::IMG_BYTES; }
-
-// gathered rows in flight per lane beside the partial sum (the panel GCN layer's budget: one more at D = 192 / 256 spills)
-template <int D>
-constexpr int rnn_panel_rows_in_flight() { return D <= 128 ? 4 : (D <= 192 ? 3 : 2); }
 
 struct RnnPanelArgs {
     const float* x[2];                                 // residual segments (nx - 1 of them)
@@ -100,32 +96,19 @@ __global__ __launch_bounds__(kRnnPanelNW * 64) void rnn_panel_kernel(RnnPanelArg
     using C = PanelCfg<D>;
     using SC = RnnPanelImg<D>;
     constexpr int NW = kRnnPanelNW, NP = C::NP, NC = C::NC, PARTS = SC::PARTS, SLOTF = SC::PART, IMGF = SC::IMG;
-    constexpr int RF = rnn_panel_rows_in_flight<D>();
-    extern __shared__ __attribute__((aligned(16))) float ring[];     // [2][PART]
+    extern __shared__ __attribute__((aligned(16))) float ring_lds[];     // [2][PART]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
     const int V = a.V;
-    const int n_tiles = (V + 15) / 16;
-    const int base = blockIdx.x * NW, stride = gridDim.x * NW;
-    const int n_pass = base < n_tiles ? (n_tiles - base + stride - 1) / stride : 0;      // (wave 0 has a tile in each)
+    const PanelPassWalk<NW> walk((V + 15) / 16, blockIdx.x, gridDim.x);
     const float* packed = a.packed;
-
-    int cur = 0;
-    auto dma = [&](const float* src, float* dst) { dma_image_asm<SC::PART_BYTES, NW>(src, dst, wave, lane); };
-    // the barrier of a round in which this wave issued `keep` vector-memory instructions BEHIND its DMA pieces (a panel's stores): the
-    // counter retires in order, so "at most keep outstanding" proves the pieces landed (gcn_panel_layer_kernel's publish_keep)
-    auto publish_keep = [&](auto keep_c) {
-        if constexpr (decltype(keep_c)::value == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
+    PanelRing<SC::PART_BYTES, NW> ring{ring_lds, wave, lane};
     // the image segment walked at position q of a pass: incoming (nx - 1) first, then x_0 .., then h (nx)
     auto seg_at = [](int q) { return q == 0 ? NX - 1 : (q == NX ? NX : q - 1); };
-    if (n_pass > 0) dma(packed + (size_t)seg_at(0) * NP * IMGF, ring);
+    if (walk.n_pass > 0) ring.fill_first(packed + (size_t)seg_at(0) * NP * IMGF);
 
-    // ACT: this wave has a tile (else it only feeds the ring and meets the barriers)
-    auto run_pass = [&](auto active_c, int idx, bool first_pass, bool last_pass) {
+    walk.run(wave, [&](auto active_c, int idx, bool first_pass, bool last_pass) {
         constexpr bool ACT = decltype(active_c)::value;
         const int r = idx * 16 + li;
         const bool live = r < V;
@@ -139,12 +122,9 @@ __global__ __launch_bounds__(kRnnPanelNW * 64) void rnn_panel_kernel(RnnPanelArg
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) f.v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-            int k = beg;
-            for (; k + RF <= end; k += RF) rnn_panel_gather<D, RF>(f, a.H, a.gidx, k, a.num_rows, kq);
-            if constexpr (RF > 2) {
-                if (k + 2 <= end) { rnn_panel_gather<D, 2>(f, a.H, a.gidx, k, a.num_rows, kq); k += 2; }
-            }
-            if (k < end) rnn_panel_gather<D, 1>(f, a.H, a.gidx, k, a.num_rows, kq);
+            panel_gather_ladder<D>(beg, end, [&](auto n_c, int k) {
+                rnn_panel_gather<D, decltype(n_c)::value>(f, a.H, a.gidx, k, a.num_rows, kq);
+            });
             if (a.use_avg) {                                // :206-209, the expression of the stand-alone segment sum
                 float deg = 0.f;
                 for (int t = 0; t < a.T; ++t) deg += a.nin[(size_t)rc * a.T + t];
@@ -158,7 +138,7 @@ __global__ __launch_bounds__(kRnnPanelNW * 64) void rnn_panel_kernel(RnnPanelArg
                 for (int c = 0; c < NC; ++c) st4_b(a.save, ob + 64u * c, f.v[c]);
             }
         }
-        if (first_pass) { dma_wait(); __syncthreads(); }    // the first part has landed (later passes: the previous pass's last round)
+        if (first_pass) ring.first_ready();                 // (later passes: the previous pass's last round)
         f32x4 acc[NP][4];
         if constexpr (ACT) {
 #pragma unroll
@@ -170,76 +150,52 @@ __global__ __launch_bounds__(kRnnPanelNW * 64) void rnn_panel_kernel(RnnPanelArg
         for (int q = 0; q <= NX; ++q) {
             const int seg = seg_at(q), nseg = seg_at(q == NX ? 0 : q + 1);
             const bool last_q = q == NX;
-            auto round = [&](auto p_c, auto part_c) {
-                constexpr int p = decltype(p_c)::value, part = decltype(part_c)::value;
-                const bool more = part + 1 < PARTS || p + 1 < NP || !last_q || !last_pass;
-                const float* nsrc = part + 1 < PARTS ? packed + (size_t)(seg * NP + p) * IMGF + (size_t)(part + 1) * SLOTF
-                                                     : (p + 1 < NP ? packed + (size_t)(seg * NP + p + 1) * IMGF
-                                                                   : packed + (size_t)nseg * NP * IMGF);
-                // every wave issues its pieces of the next part FIRST: a part issued behind a burst would not land before the barrier
-                if (more) dma(nsrc, ring + (cur ^ 1) * SLOTF);
-                if constexpr (ACT && p == 0 && part == 0) {
-                    // the fragment of a residual segment or of h, behind the round's DMA pieces: the burst below waits for it
-                    if (q > 0) load_frag<D>(f, last_q ? a.h : (q == 1 ? a.x[0] : a.x[1]), rc, kq);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT) panel_part_mma_split<D, false, false, part, kSplitBf16x3>(acc[p], f, ring + cur * SLOTF, li, kq);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ACT && part == PARTS - 1) {
-                    if (last_q) {
-                        // EpiBiasAct, term for term.  The bias quads are loaded by every lane of a wave with a tile and each store's value
-                        // depends on one, so hipcc's own waits have retired them -- and, the counter being in order, the DMA pieces issued
-                        // before them -- when the last store is issued: "at most 4 outstanding" can only leave the four stores.
-                        f32x4 c[4];
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            c[nt] = acc[p][nt] + ld4(a.b + p * 64 + nt * 16 + 4 * kq);
-                            if (a.act == GGNN_ACT_TANH) { c[nt].x = tanh_f(c[nt].x); c[nt].y = tanh_f(c[nt].y); c[nt].z = tanh_f(c[nt].z); c[nt].w = tanh_f(c[nt].w); }
-                            else { c[nt].x = fmaxf(c[nt].x, 0.f); c[nt].y = fmaxf(c[nt].y, 0.f); c[nt].z = fmaxf(c[nt].z, 0.f); c[nt].w = fmaxf(c[nt].w, 0.f); }
-                        }
-                        // (every tile has a valid first row: the four stores are issued by every wave with a tile)
-                        if (live) {
-#pragma unroll
-                            for (int nt = 0; nt < 4; ++nt)
-                                st4_b(a.h_out, ((unsigned)r * (unsigned)D + (unsigned)(p * 64 + nt * 16 + 4 * kq)) * 4u, c[nt]);
-                        }
-                        publish_keep(std::integral_constant<int, 4>{});
-                    } else {
-                        publish_keep(std::integral_constant<int, 0>{});
-                    }
-                } else {
-                    publish_keep(std::integral_constant<int, 0>{});
-                }
-                cur ^= 1;
-            };
             auto panel = [&](auto p_c) {
-                round(p_c, std::integral_constant<int, 0>{});
-                if constexpr (PARTS > 1) round(p_c, std::integral_constant<int, 1>{});
-                if constexpr (PARTS > 2) round(p_c, std::integral_constant<int, 2>{});
+                constexpr int p = decltype(p_c)::value;
+                panel_for_parts<PARTS>([&](auto part_c) {
+                    constexpr int part = decltype(part_c)::value;
+                    const bool more = part + 1 < PARTS || p + 1 < NP || !last_q || !last_pass;
+                    const float* nsrc = panel_next_part<PARTS, IMGF, SLOTF>(packed, seg * NP + p, part, p + 1 < NP ? seg * NP + p + 1 : nseg * NP);
+                    panel_round<part, PARTS, ACT, true>(ring, more, nsrc,
+                        [&] {
+                            // the fragment of a residual segment or of h, behind the round's DMA pieces: the burst below waits for it
+                            if constexpr (p == 0 && part == 0) { if (q > 0) load_frag<D>(f, last_q ? a.h : (q == 1 ? a.x[0] : a.x[1]), rc, kq); }
+                            return 0;
+                        },
+                        [&] { panel_part_mma_split<D, false, false, part, kSplitBf16x3>(acc[p], f, ring.slot(), li, kq); },
+                        [&] {
+                            if (!last_q) return 0;
+                            // EpiBiasAct, term for term.  The bias quads are loaded by every lane of a wave with a tile and each store's value
+                            // depends on one, so hipcc's own waits have retired them when the last store is issued: the four stores are the
+                            // last vector-memory instructions of the round.
+                            f32x4 c[4];
+#pragma unroll
+                            for (int nt = 0; nt < 4; ++nt) {
+                                c[nt] = acc[p][nt] + ld4(a.b + p * 64 + nt * 16 + 4 * kq);
+                                if (a.act == GGNN_ACT_TANH) { c[nt].x = tanh_f(c[nt].x); c[nt].y = tanh_f(c[nt].y); c[nt].z = tanh_f(c[nt].z); c[nt].w = tanh_f(c[nt].w); }
+                                else { c[nt].x = fmaxf(c[nt].x, 0.f); c[nt].y = fmaxf(c[nt].y, 0.f); c[nt].z = fmaxf(c[nt].z, 0.f); c[nt].w = fmaxf(c[nt].w, 0.f); }
+                            }
+                            // (every tile has a valid first row: the four stores are issued by every wave with a tile)
+                            if (live) {
+#pragma unroll
+                                for (int nt = 0; nt < 4; ++nt)
+                                    st4_b(a.h_out, ((unsigned)r * (unsigned)D + (unsigned)(p * 64 + nt * 16 + 4 * kq)) * 4u, c[nt]);
+                            }
+                            return 4;
+                        });
+                });
             };
             panel(std::integral_constant<int, 0>{});
             panel(std::integral_constant<int, 1>{});
             if constexpr (NP > 2) panel(std::integral_constant<int, 2>{});
             if constexpr (NP > 3) panel(std::integral_constant<int, 3>{});
         }
-    };
-    for (int pass = 0; pass < n_pass; ++pass) {
-        const int idx = base + pass * stride + wave;
-        if (idx < n_tiles) run_pass(std::true_type{}, idx, pass == 0, pass + 1 == n_pass);
-        else run_pass(std::false_type{}, idx, pass == 0, pass + 1 == n_pass);
-    }
+    });
 }
 
 template <int D, int NX>
 int rnn_panel_launch(const RnnPanelArgs& a, hipStream_t st) {
-    constexpr size_t lds = (size_t)2 * RnnPanelImg<D>::PART_BYTES;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (lds > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&rnn_panel_kernel<D, NX>, lds, lds_ok));
-    const long long n_tiles = (a.V + 15) / 16;
-    const long long blocks = std::min<long long>((n_tiles + kRnnPanelNW - 1) / kRnnPanelNW, (long long)num_cus());
-    hipLaunchKernelGGL((rnn_panel_kernel<D, NX>), dim3((unsigned)blocks), dim3(kRnnPanelNW * 64), lds, st, a);
-    GGNN_CHECK_HIP(hipGetLastError());
-    return GGNN_OK;
+    return panel_launch<&rnn_panel_kernel<D, NX>>((size_t)2 * RnnPanelImg<D>::PART_BYTES, 48 * 1024, panel_blocks(a.V, kRnnPanelNW), st, a);
 }
 
 template <int D>
@@ -271,7 +227,7 @@ extern "C" int ggnn_rnn_panel_supported(int D, int nx) { return rnn_panel_ok(D, 
 
 extern "C" size_t ggnn_rnn_panel_packed_bytes(int D, int nx) {
     if (!rnn_panel_ok(D, nx)) return 0;
-    return D == 256 ? rnn_panel_bytes<256>(nx) : (D == 192 ? rnn_panel_bytes<192>(nx) : rnn_panel_bytes<128>(nx));
+    return panel_for_D(D, [&](auto d) { return rnn_panel_bytes<decltype(d)::value>(nx); });
 }
 
 extern "C" void ggnn_rnn_panel_launch_geometry(int D, int nx, int* rows_per_workgroup, int* max_workgroups) {
@@ -283,12 +239,7 @@ extern "C" void ggnn_rnn_panel_launch_geometry(int D, int nx, int* rows_per_work
 extern "C" int ggnn_rnn_panel_pack_weights_f32(const float* W, int nx, int D, float* packed, ggnn_stream_t stream) {
     if (!rnn_panel_ok(D, nx)) return rnn_panel_unsupported(D, nx);
     GGNN_CHECK_ARG(W && packed && aligned16(packed) && (const void*)W != (const void*)packed, "null, misaligned or aliasing pointer");
-    hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 256: return rnn_panel_pack<256>(W, nx, packed, st);
-        case 192: return rnn_panel_pack<192>(W, nx, packed, st);
-        default: return rnn_panel_pack<128>(W, nx, packed, st);
-    }
+    return panel_for_D(D, [&](auto d) { return rnn_panel_pack<decltype(d)::value>(W, nx, packed, (hipStream_t)stream); });
 }
 
 extern "C" int ggnn_rnn_panel_gather_f32(const float* const* x_segs, int nx, const float* h, const float* packed, const float* b,
@@ -323,10 +274,5 @@ extern "C" int ggnn_rnn_panel_gather_f32(const float* const* x_segs, int nx, con
     a.num_rows = (int)num_rows;
     a.M = (num_rows > 0 && Hrows && gather_row) ? (int)M : 0;      // no rows to gather from: every node's slot range is empty
     a.T = T; a.use_avg = use_avg ? 1 : 0; a.V = V; a.act = act;
-    hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 256: return rnn_panel_dispatch_nx<256>(a, nx, st);
-        case 192: return rnn_panel_dispatch_nx<192>(a, nx, st);
-        default: return rnn_panel_dispatch_nx<128>(a, nx, st);
-    }
+    return panel_for_D(D, [&](auto d) { return rnn_panel_dispatch_nx<decltype(d)::value>(a, nx, (hipStream_t)stream); });
 }

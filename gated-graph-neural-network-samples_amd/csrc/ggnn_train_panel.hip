@@ -96,7 +96,7 @@ void launch_panel_prepare(const PanelPrepArgs& a, dim3 grid, hipStream_t st) {
 
 using namespace ggnn;
 
-extern "C" int ggnn_sparse_train_panel_supported(int D) { return D == 128 || D == 192 || D == 256; }
+extern "C" int ggnn_sparse_train_panel_supported(int D) { return panel_hidden_ok(D); }
 
 extern "C" int ggnn_sparse_train_panel_prepare_f32(int num_layers, int T, int D, const int32_t* nx, const float* const* edge_w,
                                                    float keep_prob, const uint64_t* seeds, const float* const* Wg, const float* const* Wc,
@@ -126,11 +126,7 @@ extern "C" int ggnn_sparse_train_panel_prepare_f32(int num_layers, int T, int D,
     }
     const dim3 grid(8, max_images, num_layers);
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 128: launch_panel_prepare<128>(a, grid, st); break;
-        case 192: launch_panel_prepare<192>(a, grid, st); break;
-        default: launch_panel_prepare<256>(a, grid, st); break;
-    }
+    panel_for_D(D, [&](auto d) { launch_panel_prepare<decltype(d)::value>(a, grid, st); });
     GGNN_CHECK_HIP(hipGetLastError());
     return GGNN_OK;
 }

@@ -6,6 +6,9 @@ whole kernel and inside the pass loop (the widest backward branch that encloses 
     python tools/gru_codegen.py --out mix.json                       # every fused-GRU / compact-transform kernel of this tree
     python tools/gru_codegen.py --asm a.s b.s --out mix.json         # ... of listings made elsewhere (e.g. from the parent commit)
     python tools/gru_codegen.py --pair parent.json this.json --out profiles/gru_issue_diet_codegen.json
+    # any other kernel family: its translation units and a regex on the demangled kernel names; with them --pair compares every kernel
+    python tools/gru_codegen.py --sources ggnn_panel.hip,ggnn_rnn_panel.hip --kernels 'panel_kernel<|ring_kernel<' --out this.json
+    python tools/gru_codegen.py --kernels . --pair parent.json this.json --out profiles/panel_shared_layer_codegen.json
 """
 import argparse, json, os, re, subprocess, sys, tempfile
 
@@ -18,6 +21,7 @@ COUNTS = {
     "ds_read_b128": r"ds_read_b128", "cond_branch": r"s_cbranch_(scc|vcc|exec)", "s_waitcnt": r"s_waitcnt",
     "scalar_mask": r"s_(and|or|andn2|orn2|xor|cselect)_b64|s_(and|or|andn2)_saveexec_b64",
     "v_readlane": r"v_readlane_b32", "v_writelane": r"v_writelane_b32", "v_mov": r"v_mov_|v_accvgpr_mov|v_pk_mov",
+    "global_load_lds": r"global_load_lds_", "ds_read": r"ds_read_",
 }
 COUNTS = {k: re.compile(r"(%s)" % v) for k, v in COUNTS.items()}
 # hot instantiations: label -> (parent's kernel, this tree's kernel), template argument lists as c++filt prints them
@@ -74,7 +78,7 @@ def pass_loop(body):
     return best
 
 
-def parse(path):
+def parse(path, kernels=KERNELS):
     txt = open(path, encoding="utf-8", errors="replace").read().split("\n")
     out = {}
     i = 0
@@ -104,9 +108,9 @@ def parse(path):
     dem = subprocess.run(["c++filt"] + names, check=True, capture_output=True, text=True).stdout.strip().split("\n")
     res = {}
     for n, d in zip(names, dem):
-        if not KERNELS.search(d):
+        if not kernels.search(d):
             continue
-        d = re.sub(r"^void ggnn::", "", d)
+        d = re.sub(r"^void ggnn::(\(anonymous namespace\)::)?", "", d)
         d = re.sub(r"\(.*$", "", d).replace("(ggnn::SplitFormat)", "").replace("(bool)", "")
         meta, body = out[n]
         e = dict(meta)
@@ -117,15 +121,49 @@ def parse(path):
     return res
 
 
+def pair_all(par, cur):
+    """Every kernel of two listings' records side by side (the form of profiles/xty_shared_layer_codegen.json)."""
+    keys = ("vgprs", "sgprs", "scratch_bytes", "occupancy")
+    row = lambda e: dict({k: e.get(k) for k in keys}, **{k: e["kernel"][k] for k in ("instructions", "v_mfma", "global_load_lds", "ds_read")})
+    doc = {"note": "static code generation of every kernel of the listed translation units, parent commit vs this change (tools/gru_codegen.py: "
+                   "hipcc --offload-arch=gfx950, build.py's per-source flags, --cuda-device-only -S). instructions: lines of the kernel's "
+                   "assembly that are instructions; v_mfma / global_load_lds / ds_read: those that start with the word; scratch_bytes: per lane.",
+           "kernels": {k: {"parent": row(par[k]), "branch": row(cur[k])} for k in sorted(cur) if k in par},
+           "only_parent": sorted(set(par) - set(cur)), "only_branch": sorted(set(cur) - set(par))}
+    rows = doc["kernels"].values()
+    doc["summary"] = {
+        "kernels": len(doc["kernels"]),
+        "identical_rows": sum(r["parent"] == r["branch"] for r in rows),
+        "scratch_nonzero": sorted(k for k, r in doc["kernels"].items() if r["branch"]["scratch_bytes"] or r["parent"]["scratch_bytes"]),
+        "mfma_or_lds_dma_count_differs": sorted(k for k, r in doc["kernels"].items()
+                                                if any(r["parent"][f] != r["branch"][f] for f in ("v_mfma", "global_load_lds"))),
+        "occupancy_below_2_where_parent_has_2": sorted(k for k, r in doc["kernels"].items()
+                                                       if r["parent"]["occupancy"] >= 2 and r["branch"]["occupancy"] < 2),
+        "vgprs_differ": {k: [r["parent"]["vgprs"], r["branch"]["vgprs"]] for k, r in doc["kernels"].items() if r["parent"]["vgprs"] != r["branch"]["vgprs"]},
+        "instructions_grew": {k: [r["parent"]["instructions"], r["branch"]["instructions"]] for k, r in doc["kernels"].items()
+                              if r["branch"]["instructions"] > r["parent"]["instructions"]},
+    }
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", nargs="*")
     ap.add_argument("--pair", nargs=2)
     ap.add_argument("--out", required=True)
     ap.add_argument("--flags", default="")
+    ap.add_argument("--sources", help="comma-separated csrc/*.hip translation units instead of the fused GRU and compact transform")
+    ap.add_argument("--kernels", help="regex on the demangled kernel names to keep; with --pair: compare every kernel of the two records")
     a = ap.parse_args()
+    kernels = re.compile(a.kernels) if a.kernels else KERNELS
     if a.pair:
         par, cur = (json.load(open(p)) for p in a.pair)
+        if a.kernels:
+            par, cur = ({k: v for k, v in d.items() if kernels.search(k)} for d in (par, cur))
+            doc = pair_all(par, cur)
+            json.dump(doc, open(a.out, "w"), indent=1, sort_keys=True)
+            print(json.dumps({k: (v if not isinstance(v, dict) else len(v)) for k, v in doc["summary"].items()}, indent=1))
+            return
         doc = {"note": "static code generation of the hot forward kernels, parent commit vs this change (tools/gru_codegen.py: hipcc "
                        "--offload-arch=gfx950, build.py's per-source flags, --cuda-device-only -S; pass_loop = the widest loop that "
                        "encloses matrix instructions)", "kernels": {}}
@@ -147,13 +185,13 @@ def main():
     res = {}
     if a.asm:
         for p in a.asm:
-            res.update(parse(p))
+            res.update(parse(p, kernels))
     else:
         with tempfile.TemporaryDirectory() as td:
-            for src in SOURCES:
+            for src in (a.sources.split(",") if a.sources else SOURCES):
                 out = os.path.join(td, src[:-4] + ".s")
                 compile_asm(src, out, a.flags.split())
-                res.update(parse(out))
+                res.update(parse(out, kernels))
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)
     for k in sorted(res):
         e = res[k]
