@@ -120,6 +120,35 @@ __device__ __forceinline__ f32x4 tanh4_acc(f32x4 z, f32x4 b_scaled) {
     return 1.0f - 2.0f * rcp_4(exp2_4(z * k + b_scaled) + 1.0f);
 }
 
+// Whole 16-lane rows moved between the kq groups (row = lane >> 4) by the gfx950 row swaps v_permlane16_swap / v_permlane32_swap:
+// one vector-ALU instruction per register, where a __shfl is an LDS operation (ds_bpermute_b32) with an address computation and an
+// lgkmcnt wait -- inside epilogues in which the SIMD pair issues no MFMAs.  permlane16_swap(a, b) exchanges the odd rows of a with
+// the even rows of b, permlane32_swap(a, b) rows 2, 3 of a with rows 0, 1 of b; [0] / [1] of the result are the new a / b.
+// Call them with all lanes active (wave-uniform control flow only).
+__device__ __forceinline__ float row_up16(float x) {              // rows [x1, x1, x3, x3]: lane l of an even row reads lane l + 16
+    const unsigned u = __float_as_uint(x);
+    return __uint_as_float(__builtin_amdgcn_permlane16_swap(u, u, false, false)[1]);
+}
+__device__ __forceinline__ float row_up32(float x) {              // rows [x2, x3, x2, x3]: lane l < 32 reads lane l + 32
+    const unsigned u = __float_as_uint(x);
+    return __uint_as_float(__builtin_amdgcn_permlane32_swap(u, u, false, false)[1]);
+}
+template <int SH>
+__device__ __forceinline__ f32x4 rows_up(f32x4 v) {               // every element SH = 16 / 32 lanes up
+    static_assert(SH == 16 || SH == 32, "whole rows, one or two up");
+    if constexpr (SH == 16) return f32x4{row_up16(v.x), row_up16(v.y), row_up16(v.z), row_up16(v.w)};
+    else return f32x4{row_up32(v.x), row_up32(v.y), row_up32(v.z), row_up32(v.w)};
+}
+__device__ __forceinline__ float row0_elems_to_rows(f32x4 v) {    // row k of the result = element k of v's row 0 (same lane of the row)
+    const unsigned a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v.x), __float_as_uint(v.y), false, false)[0];   // [x0, y0, ., .]
+    const unsigned b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v.z), __float_as_uint(v.w), false, false)[0];   // [z0, w0, ., .]
+    return __uint_as_float(__builtin_amdgcn_permlane32_swap(a, b, false, false)[0]);                                    // [x0, y0, z0, w0]
+}
+__device__ __forceinline__ f32x4 rows_to_row0_elems(float x) {    // element k of the result's row 0 = row k of x (rows 1..3: not meaningful)
+    const float x1 = row_up16(x);
+    return f32x4{x, x1, row_up32(x), row_up32(x1)};
+}
+
 template <int D>
 __device__ __forceinline__ void frag_zero(Frag<D>& f) {
 #pragma unroll
@@ -298,6 +327,12 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
     constexpr int KI = 4;                             // slots covered by the pipeline
     constexpr int G_U = NX == 1 ? NSTAGE : 3 * (NX - 1);
     constexpr bool G_NEXT = (NX == 1);                // all phases run one pass ahead of the consumer
+    // The mean as one reciprocal per row and three vector-ALU instructions per value (g_finish) costs one more register that lives
+    // from the in-degrees to the consuming stage.  Every single-input kernel has it, and with residual inputs the half-image forms
+    // (the default policy's) at hidden sizes 64 and 100: no scratch, the parent's occupancy.  Form 0 with residual inputs is in scratch
+    // already and went 4-52 B deeper with it, and at hidden size 32 the 97th register cost a wave of occupancy
+    // (profiles/gru_tail_epilogue_codegen.json): those keep the plain division.  Same bits either way.
+    constexpr bool G_RCP = NX == 1 || (FORM != 0 && D != 32);
     int g_beg = 0, g_end = 0;
     int g_i[KI] = {0, 0, 0, 0};                       // (row 0 is always a valid row to fetch)
     f32x4 g_n = {0.f, 0.f, 0.f, 0.f};
@@ -331,7 +366,7 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
         if (part != 2) {
             touch(g_beg); touch(g_end);
             g_den = (((g_n.x + g_n.y) + g_n.z) + g_n.w) + 1e-7f;
-            if constexpr (NX == 1) g_rcp = 1.0f / g_den;    // the in-degrees landed with the slot range
+            if constexpr (G_RCP) g_rcp = 1.0f / g_den;      // the in-degrees landed with the slot range
         }
         if (part != 1) {
 #pragma unroll
@@ -364,10 +399,10 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             // residual step q + (x - den q) r.  With a correctly rounded r this IS the correctly rounded quotient
             // (Markstein) -- bit-identical to the `/` of the stand-alone kernel, asserted by the tests -- for 3 vector-ALU
             // instructions per value instead of ~11 (vector-ALU work is paid in matrix-pipe time).
-            // (NX >= 2 keeps the plain division: one more long-lived register pushes those variants deeper into scratch)
+            // (G_RCP: where the reciprocal's long-lived register is free; elsewhere the plain division)
             const float den = g_den, r = g_rcp;
             auto dv = [&](float x) {
-                if constexpr (NX == 1) { const float q = x * r; return fmaf(fmaf(-den, q, x), r, q); }
+                if constexpr (G_RCP) { const float q = x * r; return fmaf(fmaf(-den, q, x), r, q); }
                 else return x / den;
             };
 #pragma unroll
@@ -688,13 +723,15 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
             stage_tail_reduce<D>(acc_r);                       // VALU-tail columns: add the four kq partials
             stage_tail_reduce<D>(acc_u);
             if constexpr (C::TAILPACK) {
-                // the u gate's last tile was accumulated in the padding columns of the r gate's last tile:
-                // column D + j of that tile (lane kq + (D%16)/4) is u column 16*NC + j (lane kq)
-                constexpr int SH = 16 * ((D % 16) / 4);
-                f32x4 ut;
-                ut.x = __shfl(acc_r[NT - 1].x, lane + SH); ut.y = __shfl(acc_r[NT - 1].y, lane + SH);
-                ut.z = __shfl(acc_r[NT - 1].z, lane + SH); ut.w = __shfl(acc_r[NT - 1].w, lane + SH);
-                acc_u[NT - 1] = ut;
+                // The u gate's last tile was accumulated in the padding columns of the r gate's last tile: column D + j of that tile
+                // (lane group kq + KQ) is u column 16*NC + j (lane group kq).  Both gates are sigmoids, so the packed tile gets ONE
+                // epilogue -- the r lanes read the r bias, the u lanes the u bias (bias_s: [r | u] back to back) -- and the activated
+                // u values then move down to their own lane groups.  The groups from 2 KQ up are left as they are: with TAILPACK3
+                // they carry the x segments' share of the candidate's last tile.
+                constexpr int KQ = (D % 16) / 4;
+                const f32x4 b = ld4(bias_s + 16 * NC + 4 * kq + (kq < KQ ? 0 : D - 4 * KQ));
+                if (kq < 2 * KQ) acc_r[NT - 1] = sigmoid4_acc<FMT>(acc_r[NT - 1], b);
+                acc_u[NT - 1] = rows_up<16 * KQ>(acc_r[NT - 1]);
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -702,8 +739,11 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                 if (col < D) {
                     // bias_s holds -log2(e)*bg: sigmoid(z + b) = 1 / (1 + 2^(-log2e z - log2e b)), the bias add folded
                     // into the scaling FMA; written on whole float4s so that the non-transcendental half packs (v_pk_*)
-                    const f32x4 r = sigmoid4_acc<FMT>(acc_r[nt], ld4(bias_s + col));
-                    const f32x4 u = sigmoid4_acc<FMT>(acc_u[nt], ld4(bias_s + D + col));
+                    f32x4 r = acc_r[nt], u = acc_u[nt];
+                    if (!(C::TAILPACK && nt == NT - 1)) {               // (the packed tile is activated already)
+                        r = sigmoid4_acc<FMT>(acc_r[nt], ld4(bias_s + col));
+                        u = sigmoid4_acc<FMT>(acc_u[nt], ld4(bias_s + D + col));
+                    }
                     acc_r[nt] = r; acc_u[nt] = u;
                     // u is next used by the blend, a whole stage later: without a use HERE (the training instantiation has its store)
                     // the compiler sinks the sigmoid down to the blend and the inference kernel runs out of registers
@@ -721,9 +761,14 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
                 // remainder column 16NC + 4q + kq lives in tile NC of lane (li, kq' = q), element e = kq
-                const float t0 = __shfl(acc_r[NT - 1].x, li + 16 * q), t1 = __shfl(acc_r[NT - 1].y, li + 16 * q);
-                const float t2 = __shfl(acc_r[NT - 1].z, li + 16 * q), t3 = __shfl(acc_r[NT - 1].w, li + 16 * q);
-                const float rr = kq == 0 ? t0 : (kq == 1 ? t1 : (kq == 2 ? t2 : t3));
+                float rr;
+                if constexpr (NR == 1) {
+                    rr = row0_elems_to_rows(acc_r[NT - 1]);
+                } else {
+                    const float t0 = __shfl(acc_r[NT - 1].x, li + 16 * q), t1 = __shfl(acc_r[NT - 1].y, li + 16 * q);
+                    const float t2 = __shfl(acc_r[NT - 1].z, li + 16 * q), t3 = __shfl(acc_r[NT - 1].w, li + 16 * q);
+                    rr = kq == 0 ? t0 : (kq == 1 ? t1 : (kq == 2 ? t2 : t3));
+                }
                 rh.r[q] = rr * hf.r[q];
             }
         }
@@ -763,16 +808,17 @@ __global__ __launch_bounds__(NW * 64, FORM == 1 ? 2 : 1) void ggnn_gru_fused_ker
                 // the x segments' share of the candidate's last tile was accumulated two lane groups up in the r
                 // gate's last tile (which the gates epilogue rewrote only in its own lanes); add it to the r*h share
                 constexpr int SH2 = 32 * ((D % 16) / 4);
-                f32x4 ct;
-                ct.x = __shfl(acc_r[NT - 1].x, lane + SH2); ct.y = __shfl(acc_r[NT - 1].y, lane + SH2);
-                ct.z = __shfl(acc_r[NT - 1].z, lane + SH2); ct.w = __shfl(acc_r[NT - 1].w, lane + SH2);
-                acc_c[NT - 1] = ct + acc_c[NT - 1];
+                acc_c[NT - 1] = rows_up<SH2>(acc_r[NT - 1]) + acc_c[NT - 1];
             }
+            if constexpr (NR == 1) {
+                hrem = rows_to_row0_elems(hf.r[0]);   // (read by the kq == 0 lanes only: the last tile's other columns are >= D)
+            } else {
 #pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                const float h0 = __shfl(hf.r[q], li), h1 = __shfl(hf.r[q], li + 16);
-                const float h2 = __shfl(hf.r[q], li + 32), h3 = __shfl(hf.r[q], li + 48);
-                if (kq == q) hrem = f32x4{h0, h1, h2, h3};
+                for (int q = 0; q < NR; ++q) {
+                    const float h0 = __shfl(hf.r[q], li), h1 = __shfl(hf.r[q], li + 16);
+                    const float h2 = __shfl(hf.r[q], li + 32), h3 = __shfl(hf.r[q], li + 48);
+                    if (kq == q) hrem = f32x4{h0, h1, h2, h3};
+                }
             }
         }
         if (active && row < a.V && !GGNN_ABL(4)) {

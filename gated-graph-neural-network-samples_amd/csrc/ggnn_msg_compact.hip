@@ -24,6 +24,7 @@ namespace ggnn {
 constexpr int kMaxTypesC = 64;
 struct TypeRows {
     int row_off[kMaxTypesC + 1]; int tile_off[kMaxTypesC + 1]; int T; int num_nodes;
+    int* zero;         // not NULL: the launch stores 0 there (the ticket counter of the fused GRU launch that follows on the stream)
 #if GGNN_K1C_STAMPS
     unsigned long long* tdbg;
 #endif
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(NW * 64, 4) /* 4 waves per SIMD = 2 workgroups per 
 #endif
     K1C_T(0)
     K1C_T(6)                  // (shader-clock twin of the start stamp; a wave has at most 3 tiles in these runs)
+    if (tr.zero && blockIdx.x == 0 && tid == 0) *tr.zero = 0;
     int t = 0;
     while (t + 1 < tr.T && (int)blockIdx.x >= tr.tile_off[t + 1]) ++t;
     const int row_beg = tr.row_off[t], row_end = tr.row_off[t + 1];
@@ -221,6 +223,8 @@ static int launch_compact(const float* h, const float* W, const int* pair_node, 
     return launch_compact_m<D, false>(h, W, pair_node, tr, packed, Hc, st);
 }
 
+int msg_transform_compact_zero(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off, float* Hc,
+                               void* ws, size_t ws_bytes, int V, int D, int T, int fmt, int32_t* zero, ggnn_stream_t stream);
 int gru_panel_supported(int D);      // ggnn_panel.hip: hidden sizes handled on column panels
 int transform_panel_image_floats(int D);
 int transform_panel_dispatch(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V, int D,
@@ -300,7 +304,7 @@ extern "C" int ggnn_edge_weights_pack_f32(const float* W, int T, int D, int fmt,
         return fail(GGNN_E_UNSUPPORTED, "no packed edge weights for hidden size %d", D);
     GGNN_CHECK_ARG(W && packed && aligned16(packed), "null or misaligned pointer");
     TypeRows tr{};
-    tr.T = T;                                   // all row counts zero: pack only
+    tr.T = T;                                   // all row counts zero: pack only (no counter to zero)
     hipStream_t st = (hipStream_t)stream;
     if (gru_panel_supported(D)) return transform_panel_dispatch(nullptr, W, nullptr, tr.row_off, T, 0, D, packed, nullptr, fmt, st);
     switch (D) {
@@ -312,17 +316,20 @@ extern "C" int ggnn_edge_weights_pack_f32(const float* W, int T, int D, int fmt,
 
 // W == NULL: `ws` already holds the images written by ggnn_edge_weights_pack_f32 (inference: weights are
 // constant across batches, so the pack pre-pass is paid once per weight version instead of once per call).
-extern "C" int ggnn_msg_transform_compact_f32(const float* h, const float* W, const int32_t* pair_node,
-                                              const int64_t* type_row_off, float* Hc, void* ws, size_t ws_bytes, int V, int D,
-                                              int T, int fmt, ggnn_stream_t stream) {
+// zero (may be NULL): an int32 that is 0 once the call's work on the stream is done -- written by one thread of the transform launch
+// itself, where there is one (no rows, or a hidden size on column panels: a 4-byte fill instead).
+// (the library's own entry: ggnn_propagate.hip passes the ticket counter of the timestep's fused GRU launch)
+int ggnn::msg_transform_compact_zero(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off, float* Hc,
+                                     void* ws, size_t ws_bytes, int V, int D, int T, int fmt, int32_t* zero, ggnn_stream_t stream) {
     GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0 && T > 0 && T <= kMaxTypesC, "bad sizes V=%d D=%d T=%d", V, D, T);
     GGNN_CHECK_ARG(fmt == 0 || fmt == GGNN_GRU_FMT_F16X2 || fmt == GGNN_GRU_FMT_BF16X3, "fmt %d is not a GGNN_GRU_FMT_* value", fmt);
     GGNN_CHECK_ARG(type_row_off, "null pointer");
     if (!ggnn_msg_transform_compact_supported(D))
         return fail(GGNN_E_UNSUPPORTED, "compacted message transform supports hidden sizes 32, 64, 100, 128, 192, 256 (got %d)", D);
-    TypeRows tr;
+    TypeRows tr{};
     tr.T = T;
     tr.num_nodes = V;
+    tr.zero = zero;
     tr.tile_off[0] = 0;
     GGNN_CHECK_ARG(type_row_off[0] == 0, "type_row_off must start at 0");
     for (int t = 0; t < T; ++t) {
@@ -331,12 +338,13 @@ extern "C" int ggnn_msg_transform_compact_f32(const float* h, const float* W, co
         tr.tile_off[t + 1] = tr.tile_off[t] + (int)((type_row_off[t + 1] - type_row_off[t] + 127) / 128);
     }
     tr.row_off[T] = (int)type_row_off[T];
+    hipStream_t st = (hipStream_t)stream;
+    if (zero && (tr.row_off[T] == 0 || gru_panel_supported(D))) GGNN_CHECK_HIP(hipMemsetAsync(zero, 0, sizeof(int32_t), st));
     if (tr.row_off[T] == 0) return GGNN_OK;
     GGNN_CHECK_ARG(h && pair_node && Hc && ws, "null pointer");
     GGNN_CHECK_ARG(aligned16(h) && (!W || aligned16(W)) && aligned16(Hc) && aligned16(ws), "pointers must be 16-byte aligned");
     if (ws_bytes < ggnn_msg_transform_compact_workspace_bytes(D, T))
         return fail(GGNN_E_WORKSPACE, "compact transform workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     float* packed = static_cast<float*>(ws);
     if (gru_panel_supported(D)) return transform_panel_dispatch(h, W, pair_node, tr.row_off, T, V, D, packed, Hc, fmt, st);
     switch (D) {
@@ -344,4 +352,10 @@ extern "C" int ggnn_msg_transform_compact_f32(const float* h, const float* W, co
         case 64: return launch_compact<64>(h, W, pair_node, tr, packed, Hc, fmt, st);
         default: return launch_compact<32>(h, W, pair_node, tr, packed, Hc, fmt, st);
     }
+}
+
+extern "C" int ggnn_msg_transform_compact_f32(const float* h, const float* W, const int32_t* pair_node,
+                                              const int64_t* type_row_off, float* Hc, void* ws, size_t ws_bytes, int V, int D,
+                                              int T, int fmt, ggnn_stream_t stream) {
+    return msg_transform_compact_zero(h, W, pair_node, type_row_off, Hc, ws, ws_bytes, V, D, T, fmt, nullptr, stream);
 }

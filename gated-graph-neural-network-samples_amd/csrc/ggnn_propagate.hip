@@ -18,6 +18,12 @@
 #include "ggnn_common.h"
 #include <cstring>
 
+namespace ggnn {
+// ggnn_msg_compact.hip: ggnn_msg_transform_compact_f32 that also leaves 0 in *zero (may be NULL) -- stored by the transform launch itself
+int msg_transform_compact_zero(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off, float* Hc,
+                               void* ws, size_t ws_bytes, int V, int D, int T, int fmt, int32_t* zero, ggnn_stream_t stream);
+}
+
 static constexpr int kTileCounters = 1024;     // timesteps per call that get a dynamic tile counter (the rest split statically)
 
 extern "C" size_t ggnn_sparse_propagate_workspace_bytes(int V, int D, int T, int64_t compact_rows) {
@@ -79,7 +85,11 @@ static int propagate(
     void* gru_ws = p;
     const size_t gru_ws_bytes = ggnn_gru_workspace_bytes(V, D);
     int step_no = 0;
-    {
+    // The counters are zero before their GRU launches.  The compacted transform of a timestep precedes that timestep's GRU on the
+    // stream and zeroes its counter itself (ggnn::msg_transform_compact_zero: one thread's store, no fill launch in front of the
+    // forward); the routes with another transform kernel (dense, column panels) or none (no rows) fill them all here.
+    const bool zero_in_transform = compact && rows > 0 && ggnn_gru_is_fused(D) == 1;
+    if (!zero_in_transform) {
         int total_steps = 0;
         for (int l = 0; l < num_layers; ++l) total_steps += layer_timesteps[l] > 0 ? layer_timesteps[l] : 0;
         if (total_steps > kTileCounters) total_steps = kTileCounters;
@@ -122,21 +132,22 @@ static int propagate(
         if (rnn) GGNN_CHECK_ARG(rnn->b[l] && (gather_in_rnn || (rnn->w && rnn->w[l])), "layer %d needs raw RNN weights (no fused cell for it)", l);
         for (int s = 0; s < steps; ++s) {          // :153
             int rc;
+            static const bool dyn_tiles = [] { const char* e = getenv("GGNN_DYN_TILES"); return !e || atoi(e) != 0; }();
+            int32_t* counter = (dyn_tiles && step_no < kTileCounters) ? counters + step_no : nullptr;
+            ++step_no;
             if (compact) {
                 const bool packed = edge_packed && edge_packed[l];
-                rc = ggnn_msg_transform_compact_f32(cur, packed ? nullptr : edge_w[l], pair_node, type_row_off, H,
-                                                    packed ? const_cast<float*>(edge_packed[l]) : gru_ws,
-                                                    packed ? ggnn_msg_transform_compact_workspace_bytes(D, T) : gru_ws_bytes,
-                                                    V, D, T, (packed && edge_fmt) ? edge_fmt[l] : GGNN_GRU_FMT_BF16X3, stream);
+                rc = ggnn::msg_transform_compact_zero(cur, packed ? nullptr : edge_w[l], pair_node, type_row_off, H,
+                                                      packed ? const_cast<float*>(edge_packed[l]) : gru_ws,
+                                                      packed ? ggnn_msg_transform_compact_workspace_bytes(D, T) : gru_ws_bytes,
+                                                      V, D, T, (packed && edge_fmt) ? edge_fmt[l] : GGNN_GRU_FMT_BF16X3,
+                                                      zero_in_transform ? counter : nullptr, stream);
             } else {
                 GGNN_CHECK_ARG(edge_w && edge_w[l], "dense transform needs raw edge weights");
                 rc = ggnn_msg_transform_f32(cur, D, edge_w[l], H, V, D, T, stream);
             }
             if (rc) return rc;
             float* out = (s + 1 == steps) ? layer_out[l] : ping[s & 1];
-            static const bool dyn_tiles = [] { const char* e = getenv("GGNN_DYN_TILES"); return !e || atoi(e) != 0; }();
-            int32_t* counter = (dyn_tiles && step_no < kTileCounters) ? counters + step_no : nullptr;
-            ++step_no;
             if (gather_in_rnn && panel_rnn) {
                 rc = ggnn_rnn_panel_gather_f32(xs, nx, cur, rnn->packed[l], rnn->b[l], out, H, rows > 0 ? rows : 1, row_ptr, gather_row,
                                                rnn->M, nin, T, use_avg, nullptr, V, D, act, stream);

@@ -22,16 +22,18 @@ COUNTS = {
     "scalar_mask": r"s_(and|or|andn2|orn2|xor|cselect)_b64|s_(and|or|andn2)_saveexec_b64",
     "v_readlane": r"v_readlane_b32", "v_writelane": r"v_writelane_b32", "v_mov": r"v_mov_|v_accvgpr_mov|v_pk_mov",
     "global_load_lds": r"global_load_lds_", "ds_read": r"ds_read_",
+    "ds_bpermute_b32": r"ds_bpermute_b32", "v_permlane_swap": r"v_permlane(16|32)_swap", "v_exp_f32": r"v_exp_f32", "v_rcp_f32": r"v_rcp_f32",
+    "v_div": r"v_div_(scale|fmas|fixup)_f32",
 }
 COUNTS = {k: re.compile(r"(%s)" % v) for k, v in COUNTS.items()}
 # hot instantiations: label -> (parent's kernel, this tree's kernel), template argument lists as c++filt prints them
 HOT = {
-    "gru nx=1 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 1, 4, true, true, true, true, 1, 2>", "ggnn_gru_fused_kernel<100, 1, 4, false, true, true, false, 1, 2, 1, true>"),
-    "gru nx=2 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 2, 4, true, true, true, false, 1, 2>", "ggnn_gru_fused_kernel<100, 2, 4, false, true, true, false, 1, 2, 1, true>"),
-    "gru nx=3 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 3, 4, true, true, true, false, 1, 2>", "ggnn_gru_fused_kernel<100, 3, 4, false, true, true, false, 1, 2, 1, true>"),
-    "gru nx=1 bf16x3 form 0": ("ggnn_gru_fused_kernel<100, 1, 8, true, true, true, true, 0, 3>", "ggnn_gru_fused_kernel<100, 1, 8, false, true, true, false, 0, 3, 1, true>"),
-    "gru nx=2 bf16x3 form 1": ("ggnn_gru_fused_kernel<100, 2, 4, true, true, true, false, 1, 3>", "ggnn_gru_fused_kernel<100, 2, 4, false, true, true, false, 1, 3, 1, true>"),
-    "gru nx=3 bf16x3 form 1": ("ggnn_gru_fused_kernel<100, 3, 4, true, true, true, false, 1, 3>", "ggnn_gru_fused_kernel<100, 3, 4, false, true, true, false, 1, 3, 1, true>"),
+    "gru nx=1 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 1, 4, false, true, true, false, 1, 2, 1, true>",) * 2,
+    "gru nx=2 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 2, 4, false, true, true, false, 1, 2, 1, true>",) * 2,
+    "gru nx=3 f16x2 form 1": ("ggnn_gru_fused_kernel<100, 3, 4, false, true, true, false, 1, 2, 1, true>",) * 2,
+    "gru nx=1 bf16x3 form 0": ("ggnn_gru_fused_kernel<100, 1, 8, false, true, true, false, 0, 3, 1, true>",) * 2,
+    "gru nx=2 bf16x3 form 1": ("ggnn_gru_fused_kernel<100, 2, 4, false, true, true, false, 1, 3, 1, true>",) * 2,
+    "gru nx=3 bf16x3 form 1": ("ggnn_gru_fused_kernel<100, 3, 4, false, true, true, false, 1, 3, 1, true>",) * 2,
     "compact transform f16x2": ("msg_transform_compact_kernel<100, 8, true, 2>",) * 2,
     "compact transform bf16x3": ("msg_transform_compact_kernel<100, 8, true, 3>",) * 2,
 }
@@ -169,15 +171,13 @@ def main():
                        "encloses matrix instructions)", "kernels": {}}
         for label, (pk, ck) in HOT.items():
             doc["kernels"][label] = {"parent": dict(par[pk], name=pk), "branch": dict(cur[ck], name=ck)}
-        # the generic inference instantiations behind the GGNN_GRU_FORM override (forms 0 and 2), beside the instantiation the parent
-        # ran there (SAVE = true with the stores skipped at run time): registers and scratch only
+        # the generic inference instantiations behind the GGNN_GRU_FORM override (forms 0 and 2): registers and scratch only
         doc["other_inference"] = {}
         keys = ("vgprs", "sgprs", "scratch_bytes", "occupancy")
         for form in (0, 2):
             for fmt in (2, 3):
                 for nx in (1, 2, 3):
-                    pk = "ggnn_gru_fused_kernel<100, %d, 8, true, true, true, %s, %d, %d>" % (nx, "true" if nx == 1 else "false", form, fmt)
-                    ck = "ggnn_gru_fused_kernel<100, %d, 8, false, true, true, false, %d, %d, -1, false>" % (nx, form, fmt)
+                    pk = ck = "ggnn_gru_fused_kernel<100, %d, 8, false, true, true, false, %d, %d, -1, false>" % (nx, form, fmt)
                     doc["other_inference"]["gru nx=%d %s form %d" % (nx, {2: "f16x2", 3: "bf16x3"}[fmt], form)] = {
                         "parent": dict({k: par[pk].get(k) for k in keys}, name=pk), "branch": dict({k: cur[ck].get(k) for k in keys}, name=ck)}
         json.dump(doc, open(a.out, "w"), indent=1, sort_keys=True)
