@@ -29,8 +29,8 @@ constexpr int kXtyWaves = 16;
 constexpr int kXtyMaxI = 4;                    // decoded DMA instructions per wave, operand and slab
 constexpr int kXtySplitWaves = 8;              // the two bf16x3 kernels: 8 waves of 256 registers
 constexpr int kXtySplitMaxI = 8;
-#ifndef GGNN_XTY_TIMELINE
-#define GGNN_XTY_TIMELINE 0
+#ifndef GGNN_XTY_STAMPS
+#define GGNN_XTY_STAMPS 0
 #endif
 #ifndef GGNN_XTY_INTER_MAX
 #define GGNN_XTY_INTER_MAX 24
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(kXtyWaves * 64) void xty_kernel(XtyArgs a) {
 
     // stamps of waves 0 and 15 of workgroup (0,0): [which][0] start, [1] first slab landed, [2+i] slab i consumed, [62] loop done, [63] stored
     int stamp_i = 2;
-#if GGNN_XTY_TIMELINE          // (build with -DGGNN_XTY_TIMELINE=1 for tools/xty_timeline.py: the stamps cost scalar registers in the hot loop)
+#if GGNN_XTY_STAMPS          // (a variant library, tools/variant_lib.sh, for tools/xty_timeline.py: the stamps cost scalar registers in the hot loop)
 #define GGNN_XT(K) if (a.tdbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave == 0 || wave == nw - 1) && (K) < 64) \
         a.tdbg[(wave ? 64 : 0) + (K)] = __builtin_amdgcn_s_memtime();
 #else
@@ -945,7 +945,9 @@ extern "C" int ggnn_xty_acc_f32(const float* const* x_segs, int nseg, int Dseg, 
     a.K = K; a.N = N; a.nbatch = nbatch; a.kb_tiles = sel.kb_tiles; a.n_tiles = sel.n_tiles;
     a.pitch_x = sel.px; a.pitch_y = sel.py;
     for (int b = 0; b <= kXtyMaxBatch; ++b) a.wg_off[b] = p.wg_off[b <= nbatch ? b : nbatch];
+#if GGNN_XTY_STAMPS
     { const char* e = getenv("GGNN_XTY_TPTR"); a.tdbg = e ? (unsigned long long*)strtoull(e, nullptr, 10) : nullptr; }
+#endif
     const XtyCell& c = sel.cell;
 #define GGNN_XTY_LAUNCH(F, G, R, M, Nn)                                                                     \
     if (c.family == F && c.gathered == G && c.rows == R && c.mtm == M && c.ntm == Nn) {                      \

@@ -14,7 +14,7 @@ struct GruBwdArgs {
     // optional: g_eff[v] = g[v] + sum over the (up to four) rows gz_heads[v] names of gz -- the per-node sum that closes the
     // PREVIOUS timestep's transform backward (dh[v] += sum_t Z[row(v,t)]), taken on load here instead of by a launch of its own
     const float* gz; const int* gz_heads;
-    unsigned long long* tdbg;           // debug: s_memtime stamps of workgroup 0 (GGNN_BWD_TPTR; tools/gru_bwd_timeline.py)
+    unsigned long long* tdbg;           // debug: s_memtime stamps of workgroup 0 (-DGGNN_BWD_STAMPS=1 builds only; tools/gru_bwd_timeline.py)
 };
 
 // ggnn_gru_bwd_panel.hip

@@ -174,14 +174,17 @@ def _gru_bwd_formulas(g, h, r, u, c, Wg, Wc, nx, act, den):
 
 @pytest.mark.parametrize("nx", [1, 2, 3])
 @pytest.mark.parametrize("D", [32, 64, 100])
-@pytest.mark.parametrize("V", [1, 17, 4099, 100003])
+@pytest.mark.parametrize("V", [1, 17, 4099, 37571, 100003])
 def test_fused_gru_backward_against_fp64(pkg, oracle_torch, cuda, V, D, nx):
     """ggnn_gru_bwd_fused_f32 and its gather form, tanh and ReLU, mean (with in-degree-0 rows) and sum aggregation, against the
     header's formulas evaluated in float64 on the kernel's own fp32 inputs (r, u, c of an fp64 forward rounded to fp32).  The
     formulas are first checked against fp64 autograd of oracle_torch.gru.  Per element |got - want| <= C 2^-24 m, m the same
     formula on absolute values (|1 - c^2| -> 1 + c^2, |h - c| -> |h| + |c|).  Measured worst C over all cases: 13.9 (V = 100003,
     D = 100, nx = 3), 10-12 at V = 4099; C = 32 is below the worst case of a K-term fp32 sum (K = 2D .. 4D), far above a
-    wrong formula or operand (a dropped term or factor is an O(1 / 2^-24) error)."""
+    wrong formula or operand (a dropped term or factor is an O(1 / 2^-24) error).
+    V = 37571 is the smallest V at 256 CUs where a workgroup runs a full-round pass followed by a tail pass (2349 tiles: 2048 in
+    the full round, the rest as thin tail tickets): the carry of the prefetched inputs across passes, the ring parity and the
+    next-tile prefetch, without the 100003-row case."""
     ops = pkg.ops
     T = 4
     gen = torch.Generator(device=cuda).manual_seed(V * 1000 + D * 10 + nx)
@@ -247,9 +250,12 @@ def test_fused_gru_backward_against_fp64(pkg, oracle_torch, cuda, V, D, nx):
                 if use_avg:
                     mags[4][-1] = mags[4][-1] / den
                 flat = lambda o: list(o[:4]) + list(o[4])
-                for i, (a, b, m) in enumerate(zip(flat(got), flat(want), flat(mags))):
+                ratios = []
+                for a, b, m in zip(flat(got), flat(want), flat(mags)):
                     err = (f64(a) - b).abs()
-                    ratio = float((err / (U32 * m + 1e-300)).max()) if err.numel() else 0.0
+                    ratios.append(float((err / (U32 * m + 1e-300)).max()) if err.numel() else 0.0)
+                print("gru_bwd V=%d D=%d nx=%d %s avg=%d gather=%d worst C %.2f" % (V, D, nx, act, use_avg, gather, max(ratios)))
+                for i, ratio in enumerate(ratios):
                     assert ratio <= GRU_BWD_C, (act, use_avg, gather, ["dpc", "dpg", "rh", "dh"][i] if i < 4 else "dx%d" % (i - 4), ratio)
 
 

@@ -19,6 +19,20 @@ def test_fused_backward_sizes(pkg):
     assert [lib.ggnn_gru_is_fused(D) for D in (128, 192, 256)] == [2, 2, 2]
 
 
+def test_product_library_reads_no_experiment_switches_of_the_training_kernels(pkg):
+    """The fused GRU backward launches one kernel per matrix path, and its clock stamps and the weight-gradient product's are
+    compiled in only in variant libraries (tools/variant_lib.sh): the product library holds none of the variables' names.
+    (GGNN_DG_TPTR / GGNN_DGB_TPTR are not in the list: the graph-resident dense kernels keep their run-time stamps, because
+    compiling them out moved two of those kernels across an occupancy step, profiles/README.md.)"""
+    pkg._lib.load()
+    assert pkg._lib.LIB_PATH.endswith("libggnn_hip.so"), pkg._lib.LIB_PATH
+    with open(pkg._lib.LIB_PATH, "rb") as f:
+        blob = f.read()
+    names = (b"GGNN_BWD_FORM", b"GGNN_BWD_ALIAS", b"GGNN_BWD_TPTR", b"GGNN_XTY_TPTR")
+    assert [n for n in names if n in blob] == []
+    assert b"GGNN_MATRIX" in blob                                              # (a variable the library does read: the search finds names)
+
+
 def test_packed_bytes_of_the_panel_sizes(pkg):
     """3 (nx + 1) transposed D x D blocks, each as D / 64 panel images: three bf16 planes (6 bytes per weight) under the split matrix
     path, f32 (4 bytes) otherwise."""

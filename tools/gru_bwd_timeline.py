@@ -1,6 +1,10 @@
-"""s_memtime timeline of workgroup 0 (waves 0 and 4) of the fused GRU backward (debug stamps behind GGNN_BWD_TPTR).
-   python tools/gru_bwd_timeline.py"""
+"""s_memtime timeline of workgroup 0 (waves 0 and 4) of the fused GRU backward (debug stamps behind GGNN_BWD_TPTR; compiled in only
+with -DGGNN_BWD_STAMPS=1):
+    bash tools/variant_lib.sh btl ggnn_gru_bwd_fused.hip,ggnn_gru_bwd_fused_split.hip -DGGNN_BWD_STAMPS=1
+    GGNN_LIB_VARIANT=btl python tools/gru_bwd_timeline.py"""
 import importlib, os, sys, torch, numpy as np
+if not os.environ.get("GGNN_LIB_VARIANT"):
+    sys.exit("tools/gru_bwd_timeline.py needs a variant library (see the docstring): set GGNN_LIB_VARIANT=btl")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
 V, D, nx, T = 99990, 100, 1, 4

@@ -9,6 +9,7 @@ whole kernel and inside the pass loop (the widest backward branch that encloses 
     # any other kernel family: its translation units and a regex on the demangled kernel names; with them --pair compares every kernel
     python tools/gru_codegen.py --sources ggnn_panel.hip,ggnn_rnn_panel.hip --kernels 'panel_kernel<|ring_kernel<' --out this.json
     python tools/gru_codegen.py --kernels . --pair parent.json this.json --out profiles/panel_shared_layer_codegen.json
+    # (kernels whose template list changed are paired through the RENAMED table below)
 """
 import argparse, json, os, re, subprocess, sys, tempfile
 
@@ -37,6 +38,12 @@ HOT = {
     "compact transform f16x2": ("msg_transform_compact_kernel<100, 8, true, 2>",) * 2,
     "compact transform bf16x3": ("msg_transform_compact_kernel<100, 8, true, 3>",) * 2,
 }
+
+# kernels whose template list changed: parent's name -> this tree's (--pair with --kernels compares them as one kernel).  The fused GRU
+# backward kept one form per matrix path: <D, NX, NW = 8, PREFETCH = 3 | 0, RING = 2, SPLIT> became <D, NX, SPLIT>
+RENAMED = {"ggnn_gru_bwd_fused_kernel<%d, %d, 8, %d, 2, %s>" % (D, nx, 3 if split else 0, "true" if split else "false"):
+           "ggnn_gru_bwd_fused_kernel<%d, %d, %s>" % (D, nx, "true" if split else "false")
+           for D in (32, 64, 100) for nx in (1, 2, 3) for split in (False, True)}
 
 
 def compile_asm(src, out, extra):
@@ -162,6 +169,7 @@ def main():
         par, cur = (json.load(open(p)) for p in a.pair)
         if a.kernels:
             par, cur = ({k: v for k, v in d.items() if kernels.search(k)} for d in (par, cur))
+            par = {RENAMED.get(k, k): v for k, v in par.items()}
             doc = pair_all(par, cur)
             json.dump(doc, open(a.out, "w"), indent=1, sort_keys=True)
             print(json.dumps({k: (v if not isinstance(v, dict) else len(v)) for k, v in doc["summary"].items()}, indent=1))

@@ -7,6 +7,11 @@
 #   tools/variant_lib.sh abl ggnn_gru_fused.hip,ggnn_gru_fused_split.hip -DGGNN_GRU_ABLATE=1
 # the compacted message transform with the stamps behind GGNN_K1C_TPTR (tools/k1c_timeline.py):
 #   tools/variant_lib.sh k1t ggnn_msg_compact.hip -DGGNN_K1C_STAMPS=1
+# the fused GRU backward with the stamps behind GGNN_BWD_TPTR (tools/gru_bwd_timeline.py):
+#   tools/variant_lib.sh btl ggnn_gru_bwd_fused.hip,ggnn_gru_bwd_fused_split.hip -DGGNN_BWD_STAMPS=1
+# the weight-gradient product with the stamps behind GGNN_XTY_TPTR (tools/xty_timeline.py):
+#   tools/variant_lib.sh xtl ggnn_bwd_gemm.hip -DGGNN_XTY_STAMPS=1
+# (tools/dense_graph_timeline.py needs none: the stamps of the graph-resident dense kernels are run-time, GGNN_DG_TPTR / GGNN_DGB_TPTR)
 set -e
 tag=$1; srcs=$2; shift; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd); P=$ROOT/gated-graph-neural-network-samples_amd

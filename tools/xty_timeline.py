@@ -1,6 +1,10 @@
-"""s_memtime timeline of workgroup (0,0,0) of ggnn_xty_f32 (debug stamps behind GGNN_XTY_TPTR), and the launch time as a
-function of the row count.   python tools/xty_timeline.py"""
+"""s_memtime timeline of workgroup (0,0,0) of ggnn_xty_f32 (debug stamps behind GGNN_XTY_TPTR; compiled in only with
+-DGGNN_XTY_STAMPS=1), and the launch time as a function of the row count:
+    bash tools/variant_lib.sh xtl ggnn_bwd_gemm.hip -DGGNN_XTY_STAMPS=1
+    GGNN_LIB_VARIANT=xtl python tools/xty_timeline.py"""
 import importlib, os, sys, torch, numpy as np
+if not os.environ.get("GGNN_LIB_VARIANT"):
+    sys.exit("tools/xty_timeline.py needs a variant library (see the docstring): set GGNN_LIB_VARIANT=xtl")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("gated-graph-neural-network-samples_amd")
 dev = "cuda:0"
