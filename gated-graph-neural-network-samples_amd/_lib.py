@@ -38,6 +38,7 @@ SYMBOLS = {
     "ggnn_msg_transform_compact_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ggnn_msg_transform_compact_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_size_t,
                                                c_int, c_int, c_int, c_int, c_void_p]),
+    "ggnn_msg_transform_compact_describe": (c_int, [c_int, c_int, POINTER(c_int64), c_int, POINTER(c_int32)]),
     "ggnn_gather_segment_sum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                             c_int, c_int, c_int, c_void_p]),
     "ggnn_build_slot_heads": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

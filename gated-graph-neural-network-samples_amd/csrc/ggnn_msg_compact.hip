@@ -170,13 +170,43 @@ __global__ __launch_bounds__(NW * 64, 4) /* 4 waves per SIMD = 2 workgroups per 
     K1C_T(7)
 }
 
+// ---- which kernel, in which format, on how many workgroups: host arithmetic shared by the launch and the describe query -----------
+// waves per workgroup: 8, two workgroups per CU.  (One 16-wave workgroup per CU halves the image DMA and evens out
+// the prologues -- the second workgroup of a CU otherwise starts 5 us late behind the first one's MFMA bursts --
+// but measures the same alone (32.8 us) and 2 % slower with two streams: 608 vs 621 M node-updates/s.)
+constexpr int kCompactNW = 8;
+
+// tile_off[0 .. T]: the workgroups of the types with compact rows row_off[0 .. T].
+// Workgroups per type: the smallest number of rounds R (wave tiles per wave) for which all types together fit
+// two workgroups per CU, then ceil(wave tiles of the type / (R * NW)) workgroups for each type.
+static void compact_tile_offsets(const int* row_off, int T, int* tile_off) {
+    constexpr int NW = kCompactNW;
+    long long total_wt = 0;
+    for (int t = 0; t < T; ++t) total_wt += (row_off[t + 1] - row_off[t] + 15) / 16;
+    // workgroups per CU: 2 (16 waves; both forms stay below 128 registers and 2 x 72 KiB of images fit the LDS); GGNN_K1_WG_PER_CU=1 to compare
+    static const int wg_per_cu = [] { const char* e = getenv("GGNN_K1_WG_PER_CU"); return e && atoi(e) == 1 ? 1 : 2; }();
+    const long long budget = (long long)wg_per_cu * num_cus();
+    long long R = total_wt / (budget * NW);
+    if (R < 1) R = 1;
+    for (;; ++R) {
+        long long blocks = 0;
+        for (int t = 0; t < T; ++t) blocks += ((row_off[t + 1] - row_off[t] + 15) / 16 + R * NW - 1) / (R * NW);
+        if (blocks <= budget) break;
+    }
+    tile_off[0] = 0;
+    for (int t = 0; t < T; ++t)
+        tile_off[t + 1] = tile_off[t] + (int)(((row_off[t + 1] - row_off[t] + 15) / 16 + R * NW - 1) / (R * NW));
+}
+
+// the operand format the whole-block kernel of hidden size D multiplies in when the launch asks for `fmt`: 0 = the f32 MFMA (GGNN_MATRIX=f32;
+// `fmt` is ignored), else kSplitF16x2 where asked for and kSplitBf16x3 for every other value
+template <int D>
+static int compact_operand_format(int fmt) { return SplitCfg<D>::OK && split_matrix_path() ? gru_launch_fmt(fmt) : 0; }
+
 template <int D, bool SPLIT, int FMT = kSplitBf16x3>
 static int launch_compact_m(const float* h, const float* W, const int* pair_node, TypeRows& tr, float* packed, float* Hc,
                             hipStream_t st) {
-    // waves per workgroup: 8, two workgroups per CU.  (One 16-wave workgroup per CU halves the image DMA and evens out
-    // the prologues -- the second workgroup of a CU otherwise starts 5 us late behind the first one's MFMA bursts --
-    // but measures the same alone (32.8 us) and 2 % slower with two streams: 608 vs 621 M node-updates/s.)
-    constexpr int NW = 8;
+    constexpr int NW = kCompactNW;
     using C = ImgCfg<D, SPLIT, FMT>;
     if (W) {      // raw [T,D,D] weights given: build the T stage images (skipped when the caller pre-packed them)
         hipLaunchKernelGGL((edge_weight_pack_kernel<D, SPLIT, FMT>), dim3(8, tr.T), dim3(256), 0, st, W, packed);
@@ -186,23 +216,7 @@ static int launch_compact_m(const float* h, const float* W, const int* pair_node
     const int V = tr.num_nodes;
     if ((unsigned long long)tr.row_off[tr.T] * D >= (1ULL << 30) || (unsigned long long)V * D >= (1ULL << 30))
         return fail(GGNN_E_UNSUPPORTED, "compacted transform indexes with 32-bit byte offsets: rows*D and V*D must be < 2^30");
-    // Workgroups per type: the smallest number of rounds R (wave tiles per wave) for which all types together fit
-    // two workgroups per CU, then ceil(wave tiles of the type / (R * NW)) workgroups for each type.
-    long long total_wt = 0;
-    for (int t = 0; t < tr.T; ++t) total_wt += (tr.row_off[t + 1] - tr.row_off[t] + 15) / 16;
-    // workgroups per CU: 2 (16 waves; both forms stay below 128 registers and 2 x 72 KiB of images fit the LDS); GGNN_K1_WG_PER_CU=1 to compare
-    static const int wg_per_cu = [] { const char* e = getenv("GGNN_K1_WG_PER_CU"); return e && atoi(e) == 1 ? 1 : 2; }();
-    const long long budget = (long long)wg_per_cu * num_cus();
-    long long R = total_wt / (budget * NW);
-    if (R < 1) R = 1;
-    for (;; ++R) {
-        long long blocks = 0;
-        for (int t = 0; t < tr.T; ++t) blocks += ((tr.row_off[t + 1] - tr.row_off[t] + 15) / 16 + R * NW - 1) / (R * NW);
-        if (blocks <= budget) break;
-    }
-    tr.tile_off[0] = 0;
-    for (int t = 0; t < tr.T; ++t)
-        tr.tile_off[t + 1] = tr.tile_off[t] + (int)(((tr.row_off[t + 1] - tr.row_off[t] + 15) / 16 + R * NW - 1) / (R * NW));
+    compact_tile_offsets(tr.row_off, tr.T, tr.tile_off);
     static std::atomic<unsigned long long> lds_ok{0};
     if (C::IMG_BYTES > 48 * 1024) GGNN_CHECK_HIP(allow_dynamic_lds(&msg_transform_compact_kernel<D, NW, SPLIT, FMT>, C::IMG_BYTES, lds_ok));
 #if GGNN_K1C_STAMPS
@@ -217,10 +231,11 @@ static int launch_compact_m(const float* h, const float* W, const int* pair_node
 template <int D>
 static int launch_compact(const float* h, const float* W, const int* pair_node, TypeRows& tr, float* packed, float* Hc, int fmt,
                           hipStream_t st) {
-    if (SplitCfg<D>::OK && split_matrix_path())
-        return gru_launch_fmt(fmt) == kSplitF16x2 ? launch_compact_m<D, true, kSplitF16x2>(h, W, pair_node, tr, packed, Hc, st)
-                                                  : launch_compact_m<D, true>(h, W, pair_node, tr, packed, Hc, st);
-    return launch_compact_m<D, false>(h, W, pair_node, tr, packed, Hc, st);
+    switch (compact_operand_format<D>(fmt)) {
+        case kSplitF16x2: return launch_compact_m<D, true, kSplitF16x2>(h, W, pair_node, tr, packed, Hc, st);
+        case kSplitBf16x3: return launch_compact_m<D, true>(h, W, pair_node, tr, packed, Hc, st);
+        default: return launch_compact_m<D, false>(h, W, pair_node, tr, packed, Hc, st);
+    }
 }
 
 int msg_transform_compact_zero(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off, float* Hc,
@@ -229,6 +244,7 @@ int gru_panel_supported(int D);      // ggnn_panel.hip: hidden sizes handled on 
 int transform_panel_image_floats(int D);
 int transform_panel_dispatch(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V, int D,
                              float* packed, float* Hc, int fmt, hipStream_t st);
+int transform_panel_describe(int D, const int* row_off, int T, int fmt, int* family, int* fmt_used, int* nw, int* wg, int* waves);
 
 static int stage_img_floats(int D) {
     if (gru_panel_supported(D)) return (D / 64) * transform_panel_image_floats(D);      // NP panel images per type
@@ -314,6 +330,22 @@ extern "C" int ggnn_edge_weights_pack_f32(const float* W, int T, int D, int fmt,
     }
 }
 
+// the checks of the sizes and of the HOST row offsets that the launch and the describe query share; row_off[0 .. T] <- type_row_off
+static int compact_check_rows(int V, int D, int T, int fmt, const int64_t* type_row_off, int* row_off) {
+    GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0 && T > 0 && T <= kMaxTypesC, "bad sizes V=%d D=%d T=%d", V, D, T);
+    GGNN_CHECK_ARG(fmt == 0 || fmt == GGNN_GRU_FMT_F16X2 || fmt == GGNN_GRU_FMT_BF16X3, "fmt %d is not a GGNN_GRU_FMT_* value", fmt);
+    GGNN_CHECK_ARG(type_row_off, "null pointer");
+    if (!ggnn_msg_transform_compact_supported(D))
+        return fail(GGNN_E_UNSUPPORTED, "compacted message transform supports hidden sizes 32, 64, 100, 128, 192, 256 (got %d)", D);
+    GGNN_CHECK_ARG(type_row_off[0] == 0, "type_row_off must start at 0");
+    for (int t = 0; t < T; ++t) {
+        GGNN_CHECK_ARG(type_row_off[t] <= type_row_off[t + 1] && type_row_off[t + 1] < (1LL << 31), "type_row_off not monotone");
+        row_off[t] = (int)type_row_off[t];
+    }
+    row_off[T] = (int)type_row_off[T];
+    return GGNN_OK;
+}
+
 // W == NULL: `ws` already holds the images written by ggnn_edge_weights_pack_f32 (inference: weights are
 // constant across batches, so the pack pre-pass is paid once per weight version instead of once per call).
 // zero (may be NULL): an int32 that is 0 once the call's work on the stream is done -- written by one thread of the transform launch
@@ -321,23 +353,12 @@ extern "C" int ggnn_edge_weights_pack_f32(const float* W, int T, int D, int fmt,
 // (the library's own entry: ggnn_propagate.hip passes the ticket counter of the timestep's fused GRU launch)
 int ggnn::msg_transform_compact_zero(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off, float* Hc,
                                      void* ws, size_t ws_bytes, int V, int D, int T, int fmt, int32_t* zero, ggnn_stream_t stream) {
-    GGNN_CHECK_ARG(V >= 0 && D > 0 && D % 4 == 0 && T > 0 && T <= kMaxTypesC, "bad sizes V=%d D=%d T=%d", V, D, T);
-    GGNN_CHECK_ARG(fmt == 0 || fmt == GGNN_GRU_FMT_F16X2 || fmt == GGNN_GRU_FMT_BF16X3, "fmt %d is not a GGNN_GRU_FMT_* value", fmt);
-    GGNN_CHECK_ARG(type_row_off, "null pointer");
-    if (!ggnn_msg_transform_compact_supported(D))
-        return fail(GGNN_E_UNSUPPORTED, "compacted message transform supports hidden sizes 32, 64, 100, 128, 192, 256 (got %d)", D);
     TypeRows tr{};
+    const int rc = compact_check_rows(V, D, T, fmt, type_row_off, tr.row_off);
+    if (rc != GGNN_OK) return rc;
     tr.T = T;
     tr.num_nodes = V;
     tr.zero = zero;
-    tr.tile_off[0] = 0;
-    GGNN_CHECK_ARG(type_row_off[0] == 0, "type_row_off must start at 0");
-    for (int t = 0; t < T; ++t) {
-        GGNN_CHECK_ARG(type_row_off[t] <= type_row_off[t + 1] && type_row_off[t + 1] < (1LL << 31), "type_row_off not monotone");
-        tr.row_off[t] = (int)type_row_off[t];
-        tr.tile_off[t + 1] = tr.tile_off[t] + (int)((type_row_off[t + 1] - type_row_off[t] + 127) / 128);
-    }
-    tr.row_off[T] = (int)type_row_off[T];
     hipStream_t st = (hipStream_t)stream;
     if (zero && (tr.row_off[T] == 0 || gru_panel_supported(D))) GGNN_CHECK_HIP(hipMemsetAsync(zero, 0, sizeof(int32_t), st));
     if (tr.row_off[T] == 0) return GGNN_OK;
@@ -352,6 +373,40 @@ int ggnn::msg_transform_compact_zero(const float* h, const float* W, const int32
         case 64: return launch_compact<64>(h, W, pair_node, tr, packed, Hc, fmt, st);
         default: return launch_compact<32>(h, W, pair_node, tr, packed, Hc, fmt, st);
     }
+}
+
+extern "C" int ggnn_msg_transform_compact_describe(int D, int T, const int64_t* type_row_off, int fmt, int32_t* out) {
+    int row_off[kMaxTypesC + 1], wg[kMaxTypesC] = {}, waves[kMaxTypesC] = {};
+    const int rc = compact_check_rows(0, D, T, fmt, type_row_off, row_off);
+    if (rc != GGNN_OK) return rc;
+    GGNN_CHECK_ARG(out, "null pointer");
+    if ((unsigned long long)row_off[T] * D >= (1ULL << 30))
+        return fail(GGNN_E_UNSUPPORTED, "compacted transform indexes with 32-bit byte offsets: rows*D and V*D must be < 2^30");
+    int family = GGNN_MSG_TRANSFORM_WHOLE_BLOCK, used = 0, nw = kCompactNW;
+    if (gru_panel_supported(D)) {
+        const int prc = transform_panel_describe(D, row_off, T, fmt, &family, &used, &nw, wg, waves);
+        if (prc != GGNN_OK) return prc;
+    } else {
+        used = D == 100 ? compact_operand_format<100>(fmt) : D == 64 ? compact_operand_format<64>(fmt) : compact_operand_format<32>(fmt);
+        if (row_off[T]) {
+            int tile_off[kMaxTypesC + 1];
+            compact_tile_offsets(row_off, T, tile_off);
+            for (int t = 0; t < T; ++t) {
+                wg[t] = tile_off[t + 1] - tile_off[t];
+                waves[t] = wg[t] * kCompactNW;
+            }
+        }
+    }
+    out[0] = family; out[1] = used; out[2] = nw; out[3] = 0;
+    for (int t = 0; t < T; ++t) {
+        // tiles i, i + waves, ... belong to wave i of the type: ceil((n - i) / waves) of them
+        const int n_wt = (row_off[t + 1] - row_off[t] + 15) / 16;
+        out[3] += wg[t];
+        out[4 + 3 * t] = wg[t];
+        out[5 + 3 * t] = waves[t] ? (n_wt + waves[t] - 1) / waves[t] : 0;
+        out[6 + 3 * t] = waves[t] ? n_wt / waves[t] : 0;
+    }
+    return GGNN_OK;
 }
 
 extern "C" int ggnn_msg_transform_compact_f32(const float* h, const float* W, const int32_t* pair_node,

@@ -620,31 +620,50 @@ int transform_panel_image_floats(int D) {
     return panel_for_D(D, [&](auto d) { return sp ? PanelSplitCfg<decltype(d)::value>::IMG : PanelCfg<decltype(d)::value>::IMG; });
 }
 
-// FMT: only the ring kernel (split path) has the two-piece f16 form; the stationary-image kernel and the f32 path ignore it
+// ---- which kernel, in which format, on how many workgroups: host arithmetic shared by the launch and the describe query -----------
+// The kernel family (GGNN_MSG_TRANSFORM_* of include/ggnn_hip.h), the matrix path and the operand format of a launch asked for `fmt`
+// in this process.  Only the ring kernel (split path) has the two-piece f16 form; the stationary-image kernel and the f32 path ignore it.
+struct PanelTransformChoice {
+    int family;        // GGNN_MSG_TRANSFORM_RING / GGNN_MSG_TRANSFORM_STATIONARY
+    bool split;
+    int fmt;           // the operand format multiplied in: 0 on the f32 MFMA, else kSplitBf16x3 / kSplitF16x2
+};
+static PanelTransformChoice transform_panel_choice(int fmt) {
+    if (!split_matrix_path()) return {GGNN_MSG_TRANSFORM_STATIONARY, false, 0};
+    if (!transform_ring()) return {GGNN_MSG_TRANSFORM_STATIONARY, true, kSplitBf16x3};
+    return {GGNN_MSG_TRANSFORM_RING, true, gru_launch_fmt(fmt)};
+}
+
+// the workgroups of every type under choice `c`
+template <int D>
+static PanelRows transform_panel_rows(const PanelTransformChoice& c, const int* row_off, int T) {
+    constexpr int NP = PanelCfg<D>::NP;
+    // ring: workgroups per type in proportion to its rows (one per CU all types together)
+    if (c.family == GGNN_MSG_TRANSFORM_RING) return panel_rows(row_off, T, num_cus(), 1);
+    // stationary: one workgroup per CU (64 KiB image + ~176 VGPRs per wave); every type gets workgroups in proportion to its rows,
+    // the same number on each of its NP panels, at least one per panel
+    return panel_rows(row_off, T, num_cus() / NP > 0 ? num_cus() / NP : 1, NP);
+}
+
 template <int D, bool SPLIT, int FMT = kSplitBf16x3>
-static int launch_transform_panel_m(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V,
-                                  float* packed, float* Hc, hipStream_t st) {
+static int launch_transform_panel_m(const PanelTransformChoice& c, const float* h, const float* W, const int* pair_node, const int* row_off,
+                                    int T, int V, float* packed, float* Hc, hipStream_t st) {
     using C = PanelCfg<D>;
     constexpr int NP = C::NP;
     if (W) {
-        hipLaunchKernelGGL((edge_weight_panel_pack_kernel<D, SPLIT, FMT>), dim3(8, T * NP), dim3(256), 0, st, W, packed, (int)(SPLIT && transform_ring()));
+        hipLaunchKernelGGL((edge_weight_panel_pack_kernel<D, SPLIT, FMT>), dim3(8, T * NP), dim3(256), 0, st, W, packed, (int)(c.family == GGNN_MSG_TRANSFORM_RING));
         GGNN_CHECK_HIP(hipGetLastError());
     }
     const int R = row_off[T];
     if (R == 0 || h == nullptr) return GGNN_OK;
     if ((unsigned long long)R * D >= (1ULL << 30) || (unsigned long long)V * D >= (1ULL << 30))
         return fail(GGNN_E_UNSUPPORTED, "compacted transform indexes with 32-bit byte offsets: rows*D and V*D must be < 2^30");
+    const PanelRows pr = transform_panel_rows<D>(c, row_off, T);
     if constexpr (SPLIT) {
-        if (transform_ring()) {
-            // workgroups per type in proportion to its rows (one per CU all types together)
-            const PanelRows rr = panel_rows(row_off, T, num_cus(), 1);
+        if (c.family == GGNN_MSG_TRANSFORM_RING)
             return panel_launch<&msg_transform_ring_kernel<D, kPanelNW, FMT>>((size_t)2 * PanelGruSplitCfg<D, FMT>::PART_BYTES, 48 * 1024,
-                                                                               rr.wg_off[T], st, h, pair_node, rr, (const float*)packed, Hc);
-        }
+                                                                               pr.wg_off[T], st, h, pair_node, pr, (const float*)packed, Hc);
     }
-    // one workgroup per CU (64 KiB image + ~176 VGPRs per wave); every type gets workgroups in proportion to its rows,
-    // the same number on each of its NP panels, at least one per panel
-    const PanelRows pr = panel_rows(row_off, T, num_cus() / NP > 0 ? num_cus() / NP : 1, NP);
     return panel_launch<&msg_transform_panel_kernel<D, kPanelNW, SPLIT>>(SPLIT ? PanelSplitCfg<D>::IMG_BYTES : C::IMG_BYTES, 48 * 1024,
                                                                           pr.wg_off[T], st, h, pair_node, pr, (const float*)packed, Hc);
 }
@@ -652,11 +671,32 @@ static int launch_transform_panel_m(const float* h, const float* W, const int* p
 template <int D>
 static int launch_transform_panel(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V,
                                   float* packed, float* Hc, int fmt, hipStream_t st) {
-    if (split_matrix_path())
-        return (gru_launch_fmt(fmt) == kSplitF16x2 && transform_ring())
-                   ? launch_transform_panel_m<D, true, kSplitF16x2>(h, W, pair_node, row_off, T, V, packed, Hc, st)
-                   : launch_transform_panel_m<D, true>(h, W, pair_node, row_off, T, V, packed, Hc, st);
-    return launch_transform_panel_m<D, false>(h, W, pair_node, row_off, T, V, packed, Hc, st);
+    const PanelTransformChoice c = transform_panel_choice(fmt);
+    if (!c.split) return launch_transform_panel_m<D, false>(c, h, W, pair_node, row_off, T, V, packed, Hc, st);
+    return c.fmt == kSplitF16x2 ? launch_transform_panel_m<D, true, kSplitF16x2>(c, h, W, pair_node, row_off, T, V, packed, Hc, st)
+                                : launch_transform_panel_m<D, true>(c, h, W, pair_node, row_off, T, V, packed, Hc, st);
+}
+
+// ggnn_msg_transform_compact_describe at a panel hidden size: what launch_transform_panel would start for these rows.  wg[t] (zeroed by
+// the caller): the workgroups of type t (all its panels); waves[t]: the waves that share ONE walk over the type's 16-row tiles (a
+// stationary type's workgroups are split between its NP panels, each panel's walking all tiles).
+int transform_panel_describe(int D, const int* row_off, int T, int fmt, int* family, int* fmt_used, int* nw, int* wg, int* waves) {
+    if (T > kMaxTypesP) return fail(GGNN_E_UNSUPPORTED, "more than %d edge types", kMaxTypesP);
+    if (!panel_hidden_ok(D)) return fail(GGNN_E_UNSUPPORTED, "no panel transform for hidden size %d", D);
+    const PanelTransformChoice c = transform_panel_choice(fmt);
+    *family = c.family;
+    *fmt_used = c.fmt;
+    *nw = kPanelNW;
+    if (row_off[T] == 0) return GGNN_OK;      // no rows: the launch returns before its schedule (wg / waves stay as the caller zeroed them)
+    return panel_for_D(D, [&](auto d) {
+        constexpr int NP = PanelCfg<decltype(d)::value>::NP;
+        const PanelRows pr = transform_panel_rows<decltype(d)::value>(c, row_off, T);
+        for (int t = 0; t < T; ++t) {
+            wg[t] = pr.wg_off[t + 1] - pr.wg_off[t];
+            waves[t] = wg[t] / (c.family == GGNN_MSG_TRANSFORM_RING ? 1 : NP) * kPanelNW;
+        }
+        return GGNN_OK;
+    });
 }
 
 int transform_panel_dispatch(const float* h, const float* W, const int* pair_node, const int* row_off, int T, int V, int D,

@@ -1153,6 +1153,21 @@ def msg_transform_compact_packed(h: torch.Tensor, packed: torch.Tensor, T: int, 
     return out
 
 
+MSG_TRANSFORM_FAMILIES = ("whole-block", "ring", "stationary")      # GGNN_MSG_TRANSFORM_* of include/ggnn_hip.h
+
+
+def msg_transform_compact_describe(D: int, type_row_off: Sequence[int], fmt: int = GRU_FMT_EXACT) -> Dict[str, Any]:
+    """What ggnn_msg_transform_compact_f32 launches in this process for these rows (the launchers' own selection and schedule; no
+    GPU work): {'family': one of MSG_TRANSFORM_FAMILIES, 'fmt': 0 for the f32 MFMA or the GRU_FMT_* multiplied in, 'waves': per
+    workgroup, 'workgroups': of the launch, 'types': [(workgroups, most tiles a wave walks, fewest), ...]}."""
+    T = len(type_row_off) - 1
+    off = (ctypes.c_int64 * (T + 1))(*type_row_off)
+    out = (ctypes.c_int32 * (4 + 3 * max(T, 0)))()
+    check(_lib.load().ggnn_msg_transform_compact_describe(int(D), T, off, int(fmt), out))
+    return {"family": MSG_TRANSFORM_FAMILIES[out[0]], "fmt": out[1], "waves": out[2], "workgroups": out[3],
+            "types": [tuple(out[4 + 3 * t:7 + 3 * t]) for t in range(T)]}
+
+
 def _ptr_array(tensors):
     if tensors is None:
         return None

@@ -164,7 +164,7 @@ int ggnn_msg_transform_f32(const float* h, int ldh, const float* W, float* H, in
  *                                type_row_off DEVICE [T+1] (rows of type t are type_row_off[t] .. [t+1]-1)
  *   ggnn_remap_gather_rows       gather_row [M] (src*T+type) -> compact rows, for ggnn_gather_segment_sum_f32
  *   ggnn_msg_transform_compact_f32  Hc[r,:] = h[pair_node[r],:] @ W[type(r)]   (Hc [R,D]; type_row_off on the HOST)
- * Supported hidden sizes: ggnn_msg_transform_compact_supported(D) (32, 64, 100).
+ * Supported hidden sizes: ggnn_msg_transform_compact_supported(D) (32, 64, 100, 128, 192, 256).
  */
 int ggnn_msg_transform_compact_supported(int D);
 size_t ggnn_compact_workspace_bytes(int V, int T);
@@ -175,6 +175,22 @@ int ggnn_remap_gather_rows(const int32_t* gather_row, const int32_t* pair_id, in
 size_t ggnn_msg_transform_compact_workspace_bytes(int D, int T);
 int ggnn_msg_transform_compact_f32(const float* h, const float* W, const int32_t* pair_node, const int64_t* type_row_off,
                                    float* Hc, void* ws, size_t ws_bytes, int V, int D, int T, int fmt, ggnn_stream_t stream);
+/* Which kernel ggnn_msg_transform_compact_f32 launches for (D, T, type_row_off, fmt) IN THIS PROCESS and on what schedule -- the
+ * launchers' own selection and schedule functions, host arithmetic only (never touches the GPU; GGNN_MATRIX, GGNN_PANEL_TRANSFORM and
+ * GGNN_K1_WG_PER_CU are read once per process).  out [4 + 3 T]:
+ *   out[0]  kernel family: GGNN_MSG_TRANSFORM_WHOLE_BLOCK (D = 32 / 64 / 100: a workgroup holds its type's whole D x D image),
+ *           GGNN_MSG_TRANSFORM_RING (D = 128 / 192 / 256, split path: the type's column-panel images stream through an LDS ring),
+ *           GGNN_MSG_TRANSFORM_STATIONARY (those sizes on the f32 MFMA or with GGNN_PANEL_TRANSFORM=0: one panel image per workgroup)
+ *   out[1]  the operand format the products run in: 0 = the f32 MFMA, else GGNN_GRU_FMT_BF16X3 / GGNN_GRU_FMT_F16X2 (the f32 kernels
+ *           and the stationary kernel ignore `fmt`; every other value of `fmt` than F16X2 means BF16X3)
+ *   out[2]  waves per workgroup;  out[3]  workgroups of the launch (0: no rows, nothing is launched)
+ *   per type t, at out[4 + 3 t]: its workgroups (stationary: over all its panels), the most and the fewest 16-row tiles any of its
+ *           waves walks (the waves of a type share its tiles round-robin: the two differ by at most one).
+ * Returns what the launch returns for these arguments before it looks at a pointer (0 / GGNN_E_INVALID / GGNN_E_UNSUPPORTED). */
+#define GGNN_MSG_TRANSFORM_WHOLE_BLOCK 0
+#define GGNN_MSG_TRANSFORM_RING 1
+#define GGNN_MSG_TRANSFORM_STATIONARY 2
+int ggnn_msg_transform_compact_describe(int D, int T, const int64_t* type_row_off, int fmt, int32_t* out);
 
 /* ---- (a-2,a-4..a-7) gather + segment sum + bias + mean: chem_tensorflow_sparse.py:160-162,168,
  *      198-209 ------------------------------------------------------------------------------------

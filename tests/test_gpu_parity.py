@@ -543,7 +543,9 @@ def test_golden_fixture_on_gpu(pkg, oracle, cuda):
                                      (3000, 9000, 256, 4), (1500, 4000, 128, 3), (900, 2000, 192, 2), (20000, 90000, 256, 5)])
 def test_compact_transform_equals_dense_form(pkg, oracle, cuda, V, M, D, T):
     """Compact rows are exactly the rows of the dense transform that some message reads; the segment sum over
-    compact rows equals the segment sum over dense rows bit for bit (same fmaf chains, same slot order)."""
+    compact rows equals the segment sum over dense rows bit for bit (same fmaf chains, same slot order).
+    This test pins the pair structure and the segment-sum equality; the per-kernel float64 coverage -- every row of every type of
+    each of the 21 instantiations, the multi-pass loop, the guard rows -- lives in tests/test_gpu_msg_transform_cells.py."""
     rng = np.random.default_rng(V + M)
     h, adj, nin = random_graph_batch(rng, V, M, T, D, sorted_src=True)
     W = rng.uniform(-0.3, 0.3, (T, D, D)).astype(np.float32)
