@@ -7,7 +7,7 @@ Per timestep (chem_tensorflow_dense.py:100-115):
 Inference / validation runs all timesteps in one graph-resident launch (ggnn_dense_propagate_f32).  Training runs the dense step as
 the sparse step it is on the b*v padded nodes (_compute_for_training: the hand-written backward of backward.PropagationStepFn), or,
 with params['graph_resident_training'], on the graph-resident forward and backward launches (backward.DensePropagateFn); with the
-value 'native' of that key the whole optimisation step is two native calls without torch.autograd (train_native.native_dense_train_step).
+value 'native' of that key the whole optimisation step is two native calls without torch.autograd (train_native.ROUTES, entry `dense`).
 With params['pack_on_device'] the batches are assembled on the GPU from the resident dataset (ggnn_dense_assemble_batch), training
 batches together with that sparse form.
 """
@@ -180,7 +180,7 @@ class DenseGGNNChemModel(ChemModel):
         params['graph_resident_training'] (default False): where the graph-resident kernels exist for the batch (_graph_resident_step)
         all timesteps run as ONE differentiable op instead -- one saving forward launch, one backward launch, the weight gradients
         once per variable (backward.DensePropagateFn); every other batch takes the route above.  The value 'native' of the key asks
-        for train_native.native_dense_train_step, which train.train_step dispatches to before this function is reached; being truthy, it
+        for the dense route of train_native.ROUTES, which train.train_step dispatches to before this function is reached; being truthy, it
         sends a batch the native step cannot take through the graph-resident route here, and from there to the route above."""
         from .autograd import propagation_step
         ph = self.placeholders

@@ -6,7 +6,7 @@ running as one fused aggregate-transform HIP launch (csrc/ggnn_gcn.hip) at hidde
 weighted segment sum -> GEMM -> epilogue at the others -- or, with params['gcn_panel_layers'] = True, as one launch of the
 column-panel kernel (csrc/ggnn_gcn_panel.hip) at hidden sizes 128 / 192 / 256.  Inference runs all layers behind one native call
 (ggnn_gcn_propagate_f32); training runs GCNLayerFn per layer (hand-written backward, no autograd on the kernels), or with
-params['native_training'] = True the whole step as two native calls (train_native.native_gcn_train_step, csrc/ggnn_gcn_train.hip:
+params['native_training'] = True the whole step as two native calls (train_native.ROUTES, entry `gcn`, csrc/ggnn_gcn_train.hip:
 hidden sizes 32 / 64 / 100, and 128 / 192 / 256 when params['gcn_panel_layers'] is set as well).
 The readout and loss are the fused kernels of the sparse GGNN (chem_tensorflow_gcn.py:84-93 is the same formula).
 """
@@ -111,7 +111,7 @@ class SparseGCNChemModel(ChemModel):
                        })
         # (params['pack_on_device'], default False, is read with .get like the sparse model's: a key in this dict would break
         # restoring the reference's checkpoints, whose params must match key for key, chem_tensorflow.py:336-340.  So is
-        # params['native_training'], default False: the optimisation step on train_native.native_gcn_train_step, and
+        # params['native_training'], default False: the optimisation step on the gcn route of train_native.ROUTES, and
         # params['gcn_panel_layers'], default False: hidden sizes 128 / 192 / 256 on the column-panel kernel, gcn_panel_route)
         return params
 

@@ -215,24 +215,11 @@ def train_step(model, batch_data) -> torch.Tensor:
     are combined by all-reducing the loss numerator-gradients and the mask count, not by averaging
     per-rank losses (see parallel.DataParallelContext.reduce_gradients)."""
     from . import train_native
-    if train_native.eligible(model, batch_data):
-        # the default model: forward, backward and weight-gradient products as native launch sequences (csrc/ggnn_train.hip)
-        return train_native.native_train_step(model, batch_data)
-    if train_native.attn_eligible(model, batch_data):
-        # propagation attention on the compacted route with compact_attention == 'native': the same two sequences in their attention form
-        return train_native.native_attn_train_step(model, batch_data)
-    if train_native.panel_eligible(model, batch_data):
-        # the default model at hidden 128 / 192 / 256 with native_panel_training: the same two sequences on their panel route
-        return train_native.native_panel_train_step(model, batch_data)
-    if train_native.rnn_eligible(model, batch_data):
-        # the BasicRNNCell on the compacted route with compact_rnn == 'native': the same two sequences in their RNN form
-        return train_native.native_rnn_train_step(model, batch_data)
-    if train_native.dense_eligible(model, batch_data):
-        # the dense model with graph_resident_training == 'native': the same on the graph-resident kernels (csrc/ggnn_dense_train.hip)
-        return train_native.native_dense_train_step(model, batch_data)
-    if train_native.gcn_eligible(model, batch_data):
-        # the sparse GCN with native_training: the same on the fused layer kernels (csrc/ggnn_gcn_train.hip)
-        return train_native.native_gcn_train_step(model, batch_data)
+    # forward, backward and weight-gradient products as native launch sequences, where a route of train_native.ROUTES takes this
+    # model and batch (asked per step, in the table's order: a default model pays for one predicate); else autograd, below
+    for route in train_native.ROUTES:
+        if route.eligible(model, batch_data):
+            return train_native.native_step(route, model, batch_data)
     variables =list(model.trainable_variables.values())
     for v in variables:
         v.requires_grad_(True)

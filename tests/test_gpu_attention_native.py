@@ -1,5 +1,5 @@
 """GPU tests of the native training step of the sparse GGNN with propagation attention (params['compact_attention'] == 'native';
-train_native.native_attn_train_step on ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32): gradients against
+train_native.ROUTES, entry `attention`, on ggnn_sparse_attn_train_forward_f32 / ggnn_sparse_attn_train_backward_f32): gradients against
 float64 with the attention factors as leaves, the route taken, the step against the key-True route (variants.CompactAttentionStepFn),
 determinism, the fall-backs and the reference's recorded run (chem_tensorflow_sparse.py:117-218, chem_tensorflow.py:183-191)."""
 import numpy as np

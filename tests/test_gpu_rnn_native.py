@@ -1,5 +1,5 @@
 """GPU tests of the native training step of the sparse GGNN with the BasicRNNCell (params['compact_rnn'] == 'native';
-train_native.native_rnn_train_step on ggnn_sparse_rnn_train_forward_f32 / ggnn_sparse_rnn_train_backward_f32): gradients against
+train_native.ROUTES, entry `rnn`, on ggnn_sparse_rnn_train_forward_f32 / ggnn_sparse_rnn_train_backward_f32): gradients against
 float64 with the cell's kernel and bias as leaves, the route taken, the step against the key-True route (variants.CompactRnnStepFn),
 determinism, consecutive steps, the fall-backs and the reference's recorded run (chem_tensorflow_sparse.py:109-110, 117-218,
 chem_tensorflow.py:183-191).

@@ -67,7 +67,7 @@ def _expected_gru_formats(pkg, model):
 
 @pytest.mark.parametrize("config,keeps", SMALL_CONFIGS, ids=SMALL_IDS)
 def test_native_step_gradients_match_fp64(pkg, oracle, oracle_torch, cuda, config, keeps, monkeypatch):
-    """train_native.native_train_step: forward and backward launch sequences, readout + loss backward, the 1 / keep scaling of
+    """train_native.native_step on the default route: forward and backward launch sequences, readout + loss backward, the 1 / keep scaling of
     the dropped weights' gradient views and the per-task d_stats factors -- the gradient handed to clip + Adam equals the fp64
     oracle's (2e-4 of the variable's largest entry, as the other gradient tests)."""
     monkeypatch.setattr(pkg.formats._local, "policy", "auto", raising=False)

@@ -1,5 +1,5 @@
 """The native training step of the default sparse model at hidden sizes 128 / 192 / 256 (params['native_panel_training'];
-train_native.native_panel_train_step on the panel route of csrc/ggnn_train.hip): the gradient the optimiser consumes against float64
+train_native.ROUTES, entry `panel`, on the panel route of csrc/ggnn_train.hip): the gradient the optimiser consumes against float64
 autograd of the oracle with proof that the two-call step ran, the step against the autograd step it replaces, its determinism,
 the one-launch image preparation against per-layer packing bit for bit, the accumulate form of the row-split product
 (ggnn_gemm_tn_acc_f32), and everything that keeps the old step."""
@@ -29,15 +29,15 @@ PANEL_IDS = ["h128", "h192-sum-relu-residual", "h256-dropout-two-tasks", "h128-u
 
 
 def _count_routes(pkg, monkeypatch):
-    """Counters on the three places a step can go through: the native panel step, the autograd route's fused GRU backward, and the
-    autograd forward."""
+    """Counters on the three places a step can go through: the native step on the panel route, the autograd route's fused GRU
+    backward, and the autograd forward."""
     calls = {"native_panel": 0, "gru_bwd_fused": 0, "forward_batch": 0}
-    native, fused = pkg.train_native.native_panel_train_step, pkg.ops.gru_bwd_fused
+    native, fused = pkg.train_native.native_step, pkg.ops.gru_bwd_fused
     forward = pkg.SparseGGNNChemModel.forward_batch
 
-    def native_counted(*a, **k):
-        calls["native_panel"] += 1
-        return native(*a, **k)
+    def native_counted(route, *a, **k):
+        calls["native_panel"] += route.name == "panel"
+        return native(route, *a, **k)
 
     def fused_counted(*a, **k):
         calls["gru_bwd_fused"] += 1
@@ -47,7 +47,7 @@ def _count_routes(pkg, monkeypatch):
         calls["forward_batch"] += 1
         return forward(self, *a, **k)
 
-    monkeypatch.setattr(pkg.train_native, "native_panel_train_step", native_counted)
+    monkeypatch.setattr(pkg.train_native, "native_step", native_counted)
     monkeypatch.setattr(pkg.ops, "gru_bwd_fused", fused_counted)
     monkeypatch.setattr(pkg.SparseGGNNChemModel, "forward_batch", forward_counted)
     return calls
@@ -57,7 +57,7 @@ def _count_routes(pkg, monkeypatch):
 def test_native_panel_step_gradients_match_fp64(pkg, oracle, oracle_torch, cuda, config, keeps, monkeypatch):
     """One train_batch per configuration with the key set: loss to 1e-5 relative, every variable's gradient to the project's bound
     (2e-4 of its largest entry) against the fp64 oracle, dropped weights without gradient -- and the step was ONE call of
-    native_panel_train_step, with no fused-GRU-backward op call and no autograd forward."""
+    native_step on the panel route, with no fused-GRU-backward op call and no autograd forward."""
     calls = _count_routes(pkg, monkeypatch)
     model, layers, feed = _small(pkg, oracle, dict(config, **{KEY: True}), keeps)
     assert model.num_edge_types == (8 if config.get("tie_fwd_bkwd") is False else 4)

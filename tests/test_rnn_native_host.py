@@ -252,18 +252,67 @@ def test_model_predicate_per_disqualifying_config(pkg, monkeypatch):
 
 
 def test_train_step_dispatch_order(pkg, monkeypatch):
-    """train_step asks the predicates in the order default, attention, panel, RNN, dense, GCN and takes the first that holds: the
-    order of the existing five is what it was, the new one sits behind the sparse model's other two."""
+    """train_step asks the predicates of train_native.ROUTES in the order default, attention, panel, RNN, dense, GCN and takes the
+    first that holds: the order of the existing five is what it was, the new one sits behind the sparse model's other two.  Each
+    entry's predicates are the module's functions of the matching names."""
     tn = pkg.train_native
-    pairs = [("eligible", "native_train_step"), ("attn_eligible", "native_attn_train_step"), ("panel_eligible", "native_panel_train_step"),
-             ("rnn_eligible", "native_rnn_train_step"), ("dense_eligible", "native_dense_train_step"),
-             ("gcn_eligible", "native_gcn_train_step")]
-    for k in range(len(pairs)):
+    names = [r.name for r in tn.ROUTES]
+    assert names == ["default", "attention", "panel", "rnn", "dense", "gcn"]
+    assert [n for n in names if n != "rnn"] == ["default", "attention", "panel", "dense", "gcn"]
+    preds = ["eligible", "attn_eligible", "panel_eligible", "rnn_eligible", "dense_eligible", "gcn_eligible"]
+    for route, pred in zip(tn.ROUTES, preds):
+        assert route.eligible is getattr(tn, pred), route.name
+        assert route.model_eligible is getattr(tn, pred.replace("eligible", "model_eligible")), route.name
+    real = tn.ROUTES
+    monkeypatch.setattr(tn, "native_step", lambda route, model, batch: "stepped on " + route.name)
+    for k in range(len(real)):
         asked = []
-        for i, (pred, step) in enumerate(pairs):
-            monkeypatch.setattr(tn, pred, lambda model, batch, _n=pred, _v=(i >= k): (asked.append(_n), _v)[1])
-            monkeypatch.setattr(tn, step, lambda model, batch, _n=step: _n)
-        assert pkg.train.train_step(object(), {}) == pairs[k][1]
-        assert asked == [p for p, _ in pairs[:k + 1]]
-    existing = [p for p, _ in pairs if p != "rnn_eligible"]
-    assert existing == ["eligible", "attn_eligible", "panel_eligible", "dense_eligible", "gcn_eligible"]
+        fakes = tuple(r._replace(eligible=lambda model, batch, _n=r.name, _v=(i >= k): (asked.append(_n), _v)[1])
+                      for i, r in enumerate(real))
+        monkeypatch.setattr(tn, "ROUTES", fakes)
+        assert pkg.train.train_step(object(), {}) == "stepped on " + names[k]
+        assert asked == names[:k + 1]
+
+
+def _looks_like_a_gpu_model(m):
+    """What test_model_predicate_per_disqualifying_config's verdict() stands in for: the model is said to live on a GPU and its
+    optimizer -- which keeps flat buffers on a GPU only -- is said to have them.  Nothing runs on a device."""
+    m.device = torch.device("cuda:0")
+    if not m.optimizer.fused:
+        m.optimizer._flat = {}
+    assert m.optimizer.fused
+    return m
+
+
+# (model class, config with its opt-in key, the key(s) whose absence keeps autograd, the one route that takes it)
+EXCLUSIVE = {
+    "default-h32": ("SparseGGNNChemModel", dict(hidden_size=32), (), "default"),
+    "default-h64": ("SparseGGNNChemModel", dict(hidden_size=64), (), "default"),
+    "default-h100": ("SparseGGNNChemModel", dict(hidden_size=100), (), "default"),
+    "attention": ("SparseGGNNChemModel", dict(hidden_size=64, use_propagation_attention=True, compact_attention="native"),
+                  ("compact_attention",), "attention"),
+    "panel-h128": ("SparseGGNNChemModel", dict(hidden_size=128, native_panel_training=True), ("native_panel_training",), "panel"),
+    "rnn": ("SparseGGNNChemModel", dict(README, hidden_size=32, compact_rnn="native"), ("compact_rnn",), "rnn"),
+    "dense": ("DenseGGNNChemModel", dict(batch_size=8, graph_resident_training="native"), ("graph_resident_training",), "dense"),
+    "gcn-h64": ("SparseGCNChemModel", dict(hidden_size=64, native_training=True), ("native_training",), "gcn"),
+    "gcn-panel-h128": ("SparseGCNChemModel", dict(hidden_size=128, native_training=True, gcn_panel_layers=True), ("native_training",),
+                       "gcn"),
+}
+
+
+@pytest.mark.parametrize("case", list(EXCLUSIVE))
+def test_model_predicates_are_mutually_exclusive(pkg, monkeypatch, case):
+    """What lets a table stand for an ordered chain: a model that looks like a GPU model is taken by exactly one route's model
+    predicate, the expected one, and by none once its opt-in key is gone (the default route has no key: it is its own twin)."""
+    cls, config, keys, want = EXCLUSIVE[case]
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    ms = pkg.synthetic_qm9(10, mean_nodes=6, seed=3)
+
+    def takers(cfg):
+        m = getattr(pkg, cls)({"--quiet": True, "--device": "cpu", "train_data": ms, "valid_data": ms,
+                               "--config": dict(cfg, pack_on_device=False)})
+        return [r.name for r in pkg.train_native.ROUTES if r.model_eligible(_looks_like_a_gpu_model(m))]
+
+    assert takers(config) == [want]
+    if keys:
+        assert takers({k: v for k, v in config.items() if k not in keys}) == []

@@ -11,7 +11,7 @@ Three legs (all by default, `--leg kernel|forward|step` for one):
             8 TB/s roof they reach.  Both outputs are compared first (max |difference|).
   forward   the inference forward (compute_final_node_representations under no_grad), `--fwd-iters` forwards per round
   step      one training step (train_batch; edge-weight dropout 0.8 as the reference trains), `--step-iters` steps per round.  A
-            third arm, `native`, is the key-on model with compact_attention = 'native' (train_native.native_attn_train_step: two C
+            third arm, `native`, is the key-on model with compact_attention = 'native' (train_native.ROUTES, entry `attention`: two C
             calls for the propagation instead of the autograd loop); its yardstick is the `compact` arm of the same run.  Per arm
             also `host`: the wall-clock ms per step until the `--step-iters` train_batch calls have RETURNED (before the device is
             waited for) -- the launching thread's share of the step; where it is below the device-event time the step is bound by

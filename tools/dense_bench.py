@@ -11,7 +11,7 @@ training and validation), the dense model's default params (batch_size 256, hidd
 Run from the repository root:  python tools/dense_bench.py [--graphs 50000]
 --leg pack: only device packing of `--iters` batches (for a kernel trace).
 --graph-resident [native]: the epoch leg with params['graph_resident_training'] True (the graph-resident forward and backward
-  launches under torch.autograd) or 'native' (the native step, train_native.native_dense_train_step).
+  launches under torch.autograd) or 'native' (the native step, train_native.ROUTES, entry `dense`).
 --leg step: one training step of a 256-graph batch at v = 16 and v = 29 (D 100, 4 edge types, 4 timesteps) on the per-timestep
   route, on the graph-resident route and on the native step, in ONE process with the routes alternating in interleaved rounds; device
   events around whole steps that end in a synchronise; median / min / max per route and the median of every round, plus the host time

@@ -13,7 +13,7 @@ Four legs (all by default, `--leg cell,step` for some):
   forward   the inference forward (compute_final_node_representations under no_grad), `--fwd-iters` forwards per round
   step      one training step (train_batch; edge-weight dropout as the reference trains), `--step-iters` steps per round; per arm
             also `host`: the wall-clock ms per step until the train_batch calls have RETURNED (the launching thread's share).
-            A third arm, `native`: the key 'native' (train_native.native_rnn_train_step: two native calls, no torch.autograd),
+            A third arm, `native`: the key 'native' (train_native.ROUTES, entry `rnn`: two native calls, no torch.autograd),
             judged against the `compact` arm (the key True).
   cell-bwd  the cell's backward alone on the same inputs: ggnn_act_bwd_f32 + ggnn_bwd_dx_f32 (`launches`) against the one
             ggnn_rnn_bwd_fused_f32 launch (`fused`), and with a deferred node sum ggnn_gather_segment_sum_heads_f32 in front of

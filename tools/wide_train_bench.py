@@ -1,7 +1,7 @@
 """One training step of the sparse model on the config-5 graph (100,000 nodes / 1,000,000 edges / 4 edge types / h = 256 / 8
 timesteps) with the column-panel GRU backward on the compacted route, and with ops.gru_bwd_is_fused switched off (the route before
 the panel kernel existed: dense-form transform, unfused GRU backward), interleaved in one process.  Prints one JSON line.
---route native: the native two-call step (params['native_panel_training'], train_native.native_panel_train_step) against the
+--route native: the native two-call step (params['native_panel_training'], train_native.ROUTES, entry `panel`) against the
 autograd step (`fused`) on a second model with the same config, interleaved in the same way; every arm then also reports the
 launching thread's busy time per step (the time to enqueue a round's steps, before the device is waited for).
 --shape qm9: a QM9-sized batch (~1e5 nodes, ~2e5 messages, h = 128, the default layer structure) instead of the config-5 graph.
