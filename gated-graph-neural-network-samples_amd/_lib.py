@@ -128,6 +128,16 @@ SYMBOLS = {
                                               POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                               POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_int,
                                               POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    # CudnnCompatibleGRUCell in one launch (ggnn_cudnn_gru_fused.hip) and the Cudnn form of the one-call driver
+    "ggnn_cudnn_gru_fused_supported": (c_int, [c_int, c_int]),
+    "ggnn_cudnn_gru_packed_bytes": (c_size_t, [c_int, c_int]),
+    "ggnn_cudnn_gru_pack_weights_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ggnn_cudnn_gru_fused_launch_geometry": (None, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "ggnn_cudnn_gru_packed_f32": (c_int, [POINTER(c_void_p), c_int] + [c_void_p] * 10 + [c_int, c_int, c_void_p]),
+    "ggnn_sparse_propagate_cudnn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "ggnn_sparse_propagate_cudnn_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                                c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)] +
+                                        [POINTER(c_void_p)] * 10 + [POINTER(c_int32), POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "ggnn_gru_bwd_stage1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ggnn_gru_bwd_stage2_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -15,6 +15,10 @@
 // ggnn_rnn_panel_gather_f32 on panel images) for a layer with packed
 // images, a supported (D, nx) and no edge bias, ggnn_gather_segment_sum_f32 + ggnn_rnn_f32 (3 kernels) otherwise -- always behind
 // the compacted transform.  Without one the GRU entry points launch exactly what they launched before.
+//
+// With a CudnnCell (ggnn_sparse_propagate_cudnn_f32; graph_rnn_cell = CudnnCompatibleGRUCell, :105-108) the node update is that cell,
+// always behind the compacted transform and ggnn_gather_segment_sum_f32 over the compact rows (edge bias included):
+// ggnn_cudnn_gru_packed_f32 (one launch) for a layer with packed images and a supported (D, nx), ggnn_cudnn_gru_f32 (three) otherwise.
 #include "ggnn_common.h"
 #include <cstring>
 
@@ -50,8 +54,24 @@ struct RnnCell {
     int64_t M;
 };
 
+// the CudnnCompatibleGRUCell's per-layer weights (HOST arrays of num_layers DEVICE pointers); packed: ggnn_cudnn_gru_pack_weights_f32
+struct CudnnCell {
+    const float* const* wg;
+    const float* const* bg;
+    const float* const* wcx;
+    const float* const* bcx;
+    const float* const* wch;
+    const float* const* bch;
+    const float* const* packed;
+};
+
+extern "C" size_t ggnn_sparse_propagate_cudnn_workspace_bytes(int V, int D, int T, int64_t compact_rows) {
+    const size_t base = ggnn_sparse_propagate_workspace_bytes(V, D, T, compact_rows);
+    return base ? base + ggnn_cudnn_gru_workspace_bytes(V, D) + 256 : 0;
+}
+
 static int propagate(
-        const RnnCell* rnn, const float* h0, int V, int D, int T,
+        const RnnCell* rnn, const CudnnCell* cud, const float* h0, int V, int D, int T,
         const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
         const float* nin, int use_avg,
         int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
@@ -64,16 +84,18 @@ static int propagate(
     GGNN_CHECK_ARG(num_layers > 0 && layer_timesteps && res_ptr && layer_out, "bad layer description");
     GGNN_CHECK_ARG(edge_w || edge_packed, "edge weights missing");
     if (rnn) GGNN_CHECK_ARG(rnn->b && (rnn->packed || rnn->w) && rnn->M >= 0, "RNN weights missing");
+    else if (cud) GGNN_CHECK_ARG(cud->bg && cud->bcx && cud->bch && (cud->packed || (cud->wg && cud->wcx && cud->wch)), "Cudnn GRU weights missing");
     else GGNN_CHECK_ARG(bg && bc && (gru_packed || (Wg && Wc)), "GRU weights missing");
     const bool compact = pair_node != nullptr && type_row_off != nullptr;
     GGNN_CHECK_ARG(!rnn || compact, "the RNN cell runs on the compacted transform only (pair_node, type_row_off)");
+    GGNN_CHECK_ARG(!cud || compact, "the CudnnCompatibleGRUCell runs on the compacted transform only (pair_node, type_row_off)");
     if (V == 0) return GGNN_OK;
     GGNN_CHECK_ARG(h0 && row_ptr && ws, "null pointer");
     GGNN_CHECK_ARG(!attn_factors || compact, "propagation attention needs the compacted transform (pair_node, type_row_off)");
     const int64_t rows = compact ? type_row_off[T] : -1;
-    if (ws_bytes < ggnn_sparse_propagate_workspace_bytes(V, D, T, rows))
-        return ggnn::fail(GGNN_E_WORKSPACE, "propagate workspace too small: %zu < %zu", ws_bytes,
-                          ggnn_sparse_propagate_workspace_bytes(V, D, T, rows));
+    const size_t ws_need = cud ? ggnn_sparse_propagate_cudnn_workspace_bytes(V, D, T, rows) : ggnn_sparse_propagate_workspace_bytes(V, D, T, rows);
+    if (ws_bytes < ws_need)
+        return ggnn::fail(GGNN_E_WORKSPACE, "propagate workspace too small: %zu < %zu", ws_bytes, ws_need);
     const size_t vd = (size_t)V * D * sizeof(float);
     char* p = reinterpret_cast<char*>((reinterpret_cast<size_t>(ws) + 255) / 256 * 256);
     float* H = reinterpret_cast<float*>(bump(p, compact ? (size_t)(rows > 0 ? rows : 1) * D * sizeof(float)
@@ -84,6 +106,9 @@ static int propagate(
     int32_t* counters = reinterpret_cast<int32_t*>(bump(p, kTileCounters * sizeof(int32_t)));
     void* gru_ws = p;
     const size_t gru_ws_bytes = ggnn_gru_workspace_bytes(V, D);
+    p += (gru_ws_bytes + 255) / 256 * 256;
+    void* cud_ws = p;                              // (CudnnCell only: the composed cell's r*h | u | r | hc)
+    const size_t cud_ws_bytes = ggnn_cudnn_gru_workspace_bytes(V, D);
     int step_no = 0;
     // The counters are zero before their GRU launches.  The compacted transform of a timestep precedes that timestep's GRU on the
     // stream and zeroes its counter itself (ggnn::msg_transform_compact_zero: one thread's store, no fill launch in front of the
@@ -116,13 +141,13 @@ static int propagate(
         const float* cur = states[l];              // :152
         const int steps = layer_timesteps[l];
         const float* bias_l = edge_bias ? edge_bias[l] : nullptr;
-        const bool packed_gru = !rnn && gru_packed && gru_packed[l] && ggnn_gru_is_fused(D) && nx <= 3;
+        const bool packed_gru = !rnn && !cud && gru_packed && gru_packed[l] && ggnn_gru_is_fused(D) && nx <= 3;
         const int fmt_l = gru_fmt ? gru_fmt[l] : GGNN_GRU_FMT_BF16X3;      // the format gru_packed[l] was packed in
         // fuse_gather = the largest number of concatenated GRU inputs (residuals + messages) for which the segment sum
         // is gathered inside the GRU kernel; 0 = never.
         const float* factors_l = attn_factors ? attn_factors[l] : nullptr;
         GGNN_CHECK_ARG(!attn_factors || factors_l, "attn_factors[%d] is null", l);
-        const bool gather_in_gru = !rnn && !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
+        const bool gather_in_gru = !rnn && !cud && !attn_factors && fuse_gather > 0 && nx <= fuse_gather && packed_gru && ggnn_gru_is_fused(D) == 1 && bias_l == nullptr &&
                                    (unsigned long long)V * T * D < (1ULL << 30);      // (its 32-bit byte offsets)
         // (the two supported sets are disjoint: rnn->packed[l] holds the images of whichever cell takes (D, nx))
         const bool panel_rnn = rnn && ggnn_rnn_panel_supported(D, nx);
@@ -130,6 +155,11 @@ static int propagate(
                                    (panel_rnn || ggnn_rnn_fused_supported(D, nx)) && bias_l == nullptr &&
                                    (unsigned long long)V * D < (1ULL << 30) && (unsigned long long)(rows > 0 ? rows : 1) * D < (1ULL << 30);
         if (rnn) GGNN_CHECK_ARG(rnn->b[l] && (gather_in_rnn || (rnn->w && rnn->w[l])), "layer %d needs raw RNN weights (no fused cell for it)", l);
+        const bool packed_cud = cud && cud->packed && cud->packed[l] && ggnn_cudnn_gru_fused_supported(D, nx) &&
+                                (unsigned long long)V * D < (1ULL << 30);
+        if (cud) GGNN_CHECK_ARG(cud->bg[l] && cud->bcx[l] && cud->bch[l] &&
+                                (packed_cud || (cud->wg && cud->wcx && cud->wch && cud->wg[l] && cud->wcx[l] && cud->wch[l])),
+                                "layer %d needs raw Cudnn GRU weights (no fused cell for it)", l);
         for (int s = 0; s < steps; ++s) {          // :153
             int rc;
             static const bool dyn_tiles = [] { const char* e = getenv("GGNN_DYN_TILES"); return !e || atoi(e) != 0; }();
@@ -158,6 +188,15 @@ static int propagate(
                 rc = ggnn_gather_segment_sum_f32(H, row_ptr, gather_row, nin, bias_l, use_avg, incoming, V, D, T, stream);
                 if (rc) return rc;
                 rc = ggnn_rnn_f32(xs, nx, cur, rnn->w[l], rnn->b[l], out, V, D, act, stream);
+            } else if (cud) {
+                rc = ggnn_gather_segment_sum_f32(H, row_ptr, gather_row, nin, bias_l, use_avg, incoming, V, D, T, stream);
+                if (rc) return rc;
+                if (packed_cud)
+                    rc = ggnn_cudnn_gru_packed_f32(xs, nx, cur, cud->packed[l], cud->bg[l], cud->bcx[l], cud->bch[l], out, nullptr,
+                                                   nullptr, nullptr, nullptr, V, D, stream);
+                else
+                    rc = ggnn_cudnn_gru_f32(xs, nx, cur, cud->wg[l], cud->bg[l], cud->wcx[l], cud->bcx[l], cud->wch[l], cud->bch[l], out,
+                                            cud_ws, cud_ws_bytes, V, D, stream);
             } else if (gather_in_gru) {
                 rc = ggnn_gru_packed_gather_f32(xs, nx, cur, gru_packed[l], bg[l], bc[l], out, H, row_ptr, gather_row, nin, T,
                                                 use_avg, V, D, act, fmt_l, counter, stream);
@@ -195,7 +234,7 @@ extern "C" int ggnn_sparse_propagate_f32(
         const float* const* Wg, const float* const* bg, const float* const* Wc, const float* const* bc,
         const float* const* gru_packed, const int32_t* gru_fmt, const int32_t* edge_fmt, int act, int fuse_gather,
         float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
-    return propagate(nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+    return propagate(nullptr, nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
                      res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
                      layer_out, ws, ws_bytes, nullptr, nullptr, stream);
 }
@@ -212,7 +251,7 @@ extern "C" int ggnn_sparse_propagate_attn_f32(
         ggnn_stream_t stream) {
     GGNN_CHECK_ARG(attn_factors, "attn_factors is null");
     if (D > 256) return ggnn::fail(GGNN_E_UNSUPPORTED, "propagation attention supports hidden sizes up to 256 (got %d)", D);
-    return propagate(nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+    return propagate(nullptr, nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
                      res_idx, edge_w, edge_packed, edge_bias, Wg, bg, Wc, bc, gru_packed, gru_fmt, edge_fmt, act, fuse_gather,
                      layer_out, ws, ws_bytes, slot_pair, attn_factors, stream);
 }
@@ -229,7 +268,23 @@ extern "C" int ggnn_sparse_propagate_rnn_f32(
     GGNN_CHECK_ARG(pair_node && type_row_off, "the RNN cell runs on the compacted transform only (pair_node, type_row_off)");
     GGNN_CHECK_ARG(act == GGNN_ACT_TANH || act == GGNN_ACT_RELU, "unknown activation %d", act);
     const RnnCell cell{rnn_w, rnn_b, rnn_packed, M};
-    return propagate(&cell, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
+    return propagate(&cell, nullptr, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps, res_ptr,
                      res_idx, edge_w, edge_packed, edge_bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, edge_fmt, act,
                      fuse_gather, layer_out, ws, ws_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int ggnn_sparse_propagate_cudnn_f32(
+        const float* h0, int V, int D, int T,
+        const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node, const int64_t* type_row_off,
+        const float* nin, int use_avg,
+        int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+        const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+        const float* const* wg, const float* const* bg, const float* const* wcx, const float* const* bcx,
+        const float* const* wch, const float* const* bch, const float* const* cell_packed,
+        const int32_t* edge_fmt, float* const* layer_out, void* ws, size_t ws_bytes, ggnn_stream_t stream) {
+    GGNN_CHECK_ARG(pair_node && type_row_off, "the CudnnCompatibleGRUCell runs on the compacted transform only (pair_node, type_row_off)");
+    const CudnnCell cell{wg, bg, wcx, bcx, wch, bch, cell_packed};
+    return propagate(nullptr, &cell, h0, V, D, T, row_ptr, gather_row, pair_node, type_row_off, nin, use_avg, num_layers, layer_timesteps,
+                     res_ptr, res_idx, edge_w, edge_packed, edge_bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, edge_fmt,
+                     GGNN_ACT_TANH, 0, layer_out, ws, ws_bytes, nullptr, nullptr, stream);
 }

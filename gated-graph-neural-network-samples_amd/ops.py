@@ -1080,6 +1080,11 @@ class PackedWeights:
         weight version.  (nx, D) must be in the supported set: rnn_bwd_fused_supported."""
         return self._images.get((W,), ("rnn_bwd", int(nx)), lambda: rnn_bwd_pack(W, nx))
 
+    def cudnn(self, Wg: torch.Tensor, Wcx: torch.Tensor, Wch: torch.Tensor, nx: int, D: int) -> torch.Tensor:
+        """The 3 (nx + 1) exact bf16x3 stage images of the fused CudnnCompatibleGRUCell (ggnn_cudnn_gru_pack_weights_f32), once per
+        weight version.  (nx, D) must be in the supported set: cudnn_gru_fused_supported."""
+        return self._images.get((Wg, Wcx, Wch), ("cudnn", int(nx)), lambda: cudnn_gru_pack(Wg, Wcx, Wch, nx))
+
     def _edge(self, W: torch.Tensor, fmt: int, transposed: bool) -> torch.Tensor:
         def make():
             lib = _lib.load()
@@ -1182,7 +1187,8 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
                      gru_packed: Optional[Sequence[torch.Tensor]], activation: str,
                      fuse_gather: Optional[bool] = None, gru_fmt: Optional[Sequence[int]] = None,
                      edge_fmt: Optional[Sequence[int]] = None, attn: Optional[Sequence[torch.Tensor]] = None,
-                     rnn: Optional[Sequence[Sequence[Optional[torch.Tensor]]]] = None) -> List[torch.Tensor]:
+                     rnn: Optional[Sequence[Sequence[Optional[torch.Tensor]]]] = None,
+                     cudnn: Optional[Sequence[Sequence[Optional[torch.Tensor]]]] = None) -> List[torch.Tensor]:
     """chem_tensorflow_sparse.py:131-218 in ONE native call (ggnn_sparse_propagate_f32): returns
     node_states_per_layer[1:], the last entry being the final node representations.
     gru_fmt / edge_fmt: per layer, the operand format gru_packed[l] / edge_packed[l] was packed in (None: BF16X3 for every layer).
@@ -1190,7 +1196,9 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
     attn: per layer, the [T] edge_type_attention_weights (:94-96): the propagation-attention form of the loop
     (ggnn_sparse_propagate_attn_f32; needs `comp`).
     rnn: (W per layer, b per layer, packed images per layer | None) of the BasicRNNCell: the RNN form of the loop
-    (ggnn_sparse_propagate_rnn_f32; needs `comp`; Wg / bg / Wc / bc / gru_packed are not read)."""
+    (ggnn_sparse_propagate_rnn_f32; needs `comp`; Wg / bg / Wc / bc / gru_packed are not read).
+    cudnn: (Wg, bg, Wcx, bcx, Wch, bch, packed images | None), each per layer, of the CudnnCompatibleGRUCell: the Cudnn form of the
+    loop (ggnn_sparse_propagate_cudnn_f32; needs `comp`; Wg / bg / Wc / bc / gru_packed / activation are not read)."""
     if fuse_gather is None:
         fuse_gather = FUSE_GATHER
     lib = _lib.load()
@@ -1212,6 +1220,18 @@ def sparse_propagate(h0: torch.Tensor, index: MessageIndex, comp: Optional[Compa
     i32 = lambda xs: (ctypes.c_int32 * max(len(xs), 1))(*xs)
     off = None if comp is None else (ctypes.c_int64 * (T + 1))(*comp.type_row_off)
     gather = index.gather_row if comp is None else comp.gather_row
+    if cudnn is not None:
+        if comp is None or attn is not None or rnn is not None or len(cudnn) != 7 or any(len(x) != L for x in cudnn[:6]):
+            raise ValueError("the Cudnn cell's one-call form needs the compacted transform, no attention, and six weight lists of one "
+                             "entry per layer plus the packed images")
+        ws_bytes = lib.ggnn_sparse_propagate_cudnn_workspace_bytes(V, D, T, rows)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=h0.device)
+        _launch("sparse_propagate_cudnn", lambda: lib.ggnn_sparse_propagate_cudnn_f32(
+            _ptr(h0), V, D, T, _ptr(index.row_ptr), _ptr(gather), _ptr(comp.pair_node), off,
+            _ptr(nin), 1 if use_avg else 0, L, i32([int(x) for x in layer_timesteps]), i32(res_ptr), i32(res_idx),
+            _ptr_array(edge_w), _ptr_array(edge_packed), _ptr_array(edge_bias), *[_ptr_array(x) for x in cudnn],
+            None if edge_fmt is None else i32([int(f) for f in edge_fmt]), _ptr_array(outs), _ptr(ws), ws_bytes, _stream()))
+        return outs
     if rnn is not None:
         rnn_w, rnn_b, rnn_packed = rnn
         if comp is None or attn is not None or len(rnn_w) != L or len(rnn_b) != L:
@@ -1278,6 +1298,64 @@ def gru_packed_gather(residual_segs: Sequence[torch.Tensor], h: torch.Tensor, pa
         segs, len(residual_segs) + 1, _ptr(h), _ptr(packed), _ptr(bg), _ptr(bc), _ptr(out), _ptr(H), _ptr(index.row_ptr),
         _ptr(gather), None if nin is None else _ptr(nin), index.num_edge_types, 0 if nin is None else 1, V, D, act, int(fmt),
         _ptr(tile_counter), _stream()))
+    return out
+
+
+def cudnn_gru_fused_supported(D: int, nx: int) -> bool:
+    """True when the CudnnCompatibleGRUCell with nx concatenated inputs (residuals + messages) has the single fused launch at width D
+    (ggnn_cudnn_gru_fused_supported: D = 32 / 64 / 100 with nx <= 3)."""
+    return bool(_lib.load().ggnn_cudnn_gru_fused_supported(int(D), int(nx)))
+
+
+def cudnn_gru_fused_launch_geometry(D: int, nx: int) -> Tuple[int, int]:
+    """(rows a workgroup of the fused CudnnCompatibleGRUCell covers per pass, the most workgroups a launch starts)."""
+    rows, wgs = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().ggnn_cudnn_gru_fused_launch_geometry(int(D), int(nx), ctypes.byref(rows), ctypes.byref(wgs))
+    return rows.value, wgs.value
+
+
+def cudnn_gru_pack(Wg: torch.Tensor, Wcx: torch.Tensor, Wch: torch.Tensor, nx: int) -> torch.Tensor:
+    """Wg [(nx+1) D, 2D], Wcx [nx D, D], Wch [D, D] -> the 3 (nx + 1) stage images of ggnn_cudnn_gru_packed_f32, in the pass's stage
+    order (PackedWeights.cudnn caches them per weight version)."""
+    lib = _lib.load()
+    _req(Wg, torch.float32, "Wg"); _req(Wcx, torch.float32, "Wcx"); _req(Wch, torch.float32, "Wch")
+    if Wch.dim() != 2 or Wch.shape[0] != Wch.shape[1]:
+        raise ValueError("Wch must be [D, D]")
+    D = Wch.shape[1]
+    if tuple(Wg.shape) != ((nx + 1) * D, 2 * D) or tuple(Wcx.shape) != (nx * D, D):
+        raise ValueError("Wg must be [(nx+1)*D, 2*D] and Wcx [nx*D, D]")
+    packed = torch.empty(max(lib.ggnn_cudnn_gru_packed_bytes(D, nx) // 4, 4), dtype=torch.float32, device=Wg.device)
+    check(lib.ggnn_cudnn_gru_pack_weights_f32(_ptr(Wg), _ptr(Wcx), _ptr(Wch), nx, D, _ptr(packed), _stream()))
+    return packed
+
+
+def cudnn_gru_packed(x_segs: Sequence[torch.Tensor], h: torch.Tensor, packed: torch.Tensor, bg: torch.Tensor, bcx: torch.Tensor,
+                     bch: torch.Tensor, save: Optional[dict] = None) -> torch.Tensor:
+    """chem_tensorflow_sparse.py:105-108 in one launch (ggnn_cudnn_gru_packed_f32) on cudnn_gru_pack's images; x_segs: the residual
+    states first, the aggregated messages last.  save (dict): filled with r, u, c, hc [V, D] (training: what the backward reads);
+    h' is bit-identical with and without it."""
+    lib = _lib.load()
+    _req(h, torch.float32, "h"); _req(packed, torch.float32, "packed")
+    _req(bg, torch.float32, "bg"); _req(bcx, torch.float32, "bcx"); _req(bch, torch.float32, "bch")
+    V, D = h.shape
+    for i, x in enumerate(x_segs):
+        _req(x, torch.float32, "x_segs[%d]" % i)
+        if x.shape != (V, D):
+            raise ValueError("x_segs[%d] must be [V,D]" % i)
+    nx = len(x_segs)
+    if bg.numel() != 2 * D or bcx.numel() != D or bch.numel() != D:
+        raise ValueError("bg must be [2D], bcx and bch [D]")
+    if packed.numel() * 4 < lib.ggnn_cudnn_gru_packed_bytes(D, nx):
+        raise ValueError("packed holds fewer than the 3 (nx + 1) images of cudnn_gru_pack")
+    segs = (ctypes.c_void_p * max(nx, 1))(*[s.data_ptr() for s in x_segs])
+    out = torch.empty_like(h)
+    keep = [None] * 4
+    if save is not None:
+        keep = [torch.empty_like(h) for _ in range(4)]
+        save["r"], save["u"], save["c"], save["hc"] = keep
+    _launch("cudnn_gru_packed[nx=%d]" % nx, lambda: lib.ggnn_cudnn_gru_packed_f32(
+        segs, nx, _ptr(h), _ptr(packed), _ptr(bg), _ptr(bcx), _ptr(bch), _ptr(out), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]),
+        _ptr(keep[3]), V, D, _stream()))
     return out
 
 

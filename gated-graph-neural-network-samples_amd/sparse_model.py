@@ -297,6 +297,14 @@ class SparseGGNNChemModel(ChemModel):
         at these widths and stays compact_rnn = True."""
         return bool(self.params.get('rnn_panel_cell')) and self.params.get('compact_rnn') != 'native' and self.rnn_route()
 
+    def cudnn_route(self) -> bool:
+        """True when the CudnnCompatibleGRUCell (:105-108) runs on the compacted fast route: the opt-in key
+        params['compact_cudnn_gru'], no propagation attention, a GPU model and a kernel width that has a compacted transform
+        (32 / 64 / 100 / 128 / 192 / 256 and what pads to them).  Anything else keeps the dense-transform variant route."""
+        p = self.params
+        return bool(p.get('compact_cudnn_gru')) and self.cell_type == 'cudnncompatiblegrucell' \
+            and not p['use_propagation_attention'] and torch.device(self.device).type == 'cuda' and ops.compact_supported(self._kw)
+
     # ---- the hot path -----------------------------------------------------------------------------------
     def compute_final_node_representations(self) -> torch.Tensor:
         """chem_tensorflow_sparse.py:117-218."""
@@ -323,6 +331,16 @@ class SparseGGNNChemModel(ChemModel):
         attn_route = self.attention_route() and h0.is_cuda
         rnn_route = self.rnn_route() and h0.is_cuda
         rnn_panel = rnn_route and self.rnn_panel_route()
+        cudnn_route = self.cudnn_route() and h0.is_cuda
+        if cudnn_route:
+            # (every product of this route runs in the exact format, whatever the process-wide policy says)
+            L = len(self.params['layer_timesteps'])
+            self.last_gru_formats, self.last_edge_formats = [ops.GRU_FMT_EXACT] * L, [ops.GRU_FMT_EXACT] * L
+
+        if cudnn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
+            # inference with the Cudnn cell on the compacted route: ONE native call, the cell one launch where the fused kernel takes it
+            final = self._propagate_native_cudnn(h0, index, nin, use_avg)
+            return final if Dk == h_dim else final[:, :h_dim].contiguous()
 
         if rnn_route and not need_grad and ew_keep >= 1.0 and st_keep >= 1.0 and ops._timing is None:
             # inference with the RNN cell on the compacted route: ONE native call, the cell fused with the segment sum where it can be
@@ -366,11 +384,11 @@ class SparseGGNNChemModel(ChemModel):
                     from .variants import variant_step
                     cur = variant_step(cur, index, nin, edge_weights, edge_biases, attn_w, use_avg, layer_residual_states,
                                        self.cell_type, tuple(cell), act, compact_attention=attn_route, compact_rnn=rnn_route,
-                                       rnn_panel=rnn_panel)
+                                       rnn_panel=rnn_panel, compact_cudnn=cudnn_route)
                 elif variant:
                     cur = self._variant_step(cur, index, nin, edge_weights.contiguous(), edge_biases, attn_w, use_avg,
                                              layer_residual_states, cell, act, compact_attention=attn_route, compact_rnn=rnn_route,
-                                             rnn_panel=rnn_panel)
+                                             rnn_panel=rnn_panel, compact_cudnn=cudnn_route)
                 else:
                     cur = propagation_step(cur, index, nin, edge_weights, edge_biases, use_avg,
                                            layer_residual_states, cell, act, need_grad,
@@ -397,12 +415,18 @@ class SparseGGNNChemModel(ChemModel):
         return uid
 
     def _variant_step(self, h, index, nin, edge_weights, edge_biases, attn_w, use_avg, residual_states, cell, act,
-                      compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False):
+                      compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False,
+                      compact_cudnn: bool = False):
         """One timestep with the non-default switches of chem_tensorflow_sparse.py: propagation attention
         (:147-149, 170-196) and/or the BasicRNNCell / CudnnCompatibleGRUCell cells (:105-110).  Dense transform, unless
         compact_attention (attention_route()): compacted transform, attention sum over the compact rows, packed GRU;
         or compact_rnn (rnn_route()): compacted transform, then the BasicRNNCell with the segment sum gathered inside
-        (ops.rnn_packed_gather) or, for layers it does not take, the segment sum over the compact rows and ops.rnn."""
+        (ops.rnn_packed_gather) or, for layers it does not take, the segment sum over the compact rows and ops.rnn;
+        or compact_cudnn (cudnn_route()): compacted transform, the segment sum over the compact rows, then the
+        CudnnCompatibleGRUCell in one launch (ops.cudnn_gru_packed) or, for layers it does not take, the composed cell."""
+        if compact_cudnn:
+            from .variants import compact_cudnn_forward
+            return compact_cudnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, *cell)[0]
         if compact_rnn:
             from .variants import compact_rnn_forward
             return compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, cell[0], cell[1], act,
@@ -492,6 +516,28 @@ class SparseGGNNChemModel(ChemModel):
         outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals, edge_w, edge_packed,
                                     edge_bias, None, None, None, None, None, act, edge_fmt=[ops.GRU_FMT_EXACT] * L,
                                     rnn=([c.kernel for c in cells], [c.bias for c in cells], rnn_packed))
+        return outs[-1]
+
+    def _propagate_native_cudnn(self, h0, index, nin, use_avg) -> torch.Tensor:
+        """compute_final_node_representations on cudnn_route() through ggnn_sparse_propagate_cudnn_f32: compacted transform on packed
+        edge images, the segment sum over the compact rows, then the fused CudnnCompatibleGRUCell on its packed images (layers the
+        kernel does not take -- more than three inputs, widths 128 / 192 / 256 -- run the composed cell on the raw weights).
+        Every product in the exact format."""
+        from .variants import compact_sources
+        D = self._kw
+        L = len(self.params['layer_timesteps'])
+        comp = compact_sources(index)
+        layers = [self._kernel_layer(l, False) for l in range(L)]
+        edge_w = [lay[0].contiguous() for lay in layers]
+        edge_packed = [ops.PACKED.edge(w) for w in edge_w]
+        edge_bias = [lay[1] for lay in layers] if self.params['use_edge_bias'] else None
+        cells = [tuple(lay[3]) for lay in layers]           # (Wg, bg, Wcx, bcx, Wch, bch)
+        residuals = [self.params['residual_connections'].get(str(l)) or [] for l in range(L)]
+        packed = [ops.PACKED.cudnn(c[0], c[2], c[4], len(residuals[l]) + 1, D)
+                  if ops.cudnn_gru_fused_supported(D, len(residuals[l]) + 1) else None for l, c in enumerate(cells)]
+        outs = ops.sparse_propagate(h0, index, comp, nin, use_avg, self.params['layer_timesteps'], residuals, edge_w, edge_packed,
+                                    edge_bias, None, None, None, None, None, 'tanh', edge_fmt=[ops.GRU_FMT_EXACT] * L,
+                                    cudnn=tuple([c[i] for c in cells] for i in range(6)) + (packed,))
         return outs[-1]
 
     def _graph_nodes_sorted(self) -> bool:

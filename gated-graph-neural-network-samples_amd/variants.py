@@ -18,6 +18,10 @@ gathered inside; `incoming` comes back from the launch) or, for layers that kern
 ops.rnn; the backward is the BasicRNNCell branch below, which runs transform_backward on the compact rows anyway.  With
 params['rnn_panel_cell'] as well (rnn_panel_route) the step is CompactRnnPanelStepFn: at widths 128 / 192 / 256 the forward's cell is
 ops.rnn_panel_gather, `incoming` saved the same way; same backward.
+With params['compact_cudnn_gru'] (SparseGGNNChemModel.cudnn_route: the CudnnCompatibleGRUCell without attention, a width with a
+compacted transform) the step is CompactCudnnStepFn: forward ops.msg_transform_compact_packed -> ops.gather_segment_sum_compact ->
+ops.cudnn_gru_packed (the whole cell in one launch; r, u, c, hc come back from it) or, for layers that kernel does not take,
+ops.cudnn_gru_train; the backward is the CudnnCompatibleGRUCell branch below.
 Hidden sizes beyond the fused kernels' (128 / 192 / 256 and what pads to them) run the same backward on the generic kernels:
 the un-fused GRU backward, ggnn_gemm_tn_f32 / ggnn_colsum_f32 for the weight and bias gradients.  The timestep restated in
 differentiable torch ops lives in tests/variant_oracle.py (a test oracle; BACKWARD_ORACLE below is its hook).
@@ -46,14 +50,20 @@ class VariantStepFn(torch.autograd.Function):
 
     @staticmethod
     def step_forward(ctx, compact_attention, h, index, nin, use_avg, cell_type, activation, num_cell, num_res, edge_weights,
-                     edge_biases, attention_weights, *rest, compact_rnn=False, rnn_panel=False):
+                     edge_biases, attention_weights, *rest, compact_rnn=False, rnn_panel=False, compact_cudnn=False):
         cell, residuals = rest[:num_cell], rest[num_cell:num_cell + num_res]
         h = h.contiguous()
         W = edge_weights.contiguous()
         D = h.shape[1]       # (any kernel width: sizes without a compacted transform kernel take the per-type GEMM in transform_backward)
         ctx.compact_attention = compact_attention
         out = None
-        if compact_rnn:
+        cudnn_saved = None
+        if compact_cudnn:
+            # the CudnnCompatibleGRUCell without attention, a width with a compacted transform: only the active (node, type) rows are
+            # transformed, and the cell is one launch where the fused kernel takes the layer
+            assert attention_weights is None and cell_type == 'cudnncompatiblegrucell'
+            out, incoming, *cudnn_saved = compact_cudnn_forward(h, index, nin, W, edge_biases, use_avg, residuals, *cell)
+        elif compact_rnn:
             # the BasicRNNCell without attention, a width with a compacted transform: only the active (node, type) rows are
             # transformed and the cell gathers its own segment sum where the fused kernel takes the layer
             assert attention_weights is None and cell_type == 'rnn'
@@ -88,7 +98,10 @@ class VariantStepFn(torch.autograd.Function):
             if ctx.hip_backward:
                 extra = [incoming, out]
         else:
-            if ctx.hip_backward:
+            if cudnn_saved is not None:
+                if ctx.hip_backward:
+                    extra = [incoming] + cudnn_saved
+            elif ctx.hip_backward:
                 out, r, u, c, hc = ops.cudnn_gru_train(xs, h, *cell)
                 extra = [incoming, r, u, c, hc]
             else:
@@ -142,6 +155,32 @@ class CompactRnnPanelStepFn(VariantStepFn):
     @staticmethod
     def forward(ctx, *args):
         return VariantStepFn.step_forward(ctx, False, *args, compact_rnn=True, rnn_panel=True)
+
+
+class CompactCudnnStepFn(VariantStepFn):
+    """VariantStepFn with the CudnnCompatibleGRUCell step on the compacted route; same arguments, same saved tensors, same backward
+    hook."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return VariantStepFn.step_forward(ctx, False, *args, compact_cudnn=True)
+
+
+def compact_cudnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, Wg, bg, Wcx, bcx, Wch, bch):
+    """One CudnnCompatibleGRUCell timestep on the compacted route -> (h', incoming, r, u, c, hc): the compacted transform on packed
+    edge images, the segment sum over the compact rows (edge bias included), then the cell in one launch (ops.cudnn_gru_packed) where
+    ops.cudnn_gru_fused_supported takes the layer; otherwise ops.cudnn_gru_train.  The dense [V, T*D] product is never formed."""
+    comp = compact_sources(index)
+    D, nx = h.shape[1], len(residual_states) + 1
+    Hc = ops.msg_transform_compact_packed(h, ops.PACKED.edge(edge_weights), edge_weights.shape[0], comp)
+    incoming = ops.gather_segment_sum_compact(Hc, index, comp, nin, edge_biases, use_avg)
+    xs = list(residual_states) + [incoming]
+    if ops.cudnn_gru_fused_supported(D, nx):
+        save = {}
+        out = ops.cudnn_gru_packed(xs, h, ops.PACKED.cudnn(Wg, Wcx, Wch, nx, D), bg, bcx, bch, save=save)
+        return out, incoming, save["r"], save["u"], save["c"], save["hc"]
+    out, r, u, c, hc = ops.cudnn_gru_train(xs, h, Wg, bg, Wcx, bcx, Wch, bch)
+    return out, incoming, r, u, c, hc
 
 
 def compact_rnn_forward(h, index, nin, edge_weights, edge_biases, use_avg, residual_states, W, b, activation, panel=False):
@@ -251,10 +290,15 @@ def _hip_backward(ctx, g, h, nin, W, bias, attn, cell, residuals, extra):
 
 def variant_step(h, index, nin, edge_weights, edge_biases: Optional[torch.Tensor], attention_weights: Optional[torch.Tensor],
                  use_avg: bool, residual_states: Sequence[torch.Tensor], cell_type: str, cell: Sequence[torch.Tensor],
-                 activation: str, compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False) -> torch.Tensor:
+                 activation: str, compact_attention: bool = False, compact_rnn: bool = False, rnn_panel: bool = False,
+                 compact_cudnn: bool = False) -> torch.Tensor:
     """compact_attention: the step of SparseGGNNChemModel.attention_route() (attention, GRU cell, a compacted-transform width);
     compact_rnn: the step of SparseGGNNChemModel.rnn_route() (BasicRNNCell, no attention, a compacted-transform width);
-    rnn_panel: with it, the panel cell where it takes the layer (SparseGGNNChemModel.rnn_panel_route())."""
+    rnn_panel: with it, the panel cell where it takes the layer (SparseGGNNChemModel.rnn_panel_route());
+    compact_cudnn: the step of SparseGGNNChemModel.cudnn_route() (CudnnCompatibleGRUCell, no attention, a compacted-transform width)."""
+    if compact_cudnn:
+        return CompactCudnnStepFn.apply(h, index, nin, use_avg, cell_type, activation, len(cell), len(residual_states), edge_weights,
+                                        edge_biases, attention_weights, *cell, *residual_states)
     fn = (CompactRnnPanelStepFn if rnn_panel else CompactRnnStepFn) if compact_rnn else CompactAttentionStepFn if compact_attention else VariantStepFn
     return fn.apply(h, index, nin, use_avg, cell_type, activation, len(cell), len(residual_states), edge_weights,
                     edge_biases, attention_weights, *cell, *residual_states)

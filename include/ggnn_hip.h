@@ -579,6 +579,55 @@ int ggnn_sparse_propagate_rnn_f32(const float* h0, int V, int D, int T,
                                   const int32_t* edge_fmt, int act, int fuse_gather, float* const* layer_out, void* ws,
                                   size_t ws_bytes, ggnn_stream_t stream);
 
+/* ---- CudnnCompatibleGRUCell in one launch (chem_tensorflow_sparse.py:105-108; replaces the three launches of ggnn_cudnn_gru_f32) --
+ *     [r|u] = sigmoid([x_0|..|x_{nx-1}|h] Wg + bg);  hc = h Wch + bch;  c = tanh([x_0|..|x_{nx-1}] Wcx + bcx + r * hc)
+ *     h'    = u*h + (1-u)*c                              x_{nx-1}: the aggregated messages, an ordinary input segment here
+ * The 3 (nx + 1) weight blocks [D, D] stream through a two-slot LDS-DMA ring as exact bf16x3 stage images (ggnn_cudnn_gru_fused.hip);
+ * r, u and hc stay in registers.  Accumulation order is fixed (r / u: the x segments in order, h last; cx: the x segments in order;
+ * ch: h alone), so h' is bit-identical from run to run and with or without the saves.
+ *   ggnn_cudnn_gru_fused_supported(D, nx)  (:102-108) 1 for D in {32, 64, 100} with nx in 1..3; 0 otherwise.  Every entry point below
+ *                                          returns GGNN_E_UNSUPPORTED (packed_bytes: 0, the geometry: 0 / 0) exactly where it is 0.
+ *   ggnn_cudnn_gru_packed_bytes            (:105-108) 3 (nx + 1) images: 8 KiB each at D = 32, 24 KiB at 64, 72 KiB at 100
+ *   ggnn_cudnn_gru_pack_weights_f32        (:105-108) Wg [(nx+1)D, 2D], Wcx [nx D, D], Wch [D, D] -> the images in the pass's stage
+ *                                          order: per x segment its r, u and Wcx columns, then for h its r, u columns and Wch.
+ *                                          Once per weight version.
+ *   ggnn_cudnn_gru_fused_launch_geometry   (:105-108) {rows a workgroup covers per pass, the most workgroups a launch starts}; a
+ *                                          workgroup runs the passes blockIdx, blockIdx + workgroups, .. (no counter, no atomics)
+ *   ggnn_cudnn_gru_packed_f32              (:105-108) the launch.  x_segs: HOST array of the nx segments [V, D].  save_r / save_u /
+ *                                          save_c / save_hc: all NULL, or all [V, D] (training: the tensors the backward reads).
+ *                                          Every pointer 16-byte aligned; h_out must not be h or a segment, a save buffer must not be
+ *                                          an input, h_out or another save buffer (GGNN_E_INVALID, before anything is launched).
+ *                                          V == 0 is a no-op; V*D >= 2^30: GGNN_E_UNSUPPORTED (32-bit byte offsets).
+ *                                          Rows >= V are neither read nor written. */
+int ggnn_cudnn_gru_fused_supported(int D, int nx);
+size_t ggnn_cudnn_gru_packed_bytes(int D, int nx);
+int ggnn_cudnn_gru_pack_weights_f32(const float* Wg, const float* Wcx, const float* Wch, int nx, int D, float* packed,
+                                    ggnn_stream_t stream);
+void ggnn_cudnn_gru_fused_launch_geometry(int D, int nx, int* rows_per_pass, int* max_workgroups);
+int ggnn_cudnn_gru_packed_f32(const float* const* x_segs, int nx, const float* h, const float* packed, const float* bg,
+                              const float* bcx, const float* bch, float* h_out, float* save_r, float* save_u, float* save_c,
+                              float* save_hc, int V, int D, ggnn_stream_t stream);
+
+/* ggnn_sparse_propagate_f32 for graph_rnn_cell = CudnnCompatibleGRUCell (:102-108, 131-218) on the compacted transform.  The compact
+ * form is REQUIRED (pair_node / type_row_off non-NULL, gather_row = the remapped rows; GGNN_E_INVALID otherwise).  Per timestep: the
+ * compacted transform on edge_packed[l] (or raw edge_w[l]), ggnn_gather_segment_sum_f32 over the compact rows (with the layer's edge
+ * bias, if any), then ggnn_cudnn_gru_packed_f32 for a layer with cell_packed[l] and ggnn_cudnn_gru_fused_supported(D, nx), otherwise
+ * ggnn_cudnn_gru_f32 on the raw weights (every layer with nx > 3 and every layer at widths 128 / 192 / 256).
+ *   wg [(nx+1)D, 2D], bg [2D], wcx [nx D, D], bcx [D], wch [D, D], bch [D], cell_packed (ggnn_cudnn_gru_pack_weights_f32; the array
+ *   or single entries may be NULL): HOST arrays of num_layers DEVICE pointers; the raw weight arrays may be NULL when every layer has
+ *   packed images.  ws: ggnn_sparse_propagate_cudnn_workspace_bytes (ggnn_sparse_propagate_workspace_bytes plus the composed cell's
+ *   ggnn_cudnn_gru_workspace_bytes). */
+size_t ggnn_sparse_propagate_cudnn_workspace_bytes(int V, int D, int T, int64_t compact_rows);
+int ggnn_sparse_propagate_cudnn_f32(const float* h0, int V, int D, int T,
+                                    const int32_t* row_ptr, const int32_t* gather_row, const int32_t* pair_node,
+                                    const int64_t* type_row_off, const float* nin, int use_avg,
+                                    int num_layers, const int32_t* layer_timesteps, const int32_t* res_ptr, const int32_t* res_idx,
+                                    const float* const* edge_w, const float* const* edge_packed, const float* const* edge_bias,
+                                    const float* const* wg, const float* const* bg, const float* const* wcx, const float* const* bcx,
+                                    const float* const* wch, const float* const* bch, const float* const* cell_packed,
+                                    const int32_t* edge_fmt, float* const* layer_out, void* ws, size_t ws_bytes,
+                                    ggnn_stream_t stream);
+
 /* ---- (a-B) element-wise stages of the GRU backward (TF autodiff of GRUCell, chem_tensorflow.py:184) -------
  * stage 1: dpc = g*(1-u)*act'(c) -> dpc [V,D];  g*(h-c)*u*(1-u) -> dpg[:, D:2D];  g*u -> dh [V,D];
  *          r*h -> a_c[:, col0:col0+D] (row stride lda: the [x | r*h] operand of the dWc product)
